@@ -14,9 +14,12 @@ random-init), VAE-encode the context view, VAE-decode the 4 targets.  One timed 
 value = N * B * 4 * K / max-over-ranks(wall) -- scenes are sharded over ranks, no data-path collective
 ("weak" scaling).
 
-Extra objects on the JSON line: `roofline` for the dominant kernel family (implicit-GEMM conv/linear;
-per-launch durations measured with HIP events on the launch stream, `mvldm_plan_profile`) and
-`cpu_baseline` (the CPU oracle timed on this host's cores on a bounded sample).
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds every other measurement to it:
+`roofline` for the dominant kernel family (implicit-GEMM conv/linear; per-launch durations measured with HIP events on
+the launch stream, `mvldm_plan_profile`), the other kernel families, small batches, the f16 run and the drift against
+f32, the full walk, the reference's loop shape, the other BASELINE configs, a short training line and `cpu_baseline`
+(the CPU oracle timed on this host's cores on a bounded sample); the `--no-*` options drop single legs of it.
+`--dump-outputs DIR` writes what the last timed step returned as DIR/<name>.npy (float32; see `dump_outputs`).
 """
 from __future__ import annotations
 
@@ -76,6 +79,24 @@ def synthetic_batch(b: int, v_c: int, v_t: int, res: int, seed: int, device, sce
     img = torch.rand(b, v_c, 3, res, res, generator=g).to(device)
     return {"context": {"image": img, "extrinsics": extr[:, :v_c], "intrinsics": intr[:, :v_c]},
             "target": {"extrinsics": extr[:, v_c:], "intrinsics": intr[:, v_c:]}}
+
+
+def dump_outputs(out_dir: str, arrays: dict, cap_bytes: int = 32 << 20, seed: int = 0):
+    """`--dump-outputs`: each array as `out_dir/<name>.npy` in float32.  An array of [scenes, views, ...] larger than
+    `cap_bytes` is cut to a fixed, seeded subset of its (scene, view) entries, [n, ...] in ascending (scene, view) order -- the
+    same subset whenever the arguments are the same (at most 2 arrays x 32 MB).  Each process tunes its own tiles, so two runs can
+    differ by the 16-bit rounding drift (bf16: ~5e-3 relative after 50 DDIM steps); runs that share one MVLDM_TUNE_CACHE file
+    (the first writes it, the next load it) return bit-identical outputs."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach().float()
+        if t.numel() * t.element_size() > cap_bytes:
+            flat = t.reshape(t.shape[0] * t.shape[1], *t.shape[2:])
+            n = max(1, cap_bytes // (flat[0].numel() * flat.element_size()))
+            pick = torch.randperm(flat.shape[0], generator=torch.Generator().manual_seed(seed))[:n].sort().values
+            t = flat[pick.to(flat.device)]
+        np.save(os.path.join(out_dir, f"{name}.npy"), t.cpu().numpy())
 
 
 def cpu_baseline(args, hl: int):
@@ -209,6 +230,8 @@ def train_bench(args, den, vae, dev, dtype, rank, world, dist, backend, barrier,
         losses += opt_step()
     barrier()
     elapsed = max_over_ranks(time.perf_counter() - t0, dev if backend == "nccl" else None)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"losses": torch.stack([torch.as_tensor(v) for v in losses[-acc:]])})     # the last optimizer step's
     comm = tr.opt.comm_stats()
     tp_fixed = next(iter(tr.plans.values()))            # the plan of the fixed shape `value` ran (the randomised leg below records others)
     views = world * b * 4 * acc * args.steps
@@ -414,10 +437,10 @@ def main():
     ap.add_argument("--res", type=int, default=256)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-profile", action="store_true")
-    ap.add_argument("--op-table", default=None, help="write the per-op profile (JSON) here")
+    ap.add_argument("--op-table", default=None, help="write the per-op profile (JSON) here (a --full run)")
     ap.add_argument("--no-small-batch", action="store_true", help="skip the b in {1, 4, 16} latency lines (and the 128-scene line)")
     ap.add_argument("--no-large-batch", action="store_true", help="(default since round 6: the 128-scene line is opt-in, --large-batch)")
-    ap.add_argument("--large-batch", action="store_true", help="add the 128-scene throughput line (`large_batch`; ~40 s of wall clock)")
+    ap.add_argument("--large-batch", action="store_true", help="add the 128-scene throughput line to a --full run (`large_batch`; ~40 s of wall clock)")
     ap.add_argument("--no-parity", action="store_true", help="skip the 50-step f32-vs-bench-dtype drift measurement")
     ap.add_argument("--no-train-line", action="store_true", help="skip the short training-step measurement appended to the sampling line")
     ap.add_argument("--no-full-walk", action="store_true", help="skip the 2-sample run without the exact sharing (`exact_sharing.full_walk`)")
@@ -429,7 +452,16 @@ def main():
                     help="run ONE eager UNet+DDIM pass and exit (the population `roofline` is quoted on; used for PMC passes)")
     ap.add_argument("--no-dropin", action="store_true", help="skip the `dropin` leg (the reference's own loop shape: two forwards + scheduler step per DDIM step)")
     ap.add_argument("--no-other-configs", action="store_true", help="skip the short configs[2] / configs[4] legs (`other_configs`)")
+    ap.add_argument("--full", action="store_true",
+                    help="add every measurement beyond the headline to the line (profile / roofline, small batches, f16 and drift, full walk, "
+                         "dropin, other configs, training line, CPU baseline); without it a run only times the K steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy (float32, at most 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.unet_pass_only:
+        ap.error("--dump-outputs needs timed steps (not --unet-pass-only)")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args))
@@ -509,6 +541,12 @@ def main():
     from mv_ldm_amd.dist import gather_counts, shard_scenes
     owned = shard_scenes(world * b, rank, world)
     batch = synthetic_batch(b, v_c, v_t, args.res, 1234, dev, scene_ids=owned)
+    # the sampler's noise (x_T, the context view's posterior draw), fixed per scene like the batch: every step samples the same
+    # inputs, so that the outputs of a run (`--dump-outputs`) depend on the arguments alone
+    hl = args.res // 8
+    noise = [torch.Generator().manual_seed(5678 + 7919 * int(i)) for i in owned]
+    x_T = torch.cat([torch.randn((1, v_t, 4, hl, hl), generator=g) for g in noise])
+    enc_noise = torch.cat([torch.randn((v_c, 4, hl, hl), generator=g) for g in noise]).to(dev)
 
     if args.unet_pass_only:
         # ONE eager UNet + DDIM pass between two sentinel launches (a kernel no other part of the process uses: `bessel_j0`):
@@ -532,16 +570,18 @@ def main():
             torch.cuda.synchronize()
         P.broadcast_tune_cache(dist, src=0, device=dev if backend == "nccl" else None)
     for _ in range(args.warmup):
-        pipe.sample(batch)
+        pipe.sample(batch, x_T=x_T, encode_noise=enc_noise)
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        img, _ = pipe.sample(batch)
+        img, x0 = pipe.sample(batch, x_T=x_T, encode_noise=enc_noise)
     barrier()
     elapsed = time.perf_counter() - t0
     from mv_ldm_amd.dist import max_over_ranks
     elapsed = max_over_ranks(elapsed, dev if backend == "nccl" else None)      # the only cross-rank exchange: no data-path collective
     assert torch.isfinite(img).all()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"images": img, "latents": x0})
     done = gather_counts([len(owned) * v_t * args.steps], dev if backend == "nccl" else None)      # bookkeeping, after the clock stopped
     views = sum(c[0] for c in done)
     assert views == world * b * v_t * args.steps
@@ -572,7 +612,7 @@ def main():
         meas = sum(ms)
         return {"bound_ms": round(bound, 4), "measured_ms": round(meas, 4), "frac": round(bound / max(meas, 1e-9), 4)}
 
-    if rank == 0 and not args.no_profile:
+    if args.full and rank == 0 and not args.no_profile:
         # ---- roofline of the dominant kernel family, measured live with HIP events on the launch stream
         # on VALID data: `prepare` reloads the inputs (step 0).  Timed on whatever a finished sample leaves
         # behind, the same kernels run 13 % faster -- past the end of the schedule the state is Inf/NaN, which
@@ -646,7 +686,7 @@ def main():
                 json.dump([{"name": m.name, "kind": m.kind, "ms": t, "flops": m.flops, "bytes": m.bytes}
                            for m, t in zip(plan.meta, ms)], f, indent=0)
 
-    if rank == 0 and world == 1 and not args.no_small_batch:
+    if args.full and rank == 0 and world == 1 and not args.no_small_batch:
         # ---- the small-batch regime (SURVEY.md §8d quotes config 2 at b in {1, 4, 16}; the reference's own use is b = 1):
         # whole-sample rate, per-step latency of the replayed graph, and the per-layer two-roof bound
         small = {}
@@ -697,7 +737,7 @@ def main():
                 pipe._plans.pop(key)
             torch.cuda.empty_cache()
 
-    if rank == 0 and world == 1 and not args.no_parity and args.dtype != "f32":
+    if args.full and rank == 0 and world == 1 and not args.no_parity and args.dtype != "f32":
         # ---- stated tolerance of the benched dtype: 50 DDIM steps, one scene, from the same x_T / context latents, against
         # the exact-f32 HIP path (itself within 1e-3 of the CPU oracle per step: tests/test_hip_headline.py, G5 goldens)
         pb = synthetic_batch(1, v_c, v_t, args.res, 4321, dev, scene_ids=[0])
@@ -753,7 +793,7 @@ def main():
                 "context views, whose inputs never change); the context views' eps is never read, so the last multi-view block and the "
                 "output stage run on the target views only.  Same values as the full walk (f32: 2e-6; tests/test_hip_headline.py); "
                 "`roofline` counts the FLOPs that are executed.  MVLDM_CFG_SHARE=0 MVLDM_TAIL_DROP=0 walks every image like the reference."}
-    if world == 1 and not args.no_full_walk and out["exact_sharing"]["enabled"]:
+    if args.full and world == 1 and not args.no_full_walk and out["exact_sharing"]["enabled"]:
         # ---- the same workload with every image walked through every layer (what the reference's two forwards compute): 6 samples
         saved = {k: os.environ.get(k) for k in ("MVLDM_CFG_SHARE", "MVLDM_TAIL_DROP")}
         os.environ["MVLDM_CFG_SHARE"], os.environ["MVLDM_TAIL_DROP"] = "0", "0"
@@ -778,7 +818,7 @@ def main():
                     os.environ[k] = v
             pipe._plans.clear()
             pipe._plans.update(kept)
-    if rank == 0 and world == 1 and not args.no_dropin:
+    if args.full and rank == 0 and world == 1 and not args.no_dropin:
         # ---- INTEGRATION.md level A: the reference's own loop shape (diffusion_wrapper.py:455-490 calling :413-453) -- per DDIM step two
         # `MultiViewUNet.forward` calls (conditional [1+4 views], unconditional [4]) from Python and one fused CFG + DDIM kernel --
         # beside the fused sampler that replaces the loop (level B = `value`): what registering the classes in the reference's
@@ -820,18 +860,18 @@ def main():
                         "model.forward(uncond) + fused CFG/DDIM kernel; VAE encode + decode included; same process, same box as `value`.  hooked_views_per_s: "
                         "`wrapper.sample(batch)` of a reference-style wrapper after ONE call of pipeline.install_fused_sampler(wrapper) (no edit of DiffusionWrapper)")
         out["dropin"] = drop
-    if rank == 0 and world == 1 and not args.no_other_configs:
+    if args.full and rank == 0 and world == 1 and not args.no_other_configs:
         out["other_configs"] = other_configs(args, den, vae, dev, two_roof)
-    if world == 1 and not args.no_train_line:
+    if args.full and world == 1 and not args.no_train_line:
         # ---- the training step of the same path (BASELINE configs[3]; `python bench.py --train` is the full-length run).  Last
         # GPU work of the process: the fused AdamW updates the denoiser's weights in place.
         import copy
         targs = copy.copy(args)
-        targs.steps, targs.warmup, targs.op_table, targs.scenes = 4, 2, None, 64
+        targs.steps, targs.warmup, targs.op_table, targs.scenes, targs.dump_outputs = 4, 2, None, 64, None
         t = train_bench(targs, den, vae, dev, dtype, rank, world, dist, backend, barrier, n_params)
         out["training"] = {k: t[k] for k in ("metric", "value", "unit", "steps", "warmup", "ms_per_step", "config", "micro_batch_ms",
                                               "micro_batch_tflops", "grad_norm", "roofline", "grad_rel_err", "randomised", "comm") if k in t}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args, args.res // 8)
     if rank == 0:
         print(json.dumps(out), flush=True)

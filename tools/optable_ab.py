@@ -1,4 +1,4 @@
-"""compare two per-op tables of the same plan (bench.py --op-table), batch-split remainders folded into their launch: python3 tools/optable_ab.py old.json new.json [rows]"""
+"""compare two per-op tables of the same plan (bench.py --full --op-table), batch-split remainders folded into their launch: python3 tools/optable_ab.py old.json new.json [rows]"""
 import collections, json, re, sys
 
 

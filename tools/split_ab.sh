@@ -2,7 +2,7 @@
 # same-box A/B of the batch split of the big igemm launches (plan.autosplit_igemm): MVLDM_BATCH_SPLIT=0 | 1, alternating
 for v in 0 1 0 1; do
   S=$(date +%s)
-  MVLDM_BATCH_SPLIT=$v timeout 700 python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-small-batch --no-parity --no-train-line --no-full-walk --no-alt-dtype --no-dropin --no-other-configs \
+  MVLDM_BATCH_SPLIT=$v timeout 700 python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-small-batch --no-parity --no-train-line --no-full-walk --no-alt-dtype --no-dropin --no-other-configs \
       --op-table gpurun_out/optable_split_$v.json 2>gpurun_out/split_ab_$v.err \
     | grep '^{' | tail -1 | python3 -c "import sys, json; d = json.loads(sys.stdin.read()); print('split=$v', d['value'], 'views/s', d.get('ddim_step_ms'), 'ms/step', d['roofline']['frac'], 'wall', $(date +%s) - $S)"
 done
