@@ -29,7 +29,7 @@ extern "C" {
  * unchanged (additive).
  * 4 (round 5): + mvldm_pack_skinny and tile 15 / k_order 2 of mvldm_igemm_fwd (the skinny-M weight-streaming GEMM); additive over 3.
  * 5 (round 6): + tile 19 of mvldm_igemm_fwd (register-staged Linear), tile 13's bits 13 / 14, mvldm_build_flags; additive over 4. */
-#define MVLDM_ABI_VERSION 5
+#define MVLDM_ABI_VERSION 6
 
 typedef void* mvldm_stream_t; /* hipStream_t */
 
@@ -385,6 +385,26 @@ int mvldm_mse_loss(const float* pred, const float* noise, const int32_t* tgt_img
                    int accumulate, float loss_scale, void* dpred, int dpred_c, int dpred_dtype, float grad_scale,
                    double* workspace, mvldm_stream_t stream);
 
+/* ---- f16 dynamic loss scaling (torch.amp.GradScaler under Lightning's `16-mixed`) ----------------------------------
+ * The whole scaler lives in ONE device record owned by the trainer; recorded plans and graph replays hold its address,
+ * never its values, so the scale S can change while they stay recorded.  One optimizer step with the scaler:
+ *   backward (dY of the loss carries S) -> mvldm_grad_norm_amp (norm of the UNSCALED gradients, found_inf)
+ *   -> mvldm_adamw_step_amp (skips the whole update when found_inf) -> mvldm_amp_update (one launch). */
+typedef struct mvldm_amp_state {
+    float scale;              /* S: dY of the loss and therefore every fp32 weight gradient carries it */
+    int32_t growth_tracker;   /* successful steps since the last change of S (torch's _growth_tracker) */
+    int32_t adam_step;        /* AdamW steps TAKEN (bias correction); does not advance on a skipped step */
+    int32_t found_inf;        /* set by mvldm_grad_norm_amp, cleared by mvldm_amp_update */
+    int32_t skipped;          /* optimizer steps skipped so far */
+    int32_t reserved[3];
+} mvldm_amp_state;
+/* mvldm_mse_loss with dpred additionally multiplied by *amp_scale (device, fp32: the S of mvldm_amp_state) before the
+ * rounding to dpred_dtype; the loss itself stays unscaled.  amp_scale NULL: exactly mvldm_mse_loss.  (Not to be confused
+ * with loss_scale, the 1/accumulate factor of the reported loss.) */
+int mvldm_mse_loss_amp(const float* pred, const float* noise, const int32_t* tgt_img, int n_tgt, int hw, int c, float* loss,
+                       int accumulate, float loss_scale, void* dpred, int dpred_c, int dpred_dtype, float grad_scale,
+                       const float* amp_scale, double* workspace, mvldm_stream_t stream);
+
 /* torch.nn.utils.clip_grad_norm_ over a flat fp32 gradient buffer (Lightning gradient_clip_val, src/main.py:131):
  * norm_out[0] = total norm, norm_out[1] = min(1, max_norm / (total + 1e-6)) (max_norm <= 0: 1), norm_out[2] = this
  * buffer's sum of squares.  sumsq_in (optional, device): use this total sum of squares instead (a sharded optimizer
@@ -395,6 +415,21 @@ int mvldm_grad_norm(const float* g, size_t n, const float* sumsq_in, float max_n
  * g' = g * grad_scale * clip[1] (clip optional: norm_out of mvldm_grad_norm); step >= 1 is the 1-based step count. */
 int mvldm_adamw_step(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2, float eps,
                      float weight_decay, int step, float grad_scale, const float* clip, mvldm_stream_t stream);
+/* mvldm_grad_norm on gradients that carry the loss scale S of `amp` (device): the squares are summed in fp64 and the sum
+ * multiplied by 1/S^2 there, so norm_out[0..2] are the UNSCALED total norm, clip coefficient (the coefficient of
+ * clip_grad_norm_ after GradScaler.unscale_) and this buffer's sum of squares -- a large but finite scaled gradient never
+ * overflows the fp32 norm_out[2].  sumsq_in, when given, is taken as already unscaled.  amp->found_inf = the total sum of
+ * squares is not finite (under ZeRO-1 sumsq_in is the all-reduced value, identical on every rank: every rank decides alike). */
+int mvldm_grad_norm_amp(const float* g, size_t n, const float* sumsq_in, float max_norm, float* norm_out, mvldm_amp_state* amp,
+                        double* workspace, mvldm_stream_t stream);
+/* mvldm_adamw_step with the step taken from the device: amp->found_inf set -> p, m, v untouched; otherwise
+ * g' = g * grad_scale * clip[1] / S and the bias correction uses step amp->adam_step + 1 (mvldm_amp_update advances it). */
+int mvldm_adamw_step_amp(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2, float eps,
+                         float weight_decay, float grad_scale, const float* clip, const mvldm_amp_state* amp, mvldm_stream_t stream);
+/* torch._amp_update_scale_ on the record, one thread: found_inf -> S *= backoff_factor, growth_tracker = 0, skipped += 1;
+ * else growth_tracker += 1, adam_step += 1 and, when growth_tracker reaches growth_interval, S *= growth_factor (if that is
+ * finite) and growth_tracker = 0.  found_inf is cleared. */
+int mvldm_amp_update(mvldm_amp_state* amp, float growth_factor, float backoff_factor, int growth_interval, mvldm_stream_t stream);
 
 /* DiffusionWrapper.on_before_zero_grad -> self.ema.update_parameters(self.denoiser) (diffusion_wrapper.py:138-142,152-154):
  * torch.optim.swa_utils.AveragedModel with get_ema_multi_avg_fn(0.995), i.e. avg.lerp_(p, weight) with weight = 1 - decay, on the flat
@@ -482,7 +517,8 @@ typedef struct mvldm_op {
         struct { const float* x0; const float* noise; const float* coef; void* dst; const int32_t* img_map;
                  int32_t n, c, hw, dst_c, dst_c_off, dst_dtype; } add_noise;
         struct { const float* pred; const float* noise; const int32_t* tgt_img; float* loss; void* dpred; double* workspace;
-                 int32_t n_tgt, hw, c, accumulate, dpred_c, dpred_dtype; float loss_scale, grad_scale; } mse;
+                 int32_t n_tgt, hw, c, accumulate, dpred_c, dpred_dtype; float loss_scale, grad_scale;
+                 const float* amp_scale; /* optional: mvldm_mse_loss_amp's S pointer */ } mse;
         struct { void* dst; size_t bytes; } fill;
         struct { const void* src; void* dst; size_t bytes; } memcpy_;
         struct { const void* src; void* dst; const int32_t* src_index; const int32_t* dst_index; size_t row_bytes; int32_t n_rows; } gather;

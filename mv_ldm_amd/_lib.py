@@ -11,7 +11,7 @@ from pathlib import Path
 
 LIB_PATH = Path(__file__).resolve().parent / "csrc" / "libmvldm_hip.so"
 
-ABI_VERSION = 5
+ABI_VERSION = 6
 F32, BF16, F16 = 0, 1, 2
 EPI_NONE, EPI_SILU, EPI_GEGLU, EPI_GELU = 0, 1, 2, 3
 RAYS_RAW, RAYS_POSITIONAL, RAYS_SRT = 0, 1, 2
@@ -159,7 +159,12 @@ class _AddNoise(C.Structure):
 class _Mse(C.Structure):
     _fields_ = [("pred", vp), ("noise", vp), ("tgt_img", vp), ("loss", vp), ("dpred", vp), ("workspace", vp),
                 ("n_tgt", i32), ("hw", i32), ("c", i32), ("accumulate", i32), ("dpred_c", i32), ("dpred_dtype", i32),
-                ("loss_scale", f32), ("grad_scale", f32)]
+                ("loss_scale", f32), ("grad_scale", f32), ("amp_scale", vp)]
+
+
+class AmpState(C.Structure):
+    """mvldm_amp_state: the f16 loss scaler's device record (mv_ldm_amd/train.py keeps it in an int32[8] tensor)"""
+    _fields_ = [("scale", f32), ("growth_tracker", i32), ("adam_step", i32), ("found_inf", i32), ("skipped", i32), ("reserved", i32 * 3)]
 
 
 class _Fill(C.Structure):
@@ -208,6 +213,10 @@ SIGNATURES = {
     "mvldm_mse_loss": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, f32, vp, C.c_int, C.c_int, f32, vp, vp]),
     "mvldm_grad_norm": (C.c_int, [vp, sz, vp, f32, vp, vp, vp]),
     "mvldm_adamw_step": (C.c_int, [vp, vp, vp, vp, sz, f32, f32, f32, f32, f32, C.c_int, f32, vp, vp]),
+    "mvldm_mse_loss_amp": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, f32, vp, C.c_int, C.c_int, f32, vp, vp, vp]),
+    "mvldm_grad_norm_amp": (C.c_int, [vp, sz, vp, f32, vp, vp, vp, vp]),
+    "mvldm_adamw_step_amp": (C.c_int, [vp, vp, vp, vp, sz, f32, f32, f32, f32, f32, f32, vp, vp, vp]),
+    "mvldm_amp_update": (C.c_int, [vp, f32, f32, C.c_int, vp]),
     "mvldm_timestep_embed_fwd": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "mvldm_eltwise_fwd": (C.c_int, [vp, vp, sz, C.c_int, C.c_int, C.c_int, vp]),
     "mvldm_ddim_cfg_step": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, f32, vp, vp, vp, C.c_int, C.c_int, C.c_int, f32, vp]),

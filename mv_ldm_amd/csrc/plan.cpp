@@ -40,7 +40,7 @@ int zero_insert_run(const void* x, void* out, int n_img, int h, int w, int c, in
 int add_noise_run(const float* x0, const float* noise, const float* coef, void* dst, int n, int c, int hw, int dst_c, int dst_c_off, int dst_dtype,
                   const int32_t* img_map, hipStream_t s);
 int mse_run(const float* pred, const float* noise, const int32_t* tgt_img, int n_tgt, int hw, int c, float* loss, int accumulate, float loss_scale,
-            void* dpred, int dc, int dtype, float grad_scale, double* ws, hipStream_t s);
+            void* dpred, int dc, int dtype, float grad_scale, const float* amp_scale, double* ws, hipStream_t s);
 int to_nchw_run(const void* src, float* dst, int n_img, int c, int hw, int src_c, int src_c_off, int src_dtype, float scale,
                 float shift, int clamp01, hipStream_t s);
 int gather_rows_run(const void* src, void* dst, const int32_t* src_index, const int32_t* dst_index, int n_rows, size_t row_bytes, hipStream_t s);
@@ -136,7 +136,7 @@ static int run_op(const mvldm_op& op, hipStream_t s) {
         case MVLDM_OP_MSE_LOSS: {
             const auto& m = op.u.mse;
             return mse_run(m.pred, m.noise, m.tgt_img, m.n_tgt, m.hw, m.c, m.loss, m.accumulate, m.loss_scale, m.dpred, m.dpred_c, m.dpred_dtype,
-                           m.grad_scale, m.workspace, s);
+                           m.grad_scale, m.amp_scale, m.workspace, s);
         }
         case MVLDM_OP_FILL_ZERO: {
             const auto& f = op.u.fill;

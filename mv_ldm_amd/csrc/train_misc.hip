@@ -174,12 +174,14 @@ __global__ __launch_bounds__(256) void add_noise_kernel(const float* __restrict_
 // F.mse_loss(pred[:, v_c:], noise, reduction="mean") and its gradient (diffusion_wrapper.py:405-411):
 // pred fp32 NHWC [n_img][hw][c]; target t: image tgt_img[t] of pred, noise fp32 NCHW [n_tgt][c][hw].
 // partial[block] = sum (pred - noise)^2;  dpred [n_img][hw][dc] (activation dtype, zero-filled by the caller for the
-// non-target images and the padding channels) = grad_scale * 2 (pred - noise) / N
+// non-target images and the padding channels) = grad_scale * 2 (pred - noise) / N [* S, read from amp_scale when given]
 template <typename T>
 __global__ __launch_bounds__(256) void mse_kernel(const float* __restrict__ pred, const float* __restrict__ noise, const int32_t* __restrict__ tgt_img,
-                                                  int n_tgt, int hw, int c, double* __restrict__ partial, T* __restrict__ dpred, int dc, float gscale) {
+                                                  int n_tgt, int hw, int c, double* __restrict__ partial, T* __restrict__ dpred, int dc, float gscale,
+                                                  const float* __restrict__ amp_scale) {
     __shared__ double s_red[256];
     const size_t per = (size_t)hw * c, total = (size_t)n_tgt * per;
+    if (amp_scale) gscale *= amp_scale[0];       // f16 loss scaling: dY carries S before its rounding (S: a power of two by default)
     double acc = 0.0;
     for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
         const int t = (int)(idx / per);
@@ -263,6 +265,30 @@ __global__ __launch_bounds__(256) void clip_coef_kernel(const double* __restrict
         norm_out[2] = (float)s_red[0];      // this buffer's own sum of squares (what a sharded optimizer all-reduces)
     }
 }
+// the same on gradients that carry the loss scale S: the fp64 sums are unscaled (x 1/S^2) before anything is rounded to fp32, and
+// found_inf = the total is not finite.  1/S as torch's GradScaler.unscale_ forms it (fp64 reciprocal, rounded to fp32).
+__global__ __launch_bounds__(256) void clip_coef_amp_kernel(const double* __restrict__ partial, int n, const float* __restrict__ sumsq_in,
+                                                            float max_norm, float* __restrict__ norm_out, mvldm_amp_state* __restrict__ amp) {
+    __shared__ double s_red[256];
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < n; i += 256) acc += partial[i];
+    s_red[threadIdx.x] = acc;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (threadIdx.x < o) s_red[threadIdx.x] += s_red[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const double inv = (double)(float)(1.0 / (double)amp->scale);
+        const double own = s_red[0] * inv * inv;
+        const double tot2 = sumsq_in ? (double)sumsq_in[0] : own;
+        const float total = (float)sqrt(tot2);
+        norm_out[0] = total;
+        norm_out[1] = max_norm > 0.f ? fminf(1.0f, max_norm / (total + 1e-6f)) : 1.0f;
+        norm_out[2] = (float)own;
+        amp->found_inf = isfinite(tot2) ? 0 : 1;
+    }
+}
 // torch.optim.AdamW (decoupled weight decay, no amsgrad), one launch over the flat fp32 master parameters:
 //   g *= gscale * clip;  p *= 1 - lr * wd;  m = b1 m + (1 - b1) g;  v = b2 v + (1 - b2) g^2;
 //   p -= (lr / bc1) * m / (sqrt(v) / sqrt(bc2) + eps)          (bc = 1 - beta^step, computed on the host in fp64)
@@ -324,6 +350,75 @@ __global__ __launch_bounds__(256) void adamw_kernel4(f32x4* __restrict__ p, cons
             p[i] = p4;
         }
     }
+}
+
+// AdamW under the loss scaler: the step count and the skip decision come from the device record.  A found_inf step leaves p, m, v
+// untouched (the whole grid returns before loading anything); otherwise g' = g * gscale * clip / S and the bias correction of step
+// adam_step + 1 is formed here in fp64, as adamw_run does on the host.
+__global__ __launch_bounds__(256) void adamw_amp_kernel4(f32x4* __restrict__ p, const f32x4* __restrict__ g, f32x4* __restrict__ m,
+                                                         f32x4* __restrict__ v, const float* __restrict__ gp, float* __restrict__ pp,
+                                                         float* __restrict__ mp, float* __restrict__ vp, size_t n, float lr, float b1, float b2,
+                                                         float eps, float wd, float gscale, const float* __restrict__ clip,
+                                                         const mvldm_amp_state* __restrict__ amp) {
+    if (amp->found_inf) return;
+    const int step = amp->adam_step + 1;
+    const double bc1 = 1.0 - pow((double)b1, step), bc2 = 1.0 - pow((double)b2, step);
+    const float step_size = (float)(lr / bc1), inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
+    const float gs = gscale * (clip ? clip[1] : 1.0f) * (float)(1.0 / (double)amp->scale);
+    const size_t n4 = p ? n / 4 : 0;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
+        const f32x4 g4 = __builtin_nontemporal_load(g + i), m4 = __builtin_nontemporal_load(m + i), v4 = __builtin_nontemporal_load(v + i);
+        f32x4 p4 = __builtin_nontemporal_load(p + i), mo, vo;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float gi = g4[e] * gs;
+            float pi = p4[e] * (1.0f - lr * wd);
+            const float mi = b1 * m4[e] + (1.0f - b1) * gi;
+            const float vi = b2 * v4[e] + (1.0f - b2) * gi * gi;
+            mo[e] = mi;
+            vo[e] = vi;
+            pi -= step_size * (mi / (sqrtf(vi) * inv_sqrt_bc2 + eps));
+            p4[e] = pi;
+        }
+        __builtin_nontemporal_store(mo, m + i);
+        __builtin_nontemporal_store(vo, v + i);
+        __builtin_nontemporal_store(p4, p + i);
+    }
+    // unaligned / non-multiple-of-4 form: the scalar pointers (p == nullptr selects it)
+    const size_t ns = p ? 0 : n;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < ns; i += (size_t)gridDim.x * 256) {
+        const float gi = gp[i] * gs;
+        float pi = pp[i] * (1.0f - lr * wd);
+        const float mi = b1 * mp[i] + (1.0f - b1) * gi;
+        const float vi = b2 * vp[i] + (1.0f - b2) * gi * gi;
+        mp[i] = mi;
+        vp[i] = vi;
+        pi -= step_size * (mi / (sqrtf(vi) * inv_sqrt_bc2 + eps));
+        pp[i] = pi;
+    }
+}
+
+// torch._amp_update_scale_ (one thread)
+__global__ void amp_update_kernel(mvldm_amp_state* __restrict__ amp, float growth, float backoff, int interval) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    mvldm_amp_state a = *amp;
+    if (a.found_inf) {
+        a.scale *= backoff;
+        a.growth_tracker = 0;
+        a.skipped += 1;
+    } else {
+        a.adam_step += 1;
+        const int successful = a.growth_tracker + 1;
+        if (successful >= interval) {
+            const float grown = a.scale * growth;
+            if (isfinite(grown)) a.scale = grown;
+            a.growth_tracker = 0;
+        } else {
+            a.growth_tracker = successful;
+        }
+    }
+    a.found_inf = 0;
+    *amp = a;
 }
 
 // ---- host entry points ---------------------------------------------------------------------------------------
@@ -437,14 +532,14 @@ int add_noise_run(const float* x0, const float* noise, const float* coef, void* 
 
 constexpr int kLossBlocks = 256;
 int mse_run(const float* pred, const float* noise, const int32_t* tgt_img, int n_tgt, int hw, int c, float* loss, int accumulate, float loss_scale,
-            void* dpred, int dc, int dtype, float grad_scale, double* ws, hipStream_t s) {
+            void* dpred, int dc, int dtype, float grad_scale, const float* amp_scale, double* ws, hipStream_t s) {
     MVLDM_REQUIRE(pred && noise && tgt_img && loss && ws && n_tgt > 0 && hw > 0, "mse_loss: bad arguments");
     MVLDM_REQUIRE(!dpred || dc >= c, "mse_loss: dpred has %d channels, need %d", dc, c);
     const double N = (double)n_tgt * hw * c;
     int rc = dispatch_dtype(dtype, [&](auto t) {
         using T = decltype(t);
         hipLaunchKernelGGL(mse_kernel<T>, dim3(kLossBlocks), dim3(256), 0, s, pred, noise, tgt_img, n_tgt, hw, c, ws, reinterpret_cast<T*>(dpred), dc,
-                           (float)(2.0 * grad_scale / N));
+                           (float)(2.0 * grad_scale / N), amp_scale);
         return check_launch();
     });
     if (rc) return rc;
@@ -459,6 +554,36 @@ int grad_norm_run(const float* g, size_t n, const float* sumsq_in, float max_nor
     int rc = check_launch();
     if (rc) return rc;
     hipLaunchKernelGGL(clip_coef_kernel, dim3(1), dim3(256), 0, s, ws, kNormBlocks, sumsq_in, max_norm, norm_out);
+    return check_launch();
+}
+
+int grad_norm_amp_run(const float* g, size_t n, const float* sumsq_in, float max_norm, float* norm_out, mvldm_amp_state* amp, double* ws, hipStream_t s) {
+    MVLDM_REQUIRE(g && norm_out && ws && amp, "grad_norm_amp: null pointer");
+    hipLaunchKernelGGL(sumsq_kernel, dim3(kNormBlocks), dim3(256), 0, s, g, n, ws);
+    int rc = check_launch();
+    if (rc) return rc;
+    hipLaunchKernelGGL(clip_coef_amp_kernel, dim3(1), dim3(256), 0, s, ws, kNormBlocks, sumsq_in, max_norm, norm_out, amp);
+    return check_launch();
+}
+
+int adamw_amp_run(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2, float eps, float weight_decay,
+                  float grad_scale, const float* clip, const mvldm_amp_state* amp, hipStream_t s) {
+    if (n == 0) return MVLDM_OK;
+    MVLDM_REQUIRE(p && g && m && v && amp, "adamw_amp: bad arguments");
+    const bool vec = n % 4 == 0 && (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0;
+    if (vec)
+        hipLaunchKernelGGL(adamw_amp_kernel4, dim3(grid_for(n / 4, 2048)), dim3(256), 0, s, reinterpret_cast<f32x4*>(p), reinterpret_cast<const f32x4*>(g),
+                           reinterpret_cast<f32x4*>(m), reinterpret_cast<f32x4*>(v), nullptr, nullptr, nullptr, nullptr, n, lr, beta1, beta2, eps,
+                           weight_decay, grad_scale, clip, amp);
+    else
+        hipLaunchKernelGGL(adamw_amp_kernel4, dim3(grid_for(n, 1024)), dim3(256), 0, s, nullptr, nullptr, nullptr, nullptr, g, p, m, v, n, lr, beta1,
+                           beta2, eps, weight_decay, grad_scale, clip, amp);
+    return check_launch();
+}
+
+int amp_update_run(mvldm_amp_state* amp, float growth, float backoff, int interval, hipStream_t s) {
+    MVLDM_REQUIRE(amp && interval >= 1 && growth > 0.f && backoff > 0.f, "amp_update: bad arguments");
+    hipLaunchKernelGGL(amp_update_kernel, dim3(1), dim3(64), 0, s, amp, growth, backoff, interval);
     return check_launch();
 }
 
@@ -512,7 +637,25 @@ extern "C" int mvldm_add_noise(const float* x0, const float* noise, const float*
 }
 extern "C" int mvldm_mse_loss(const float* pred, const float* noise, const int32_t* tgt_img, int n_tgt, int hw, int c, float* loss, int accumulate,
                               float loss_scale, void* dpred, int dpred_c, int dpred_dtype, float grad_scale, double* workspace, mvldm_stream_t stream) {
-    return mse_run(pred, noise, tgt_img, n_tgt, hw, c, loss, accumulate, loss_scale, dpred, dpred_c, dpred_dtype, grad_scale, workspace, (hipStream_t)stream);
+    return mse_run(pred, noise, tgt_img, n_tgt, hw, c, loss, accumulate, loss_scale, dpred, dpred_c, dpred_dtype, grad_scale, nullptr, workspace,
+                   (hipStream_t)stream);
+}
+extern "C" int mvldm_mse_loss_amp(const float* pred, const float* noise, const int32_t* tgt_img, int n_tgt, int hw, int c, float* loss, int accumulate,
+                                  float loss_scale, void* dpred, int dpred_c, int dpred_dtype, float grad_scale, const float* amp_scale, double* workspace,
+                                  mvldm_stream_t stream) {
+    return mse_run(pred, noise, tgt_img, n_tgt, hw, c, loss, accumulate, loss_scale, dpred, dpred_c, dpred_dtype, grad_scale, amp_scale, workspace,
+                   (hipStream_t)stream);
+}
+extern "C" int mvldm_grad_norm_amp(const float* g, size_t n, const float* sumsq_in, float max_norm, float* norm_out, mvldm_amp_state* amp,
+                                   double* workspace, mvldm_stream_t stream) {
+    return grad_norm_amp_run(g, n, sumsq_in, max_norm, norm_out, amp, workspace, (hipStream_t)stream);
+}
+extern "C" int mvldm_adamw_step_amp(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2, float eps,
+                                    float weight_decay, float grad_scale, const float* clip, const mvldm_amp_state* amp, mvldm_stream_t stream) {
+    return adamw_amp_run(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, grad_scale, clip, amp, (hipStream_t)stream);
+}
+extern "C" int mvldm_amp_update(mvldm_amp_state* amp, float growth_factor, float backoff_factor, int growth_interval, mvldm_stream_t stream) {
+    return amp_update_run(amp, growth_factor, backoff_factor, growth_interval, (hipStream_t)stream);
 }
 extern "C" int mvldm_grad_norm(const float* g, size_t n, const float* sumsq_in, float max_norm, float* norm_out, double* workspace, mvldm_stream_t stream) {
     return grad_norm_run(g, n, sumsq_in, max_norm, norm_out, workspace, (hipStream_t)stream);

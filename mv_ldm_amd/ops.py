@@ -554,6 +554,28 @@ def adamw_step(p, g, m, v, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, 
                                       weight_decay, step, grad_scale, ptr(clip), stream()))
 
 
+def grad_norm_amp(flat_grad, max_norm: float, amp_state, norm_out=None, sumsq_in=None):
+    """`grad_norm` of gradients that carry the loss scale of `amp_state` (mvldm_amp_state, int32 [8] device tensor): the norm, clip
+    coefficient and sum of squares of the UNSCALED gradients; sets the record's found_inf when the total is not finite"""
+    norm_out = torch.zeros(4, dtype=torch.float32, device=flat_grad.device) if norm_out is None else norm_out
+    ws = workspace(1024 * 8, flat_grad.device, "norm")
+    L.check(L.load().mvldm_grad_norm_amp(flat_grad.data_ptr(), flat_grad.numel(), ptr(sumsq_in), max_norm, norm_out.data_ptr(),
+                                         amp_state.data_ptr(), ws.data_ptr(), stream()))
+    return norm_out
+
+
+def adamw_step_amp(p, g, m, v, lr, amp_state, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, grad_scale=1.0, clip=None):
+    """`adamw_step` with the step count, 1/S and the skip decision read from the loss scaler's device record"""
+    assert all(t.dtype == torch.float32 and t.is_contiguous() and t.numel() == p.numel() for t in (p, g, m, v))
+    L.check(L.load().mvldm_adamw_step_amp(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), lr, betas[0], betas[1], eps,
+                                          weight_decay, grad_scale, ptr(clip), amp_state.data_ptr(), stream()))
+
+
+def amp_update(amp_state, growth_factor: float, backoff_factor: float, growth_interval: int):
+    """torch._amp_update_scale_ on the record (one launch); also advances AdamW's step count on a taken step and clears found_inf"""
+    L.check(L.load().mvldm_amp_update(amp_state.data_ptr(), float(growth_factor), float(backoff_factor), int(growth_interval), stream()))
+
+
 def ema_update(avg, p, weight: float):
     """avg.lerp_(p, weight) on flat fp32 buffers (torch.optim.swa_utils EMA: weight = 1 - decay)"""
     assert avg.dtype == p.dtype == torch.float32 and avg.is_contiguous() and p.is_contiguous() and avg.numel() == p.numel()

@@ -13,8 +13,9 @@ Gradient kernels (include/mvldm.h, "Training"):
     norms            `mvldm_groupnorm_bwd`, `mvldm_layernorm_bwd`;  attention `mvldm_attention_bwd` (recompute from lse)
     elementwise      SiLU / GEGLU backward, column sums for biases and the time-embedding rows
 Master weights, gradients and AdamW moments are fp32 in flat buffers (`FlatParams`); activations and activation
-gradients are in the compute dtype (bf16: the bench dtype; f32: the parity mode; the reference trains under fp16
-autocast WITH a loss scaler -- f16 activations gradients would need one here as well, so f16 is refused for training).
+gradients are in the compute dtype (bf16: the bench dtype; f32: the parity mode; f16: the reference's own `16-mixed`, fp16 autocast
+WITH a dynamic loss scaler -- here `GradScalerCfg`, kept entirely on the device: the loss gradient carries the scale S, so under f16
+scaling `flat.grad` holds S x g, the way torch's `.grad` does before `GradScaler.unscale_`; see `DistributedOptimizer` for the step).
 Parameters that never enter the graph (the SD up-block transformers when `pretrained_from` is set, mvunet.py:178) are
 excluded statically instead of discovered per step (`find_unused_parameters`); parameters that enter it with an exactly
 zero gradient (cross-attention to the all-zero context, mvunet.py:124-128) stay in the optimizer -- AdamW's decoupled
@@ -47,7 +48,8 @@ from .plan import Builder, Plan
 class FlatParams:
     """fp32 master parameters and gradients of the TRAINED part of a module in two flat device buffers; every
     `nn.Parameter` becomes a view (`p.data`, `p.grad`), so state dicts / checkpoints keep working.  Order = the stacked `groups`
-    first, then module registration order (what `parameters()` yields); offsets aligned to 16 bytes."""
+    first, then module registration order (what `parameters()` yields); offsets aligned to 16 bytes.  An f16 trainer under the loss
+    scaler leaves S x g in `grad` (S = `DistributedOptimizer.grad_scale`), like torch's `.grad` before `GradScaler.unscale_`."""
 
     def __init__(self, module: nn.Module, exclude: Sequence[nn.Parameter] = (), groups: Sequence[Sequence[nn.Parameter]] = ()):
         """`groups`: parameter lists that one kernel treats as ONE stacked matrix (the 22 `time_emb_proj` weights / biases of the UNet's
@@ -126,7 +128,8 @@ class TrainBuilder(Builder):
     """records forward ops like `Builder` plus, per op, a closure that emits its backward ops"""
 
     def __init__(self, device, dtype, flat: FlatParams, ws_bytes: int = 512 << 20, store_first: bool = False):
-        assert dtype in (torch.float32, torch.bfloat16), "training runs in bf16 (fp32 accumulation / master weights) or f32"
+        assert dtype in (torch.float32, torch.bfloat16, torch.float16), \
+            "training runs in bf16 / f16 (fp32 accumulation / master weights) or f32"
         super().__init__(device, dtype, record=True)
         self.skinny = False             # the training packs are refreshed in place after every optimizer step: no fragment-order copies
         self.flat = flat
@@ -788,9 +791,12 @@ class TrainPlan:
     micro-batches one by one adds up to), the weights are read once, and every launch serves the whole window."""
 
     def __init__(self, den, flat: FlatParams, b, v_c=None, v_t=None, hl: int = 0, wl: int = 0, dtype=torch.bfloat16, loss_scale: float = 1.0,
-                 grad_scale: float = 1.0, graph: bool = False, rays=None, tune: Optional[bool] = None, store_first: bool = False):
+                 grad_scale: float = 1.0, graph: bool = False, rays=None, tune: Optional[bool] = None, store_first: bool = False,
+                 amp_scale: Optional[torch.Tensor] = None):
         """`store_first`: the plan runs once per accumulation window and its first write of every gradient range is a store -- the
-        caller replaces `flat.zero_grad()` by `flat.begin_window(plan.stored)`"""
+        caller replaces `flat.zero_grad()` by `flat.begin_window(plan.stored)`.  `amp_scale`: fp32 device scalar of the f16 loss
+        scaler (`DistributedOptimizer.grad_scale`): the loss gradient is multiplied by it, read at RUN time -- the plan (and its
+        graph) records the address, never the value."""
         dev = flat.flat.device
         if tune is None:        # plan-time tile selection of the forward / data-gradient implicit GEMMs (MVLDM_TRAIN_AUTOTUNE=0: rules only)
             tune = os.environ.get("MVLDM_TRAIN_AUTOTUNE", "1") != "0" and os.environ.get("MVLDM_AUTOTUNE", "1") != "0"
@@ -850,8 +856,9 @@ class TrainPlan:
             m = op.u.mse
             m.pred, m.noise, m.tgt_img, m.loss, m.dpred, m.workspace = ptr(eps), ptr(self.noise[t0:t0 + nt]), ptr(tgt_img[t0:t0 + nt]), ptr(self.loss[i:i + 1]), ptr(d_eps), ptr(ws)
             m.n_tgt, m.hw, m.c, m.accumulate, m.dpred_c, m.dpred_dtype = nt, hl * wl, lc, 1, dc, dt(d_eps)
-            m.loss_scale, m.grad_scale = loss_scale, grad_scale
-            bld._emit(op, "mse_loss" if len(parts) == 1 else f"mse_loss.{i}", 0.0, nt * hl * wl * lc * 8.0, (eps, self.noise, tgt_img, self.loss, d_eps, ws))
+            m.loss_scale, m.grad_scale, m.amp_scale = loss_scale, grad_scale, ptr(amp_scale)
+            bld._emit(op, "mse_loss" if len(parts) == 1 else f"mse_loss.{i}", 0.0, nt * hl * wl * lc * 8.0, (eps, self.noise, tgt_img, self.loss, d_eps, ws)
+                      + (() if amp_scale is None else (amp_scale,)))
         self.n_forward_ops = len(bld.ops)
         bld.grads[_key(eps)] = d_eps
         with bld.scope("backward"):
@@ -901,6 +908,28 @@ class OptimizerCfg:
                                                                "kwargs": {"start_factor": 5e-4, "total_iters": 200}})
 
 
+@dataclass
+class GradScalerCfg:
+    """torch.amp.GradScaler / Lightning `16-mixed` (src/main.py:124, config/experiment/baseline.yaml:60): dynamic loss scaling of the
+    f16 training path, torch's defaults.  Only an f16 trainer scales; bf16 and f32 never do."""
+    enabled: bool = True
+    init_scale: float = 2.0 ** 16
+    growth_factor: float = 2.0
+    backoff_factor: float = 0.5
+    growth_interval: int = 2000
+
+
+def training_precision(precision) -> Tuple[torch.dtype, bool]:
+    """Lightning's `trainer.precision` ("16-mixed", "bf16-mixed", "32", ...) -> (compute dtype, loss scaler on): the dtype map is
+    the harness's (`generate._PRECISION`); the scaler is on exactly for f16, as Lightning's MixedPrecision plugin does"""
+    from .generate import _PRECISION
+    key = None if precision is None else str(precision)
+    if key not in _PRECISION:
+        raise ValueError(f"trainer.precision {precision!r}: expected one of {sorted(k for k in _PRECISION if k)}")
+    dtype = _PRECISION[key]
+    return dtype, dtype == torch.float16
+
+
 def linear_lr_factor(step: int, start_factor: float = 1.0 / 3, end_factor: float = 1.0, total_iters: int = 5) -> float:
     """torch.optim.lr_scheduler.LinearLR in closed form: the factor in force after `step` scheduler steps"""
     return start_factor + (end_factor - start_factor) * min(step, total_iters) / total_iters
@@ -915,11 +944,26 @@ class DistributedOptimizer:
     the master weights with its slice of the moments, and the slices are all-gathered back.  world = 1 without a process
     group: no collectives; world = 1 WITH a group (`collective=True`): the same reduce-scatter / all-gather calls on a one-rank
     communicator -- the RCCL branch end to end on a single GPU (tests/test_hip_train.py), bit-identical to the plain step.
-    `update` / `sumsq` default to the HIP kernels; the CPU tests inject torch implementations (there is no CPU product path)."""
+    `update` / `sumsq` default to the HIP kernels; the CPU tests inject torch implementations (there is no CPU product path).
+
+    f16 dynamic loss scaling (`scaler`: an enabled `GradScalerCfg`) -- torch.amp.GradScaler under Lightning's automatic optimisation.
+    All scaler state is one device record, `amp_state` (include/mvldm.h mvldm_amp_state: S, growth tracker, AdamW's own step count,
+    found-inf flag, skipped-step counter); nothing is read back to the host.  The loss gradient carries S, so `flat.grad` holds S x g.
+    One step: the norm is taken of the UNSCALED gradients (1/S^2 applied to the fp64 sum of squares: a large finite scaled gradient
+    cannot overflow it), found-inf = "the all-reduced sum of squares is not finite" -- identical on every rank, so every rank takes the
+    same decision without another collective; the clip coefficient is formed from the unscaled norm (Lightning clips after
+    `scaler.unscale_`); AdamW applies g * clip / S or, on found-inf, leaves masters and moments bit-identical; then one launch updates
+    S / tracker / step count / skips like `torch._amp_update_scale_`.  A SKIPPED step still advances `step_count` (the LR schedule) and
+    the trainer's `global_step`: Lightning steps the scheduler and counts the optimizer step whether or not `scaler.step` skipped
+    `optimizer.step` (and the EMA update at the start of the next window still happens).  AdamW's bias-correction step is the record's
+    count, `adam_step`, which only advances on a taken step.  The 16-bit parameter gather still runs on a skipped step (it gathers
+    unchanged weights: reading the flag on the host to avoid that would cost a sync).
+    `amp`: the four scaler operations (`HipAmpOps` interface: sumsq / clip / update / update_scale); the CPU tests inject torch forms."""
 
     def __init__(self, flat: FlatParams, cfg: OptimizerCfg = None, world: int = 1, rank: int = 0, group=None,
                  bucket_bytes: int = 256 << 20, max_norm: float = 0.1, update=None, sumsq=None, clip=None,
-                 collective: Optional[bool] = None, effective_batch_size: Optional[int] = None, gather_dtype: Optional[torch.dtype] = None):
+                 collective: Optional[bool] = None, effective_batch_size: Optional[int] = None, gather_dtype: Optional[torch.dtype] = None,
+                 scaler: Optional[GradScalerCfg] = None, amp=None):
         cfg = cfg or OptimizerCfg()
         if cfg.name != "AdamW":
             raise NotImplementedError(f"optimizer {cfg.name}: the released config trains with AdamW (baseline.yaml:63)")
@@ -946,6 +990,12 @@ class DistributedOptimizer:
         self.exp_avg_sq = torch.zeros(n_own, dtype=torch.float32, device=dev)
         self.norm = torch.zeros(4, dtype=torch.float32, device=dev)
         self._update, self._sumsq, self._clip = update or _hip_adamw, sumsq or _hip_sumsq, clip or _hip_clip
+        self.scaler = scaler if (scaler is not None and scaler.enabled) else None
+        self.amp_state = None                  # int32 [8] = mvldm_amp_state (S at [0] as fp32 bits)
+        if self.scaler is not None:
+            self.amp_state = torch.zeros(8, dtype=torch.int32, device=dev)
+            self.amp_state[0:1].view(torch.float32).fill_(float(self.scaler.init_scale))
+        self._amp = amp or HipAmpOps()
         self._pending = []
         # ---- 16-bit parameter gather (round 6).  What the next forward needs from the other ranks is their slice of the 16-bit weight
         # PACKS -- a per-layer permutation of RNE_16(master) -- not their fp32 masters (ZeRO-1: a master is only ever updated by its
@@ -1059,13 +1109,17 @@ class DistributedOptimizer:
         self.wait()
         self.flat.wait_readers()          # a re-pack running ahead on the side stream reads the parameters this step overwrites
         g, p = self.flat.grad, self.flat.flat
+        amp = self.amp_state
         own_sq = torch.zeros(1, dtype=torch.float32, device=g.device)
-        for oa, ob in self.owned:
-            own_sq += self._sumsq(g[oa:ob])                 # (a handful of scalars: bookkeeping, not the data path)
+        for oa, ob in self.owned:                           # (a handful of scalars: bookkeeping, not the data path)
+            own_sq += self._sumsq(g[oa:ob]) if amp is None else self._amp.sumsq(g[oa:ob], amp)      # (scaled: the unscaled sum)
         if self.collective:
             import torch.distributed as dist
             dist.all_reduce(own_sq, op=dist.ReduceOp.SUM, group=self.group)
-        self._clip(own_sq, self.max_norm or 0.0, self.norm)     # norm[0] = total norm, norm[1] = clip coefficient
+        if amp is None:
+            self._clip(own_sq, self.max_norm or 0.0, self.norm)     # norm[0] = total norm, norm[1] = clip coefficient
+        else:                                                       # ... and found-inf into the record
+            self._amp.clip(own_sq, self.max_norm or 0.0, self.norm, amp)
         total = self.norm[0]
         self.step_count += 1
         lr, off = self._lr_for_step(), 0
@@ -1079,8 +1133,12 @@ class DistributedOptimizer:
             self._init_gather16()
         for (a, b), (oa, ob) in zip(self.buckets, self.owned):
             n = ob - oa
-            self._update(p[oa:ob], g[oa:ob], self.exp_avg[off:off + n], self.exp_avg_sq[off:off + n], lr, self.betas, self.eps,
-                         self.weight_decay, self.step_count, self.norm)
+            if amp is None:
+                self._update(p[oa:ob], g[oa:ob], self.exp_avg[off:off + n], self.exp_avg_sq[off:off + n], lr, self.betas, self.eps,
+                             self.weight_decay, self.step_count, self.norm)
+            else:
+                self._amp.update(p[oa:ob], g[oa:ob], self.exp_avg[off:off + n], self.exp_avg_sq[off:off + n], lr, self.betas, self.eps,
+                                 self.weight_decay, self.norm, amp)
             off += n
             if g16:
                 self._p16[oa:ob].copy_(p[oa:ob])             # RNE to the pack type
@@ -1090,6 +1148,9 @@ class DistributedOptimizer:
                 src = self._p16 if g16 else p
                 works.append(dist.all_gather_into_tensor(src[a:b], src[oa:ob], group=self.group, async_op=True))
                 self.bytes_gathered += (b - a) * (2 if g16 else 4)
+        if amp is not None:         # after every bucket's AdamW launch (they read the flag and the step count it advances)
+            sc = self.scaler
+            self._amp.update_scale(amp, sc.growth_factor, sc.backoff_factor, sc.growth_interval)
         if self.collective and gloo:
             src, es = (self._p16.view(torch.uint8), 2) if g16 else (p, 1)      # (gloo moves bytes: the 16-bit slices travel as uint8)
             for (a, b) in self.buckets:
@@ -1124,6 +1185,52 @@ class DistributedOptimizer:
             self.masters_exact = self.world == 1
         self.flat.bump()
         return float(total)
+
+    # ---- the f16 loss scaler's state (device record `amp_state`) ----
+    @property
+    def grad_scale(self) -> Optional[torch.Tensor]:
+        """S as an fp32 device scalar (a view of the record: follows every update); None without a scaler"""
+        return None if self.amp_state is None else self.amp_state[0:1].view(torch.float32)[0]
+
+    @property
+    def skipped_steps(self) -> Optional[torch.Tensor]:
+        """optimizer steps skipped on found-inf, an int32 device counter; None without a scaler"""
+        return None if self.amp_state is None else self.amp_state[4]
+
+    @property
+    def adam_step(self) -> int:
+        """AdamW's step count (bias correction): the steps TAKEN -- `step_count` minus the skipped steps under the scaler, `step_count`
+        itself without one (reading it synchronises)"""
+        return self.step_count if self.amp_state is None else int(self.amp_state[2])
+
+    @adam_step.setter
+    def adam_step(self, n: int):
+        if self.amp_state is None:
+            self.step_count = int(n)
+        else:
+            self.amp_state[2:3].fill_(int(n))
+
+    def scaler_state_dict(self) -> dict:
+        """`torch.amp.GradScaler.state_dict()`'s layout (empty without a scaler, like a disabled GradScaler)"""
+        if self.scaler is None:
+            return {}
+        st = self.amp_state.cpu()
+        return {"scale": float(st[0:1].view(torch.float32)[0]), "growth_factor": float(self.scaler.growth_factor),
+                "backoff_factor": float(self.scaler.backoff_factor), "growth_interval": int(self.scaler.growth_interval),
+                "_growth_tracker": int(st[1])}
+
+    def load_scaler_state_dict(self, sd: dict):
+        """`GradScaler.load_state_dict`: the scale and the growth tracker go into the device record, the factors / interval into the
+        config.  A disabled scaler ignores it (as torch's does); AdamW's step count is not part of this layout (`adam_step`)."""
+        if self.scaler is None:
+            return
+        if len(sd) == 0:
+            raise RuntimeError("The source state dict is empty, possibly because it was saved from a disabled instance of GradScaler.")
+        import dataclasses
+        self.scaler = dataclasses.replace(self.scaler, growth_factor=float(sd["growth_factor"]), backoff_factor=float(sd["backoff_factor"]),
+                                          growth_interval=int(sd["growth_interval"]))
+        self.amp_state[0:1].view(torch.float32).fill_(float(sd["scale"]))
+        self.amp_state[1:2].fill_(int(sd["_growth_tracker"]))
 
     def _lr_for_step(self) -> float:
         # the factor in force for optimizer step t (1-based) is the one after t-1 scheduler steps
@@ -1162,6 +1269,33 @@ def _hip_adamw(p, g, m, v, lr, betas, eps, wd, step, norm):
     ops.adamw_step(p, g, m, v, lr, betas, eps, wd, step, 1.0, norm)
 
 
+class HipAmpOps:
+    """the loss scaler's four operations on the device record `state` (mvldm_amp_state) -- the HIP kernels.  The CPU tests inject an
+    object with the same methods written in torch (tests/test_grad_scaler_cpu.py)."""
+
+    @staticmethod
+    def sumsq(g: torch.Tensor, state: torch.Tensor) -> torch.Tensor:
+        """unscaled sum of squares of a slice of the scaled gradient (fp32 [1])"""
+        n = ops.grad_norm_amp(g, 0.0, state)
+        return n[2:3].clone()
+
+    @staticmethod
+    def clip(sumsq: torch.Tensor, max_norm: float, norm_out: torch.Tensor, state: torch.Tensor):
+        """total norm + clip coefficient from the (all-reduced, unscaled) sum of squares; found-inf = it is not finite"""
+        ws = ops.workspace(1024 * 8, sumsq.device, "norm")
+        L.check(L.load().mvldm_grad_norm_amp(sumsq.data_ptr(), 0, sumsq.data_ptr(), max_norm, norm_out.data_ptr(), state.data_ptr(),
+                                             ws.data_ptr(), ops.stream()))
+
+    @staticmethod
+    def update(p, g, m, v, lr, betas, eps, wd, norm, state):
+        """AdamW on g * clip / S with the record's step count; nothing moves on found-inf"""
+        ops.adamw_step_amp(p, g, m, v, lr, state, betas, eps, wd, 1.0, norm)
+
+    @staticmethod
+    def update_scale(state, growth_factor, backoff_factor, growth_interval):
+        ops.amp_update(state, growth_factor, backoff_factor, growth_interval)
+
+
 # ================================================================================================ the training wrapper
 @dataclass
 class TrainCfg:
@@ -1169,6 +1303,7 @@ class TrainCfg:
     accumulate_grad_batches: int = 2     # config/main.yaml:84
     gradient_clip_val: float = 0.1       # config/main.yaml:82
     num_train_timesteps: int = 1000      # config/model/scheduler/ddim.yaml:4
+    grad_scaler: GradScalerCfg = field(default_factory=GradScalerCfg)     # `16-mixed` (baseline.yaml:60): used by an f16 trainer only
 
 
 class EMAWeights:
@@ -1243,9 +1378,11 @@ class MVLDMTrainer:
             p.requires_grad_(False)
         self.flat = _flat_padded(denoiser, world)
         # (the 16-bit parameter gather needs no exact replica of the other ranks' masters -- an EMA over the whole model does)
+        # f16 trains under the dynamic loss scaler (`16-mixed`) unless `train_cfg.grad_scaler.enabled` is False; bf16 / f32 never scale
         self.opt = DistributedOptimizer(self.flat, optimizer_cfg, world, rank, group, bucket_bytes, self.cfg.gradient_clip_val,
                                         collective=collective, effective_batch_size=effective_batch_size,
-                                        gather_dtype=None if ema_decay is not None else self.dtype)
+                                        gather_dtype=None if ema_decay is not None else self.dtype,
+                                        scaler=self.cfg.grad_scaler if dtype == torch.float16 else None)
         self.plans: Dict[tuple, TrainPlan] = {}          # insertion order = least recently used first (plan_for_parts)
         self.max_plans = max(1, int(os.environ.get("MVLDM_TRAIN_MAX_PLANS", "4")))
         self.micro = 0
@@ -1286,7 +1423,8 @@ class MVLDMTrainer:
             # micro-batch plans, A/B knob)
             store = len(parts) > 1 and os.environ.get("MVLDM_TRAIN_STORE_FIRST", "1") != "0"
             tp = TrainPlan(self.denoiser, self.flat, parts, None, None, hl, wl, self.dtype, loss_scale=1.0 / acc,
-                           grad_scale=1.0 / (acc * self.world), graph=use_graph, rays=self.rays, store_first=store)
+                           grad_scale=1.0 / (acc * self.world), graph=use_graph, rays=self.rays, store_first=store,
+                           amp_scale=self.opt.grad_scale)
             if saved is not None:
                 self.flat.grad.copy_(saved)
                 tp.loss.zero_()
@@ -1386,6 +1524,33 @@ class MVLDMTrainer:
         tp = self.plan_for(part["b"], part["vc_eff"], part["v_t"], lat.shape[-2], lat.shape[-1])
         self._stage_part(tp, 0, part)
         return tp
+
+    # ---- the f16 loss scaler (DistributedOptimizer: `16-mixed` semantics) ------------------------------------------
+    @property
+    def grad_scale(self) -> Optional[torch.Tensor]:
+        """the loss scale S, an fp32 device scalar (None unless the trainer is f16 with the scaler on); `flat.grad` holds S x g"""
+        return self.opt.grad_scale
+
+    @property
+    def skipped_steps(self) -> Optional[torch.Tensor]:
+        """optimizer steps skipped because a gradient was not finite, an int32 device counter (None without the scaler)"""
+        return self.opt.skipped_steps
+
+    @property
+    def adam_step(self) -> int:
+        """AdamW's own step count: `opt.step_count` (== global_step in a plain run) minus the skipped steps"""
+        return self.opt.adam_step
+
+    @adam_step.setter
+    def adam_step(self, n: int):
+        self.opt.adam_step = n
+
+    def scaler_state_dict(self) -> dict:
+        """the scaler's state in `torch.amp.GradScaler.state_dict()`'s key layout ({} without the scaler)"""
+        return self.opt.scaler_state_dict()
+
+    def load_scaler_state_dict(self, sd: dict):
+        self.opt.load_scaler_state_dict(sd)
 
     def sync_masters(self):
         """multi-rank runs with the 16-bit parameter gather (DistributedOptimizer): make every rank's fp32 masters exact again -- call
@@ -1637,7 +1802,10 @@ def gradient_drift_vs_f32(trainer: "MVLDMTrainer", batch, **choices) -> dict:
         plan.loss.zero_()
         plan.run()
         torch.cuda.synchronize()
-        out.append((flat.grad.clone(), float(plan.loss[0]) * acc))
+        g_ = flat.grad.clone()
+        if plan is tp and trainer.grad_scale is not None:
+            g_ /= trainer.grad_scale            # f16 under the loss scaler: the plan's gradients carry S
+        out.append((g_, float(plan.loss[0]) * acc))
     flat.zero_grad()
     tp.loss.zero_()
     (g_lo, l_lo), (g_hi, l_hi) = out
