@@ -195,8 +195,8 @@ void attention_kernel(const AttnParams p) {
         const bool in_tile = idx < BKV * NCH;
         const bool live = in_tile && ch * EPC < d;
         if (live) live_bits |= 1u << j;
-        st_ko[j] = live ? ((unsigned)key * (unsigned)p.ld_k + (unsigned)(ch * EPC)) * (unsigned)sizeof(T) : 0xFFFFFFF0u;
-        st_vo[j] = live ? ((unsigned)key * (unsigned)p.ld_v + (unsigned)(ch * EPC)) * (unsigned)sizeof(T) : 0xFFFFFFF0u;
+        st_ko[j] = live ? ((unsigned)key * (unsigned)p.ld_k + (unsigned)(ch * EPC)) * (unsigned)sizeof(T) : kBufOob;
+        st_vo[j] = live ? ((unsigned)key * (unsigned)p.ld_v + (unsigned)(ch * EPC)) * (unsigned)sizeof(T) : kBufOob;
         if (in_tile && !live) {
             Chunk<T> zk, zv;
             zk.zero();

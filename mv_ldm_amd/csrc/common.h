@@ -23,6 +23,12 @@ typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
 
 constexpr int WAVE = 64;
 
+// Offset handed to a buffer load / store / LDS-DMA instead of a real one where nothing is to be moved: beyond every descriptor's byte range
+// (the kernels' applicability rules keep those below 4e9), so the bounds check returns zeros / drops the store -- no zero page, no select.
+constexpr unsigned kBufOob = 0xFFFFFFF0u;
+// s_waitcnt immediate for vmcnt(n), expcnt / lgkmcnt untouched (gfx9 encoding: vmcnt is bits 3:0 and 15:14); & ~0x0F00 adds lgkmcnt(0)
+constexpr int waitcnt_vmcnt(int n) { return (n & 15) | ((n >> 4) << 14) | 0x0F70; }
+
 int set_error(int code, const char* fmt, ...);
 #define MVLDM_CHECK_HIP(expr)                                                              \
     do {                                                                                   \

@@ -558,7 +558,6 @@ __global__ __launch_bounds__(WM* WN * 64) void igemm_kernel(const IgemmParams p)
 // `buffer_load_dwordx4 ... lds` with a scalar soffset (channel block / K position), the M0 updates, the
 // fragment ds_reads and the MFMAs -- no vector address arithmetic at all (PMC of the previous loop: 11
 // VALU + 16 SALU instructions per MFMA).
-constexpr unsigned kOob = 0xFFFFFFF0u;
 
 // Per-lane source addressing of the A pieces.  Without upsampling every tap of a pixel is the centre tap's
 // byte offset plus a displacement that is the same for all lanes, so a lane keeps ONE offset per piece and
@@ -602,8 +601,8 @@ __device__ __forceinline__ void bl_issue(const IgemmParams& p, char* stage_base,
             v1 = ad.a1[DUAL ? t : 0][DUAL ? it : 0];
         } else {
             const bool ok = (ad.mask[it] >> t) & 1u;
-            v0 = ok ? ad.a0[0][it] : kOob;
-            v1 = ok ? ad.a1[0][DUAL ? it : 0] : kOob;
+            v0 = ok ? ad.a0[0][it] : kBufOob;
+            v1 = ok ? ad.a1[0][DUAL ? it : 0] : kBufOob;
         }
         if (from0) __builtin_amdgcn_raw_ptr_buffer_load_lds(r0, dst, 16, v0, soff, 0, 0);
         else __builtin_amdgcn_raw_ptr_buffer_load_lds(r1, dst, 16, v1, soff, 0, 0);
@@ -713,8 +712,8 @@ __global__ __launch_bounds__(WM* WN * 64) void igemm_bl_kernel(const IgemmParams
                 const int iy = y0 + t / KS, ix = x0 + t % KS;
                 const bool ok = (unsigned)iy < hs && (unsigned)ix < wsz;
                 const unsigned pix = (unsigned)(img * p.h_in + (iy >> 1)) * (unsigned)p.w_in + (unsigned)(ix >> 1);
-                ad.a0[t][it] = ok ? (pix * (unsigned)p.c0 + chunk) * 2u : kOob;
-                if constexpr (DUAL) ad.a1[t][it] = ok ? (pix * (unsigned)p.c1 + chunk) * 2u : kOob;
+                ad.a0[t][it] = ok ? (pix * (unsigned)p.c0 + chunk) * 2u : kBufOob;
+                if constexpr (DUAL) ad.a1[t][it] = ok ? (pix * (unsigned)p.c1 + chunk) * 2u : kBufOob;
             }
         } else {
             // centre tap (inside the image for every live row: checked on the host)
@@ -737,7 +736,7 @@ __global__ __launch_bounds__(WM* WN * 64) void igemm_bl_kernel(const IgemmParams
         const int row = (wave + NW * it) * 8 + rsub;
         const int n = tn * BN + row;
         const unsigned chunk = (unsigned)((slot ^ ((row >> 1) & 7)) * EPC);
-        vb[it] = n < p.n_pad ? ((unsigned)n * (unsigned)p.k_pad + chunk) * 2u : kOob;
+        vb[it] = n < p.n_pad ? ((unsigned)n * (unsigned)p.k_pad + chunk) * 2u : kBufOob;
     }
 
     f32x16 acc[TM][TN];
@@ -993,8 +992,8 @@ __global__ __launch_bounds__(512) void igemm_halo_kernel(const IgemmParams p, in
         const int pm = m0 - lead + hr;
         const bool ok = q < np && pm >= 0 && pm < m_tot;
         const unsigned chunk = (unsigned)((slot ^ ((hr >> 1) & 7)) * EPC);
-        off0[k] = ok ? ((unsigned)pm * (unsigned)p.c0 + chunk) * 2u : kOob;
-        if constexpr (DUAL) off1[k] = ok ? ((unsigned)pm * (unsigned)p.c1 + chunk) * 2u : kOob;
+        off0[k] = ok ? ((unsigned)pm * (unsigned)p.c0 + chunk) * 2u : kBufOob;
+        if constexpr (DUAL) off1[k] = ok ? ((unsigned)pm * (unsigned)p.c1 + chunk) * 2u : kBufOob;
     }
     unsigned vb[B_IT];
 #pragma unroll
@@ -1002,7 +1001,7 @@ __global__ __launch_bounds__(512) void igemm_halo_kernel(const IgemmParams p, in
         const int row = (wave + NW * it) * 8 + rsub;
         const int n = tn * BN + row;
         const unsigned chunk = (unsigned)((slot ^ ((row >> 1) & 7)) * EPC);
-        vb[it] = n < p.n_pad ? ((unsigned)n * (unsigned)p.k_pad + chunk) * 2u : kOob;
+        vb[it] = n < p.n_pad ? ((unsigned)n * (unsigned)p.k_pad + chunk) * 2u : kBufOob;
     }
     // per-row tap validity
     unsigned mask[TM];
@@ -1037,15 +1036,15 @@ __global__ __launch_bounds__(512) void igemm_halo_kernel(const IgemmParams p, in
     {                                                                                                                  \
         const int q_ = wave + NW * (k_);                                                                               \
         const bool real_ = (cb_) < cb1 && q_ < np;                                                                     \
-        halo_issue_a<DUAL>(p, real_ ? smem + ((cb_) & 1) * a_bytes + q_ * 1024 : dummy, real_ ? off0[k_] : kOob,       \
-                           real_ ? off1[DUAL ? (k_) : 0] : kOob, (cb_) < cb1 ? (cb_) : 0);                             \
+        halo_issue_a<DUAL>(p, real_ ? smem + ((cb_) & 1) * a_bytes + q_ * 1024 : dummy, real_ ? off0[k_] : kBufOob,     \
+                           real_ ? off1[DUAL ? (k_) : 0] : kBufOob, (cb_) < cb1 ? (cb_) : 0);                           \
     }
     // W tile of K-tile index kt_ (= cb*9 + tap) into ring slot ws_; past the end of K: zeros
 #define MVLDM_HALO_W(kt_, ws_)                                                                                         \
     {                                                                                                                  \
         const bool real_ = (kt_) < cb1 * 9;                                                                            \
         _Pragma("unroll") for (int it = 0; it < B_IT; ++it)                                                            \
-            halo_issue_w(p, wring + (ws_) * W_BYTES + (wave + NW * it) * 1024, real_ ? vb[it] : kOob, real_ ? (kt_) * 128 : 0); \
+            halo_issue_w(p, wring + (ws_) * W_BYTES + (wave + NW * it) * 1024, real_ ? vb[it] : kBufOob, real_ ? (kt_) * 128 : 0); \
     }
 
     // prologue: the whole halo of block 0, W tiles 0..2
@@ -1161,7 +1160,7 @@ __global__ __launch_bounds__(512) void igemm_halow_kernel(const IgemmParams p, i
         const int pm = m0 - lead + hr;
         const bool ok = q < np && pm >= 0 && pm < m_tot;
         const unsigned chunk = (unsigned)((slot ^ ((hr >> 1) & 7)) * EPC);
-        off0[k] = ok ? ((unsigned)pm * (unsigned)p.c0 + chunk) * 2u : kOob;
+        off0[k] = ok ? ((unsigned)pm * (unsigned)p.c0 + chunk) * 2u : kBufOob;
     }
     unsigned vb[B_IT];
 #pragma unroll
@@ -1169,7 +1168,7 @@ __global__ __launch_bounds__(512) void igemm_halow_kernel(const IgemmParams p, i
         const int row = (wave + NW * it) * 8 + rsub;
         const int n = tn * BN + row;
         const unsigned chunk = (unsigned)((slot ^ ((row >> 1) & 7)) * EPC);
-        vb[it] = n < p.n_pad ? ((unsigned)n * (unsigned)p.k_pad + chunk) * 2u : kOob;
+        vb[it] = n < p.n_pad ? ((unsigned)n * (unsigned)p.k_pad + chunk) * 2u : kBufOob;
     }
     unsigned mask[TM];
     int rloc[TM];
@@ -1202,14 +1201,14 @@ __global__ __launch_bounds__(512) void igemm_halow_kernel(const IgemmParams p, i
     {                                                                                                                  \
         const int q_ = wave + NW * (k_);                                                                               \
         const bool real_ = (cb_) < cb1 && q_ < np;                                                                     \
-        halo_issue_a<false>(p, real_ ? smem + ((cb_) & 1) * a_bytes + q_ * 1024 : dummy, real_ ? off0[k_] : kOob, kOob, \
+        halo_issue_a<false>(p, real_ ? smem + ((cb_) & 1) * a_bytes + q_ * 1024 : dummy, real_ ? off0[k_] : kBufOob, kBufOob,  \
                             (cb_) < cb1 ? (cb_) : 0);                                                                  \
     }
 #define MVLDM_HW_W(kt_, ws_)                                                                                           \
     {                                                                                                                  \
         const bool real_ = (kt_) < cb1 * 9;                                                                            \
         _Pragma("unroll") for (int it = 0; it < B_IT; ++it)                                                            \
-            halo_issue_w(p, wring + (ws_) * W_BYTES + (wave + NW * it) * 1024, real_ ? vb[it] : kOob, real_ ? (kt_) * 128 : 0); \
+            halo_issue_w(p, wring + (ws_) * W_BYTES + (wave + NW * it) * 1024, real_ ? vb[it] : kBufOob, real_ ? (kt_) * 128 : 0); \
     }
 
     // prologue: the whole halo of block 0, W tiles 0 and 1

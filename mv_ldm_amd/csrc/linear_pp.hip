@@ -24,10 +24,9 @@
 // activation row block crosses the fabric into ONE L2.
 // Same XOR-swizzled 128-byte LDS rows and fragment reads as igemm.hip.  GEGLU: value / gate column blocks are adjacent (the
 // packed weight interleaves them by 32): step 1/3 evaluate GELU(gate) of row block 0/1 into registers, step 2/4 the product.
-#include <algorithm>
 #include <cstdlib>
 
-#include "common.h"
+#include "linear_common.h"
 
 namespace mvldm {
 
@@ -49,23 +48,11 @@ static const int kLppFake = knob_int("MVLDM_LPP_FAKE", 0);
 static constexpr int kLppFake = 0;
 #endif
 
-constexpr unsigned kLinOob = 0xFFFFFFF0u;
-constexpr unsigned kRowNone = 0xFFFFFFFFu;
 constexpr int LP_BM = 256, LP_BN = 128, LP_NW = 8, LP_STAGE = (LP_BM + LP_BN) * 128;
 constexpr int LP_SLAB = 3 * LP_STAGE;           // bias slab of the next tile: 128 floats (+ 512 bytes the DMA instruction also writes)
 constexpr int LP_SMEM = LP_SLAB + 1024;
-constexpr int kWaitAllButRing = 0x0F76;         // s_waitcnt vmcnt(6), expcnt / lgkmcnt untouched (gfx9 encoding)
-constexpr int kWaitVm0 = 0x0F70;
-
-template <typename T> struct LpMma;
-template <> struct LpMma<bf16_t> {
-    using Frag = bf16x8;
-    static __device__ __forceinline__ f32x16 mma(Frag a, Frag b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
-};
-template <> struct LpMma<f16_t> {
-    using Frag = f16x8;
-    static __device__ __forceinline__ f32x16 mma(Frag a, Frag b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
-};
+constexpr int kWaitAllButRing = waitcnt_vmcnt(6);   // everything but the newest step's six DMA pieces
+constexpr int kWaitVm0 = waitcnt_vmcnt(0);
 
 // (buffer descriptors only in free functions: an opaque __amdgpu_buffer_rsrc_t inside a lambda trips hipcc's host pass)
 __device__ __forceinline__ void lp_issue(const LinPPParams& p, char* stage, int wave, int kt, const unsigned (&ao)[2][4], const unsigned (&bo)[2]) {
@@ -98,15 +85,15 @@ __device__ __forceinline__ void lp_offsets(const LinPPParams& p, bool valid, int
         const int row = (wave + LP_NW * it) * 8 + rsub;
         const int m = tm * LP_BM + row;
         const unsigned chunk = (unsigned)((slot ^ ((row >> 1) & 7)) * 8);
-        ao[0][it] = (valid && m < p.M) ? ((unsigned)m * (unsigned)p.c0 + chunk) * 2u : kLinOob;
-        ao[1][it] = (valid && m < p.M) ? ((unsigned)m * (unsigned)p.c1 + chunk) * 2u : kLinOob;
+        ao[0][it] = (valid && m < p.M) ? ((unsigned)m * (unsigned)p.c0 + chunk) * 2u : kBufOob;
+        ao[1][it] = (valid && m < p.M) ? ((unsigned)m * (unsigned)p.c1 + chunk) * 2u : kBufOob;
     }
 #pragma unroll
     for (int it = 0; it < 2; ++it) {
         const int row = (wave + LP_NW * it) * 8 + rsub;
         const int n = tn * LP_BN + row;
         const unsigned chunk = (unsigned)((slot ^ ((row >> 1) & 7)) * 8);
-        bo[it] = (valid && n < p.n_pad) ? ((unsigned)n * (unsigned)p.K + chunk) * 2u : kLinOob;
+        bo[it] = (valid && n < p.n_pad) ? ((unsigned)n * (unsigned)p.K + chunk) * 2u : kBufOob;
     }
 }
 
@@ -119,13 +106,8 @@ __device__ __forceinline__ void lp_issue_bias(const LinPPParams& p, char* smem, 
         const int blk = pc >> 5, w = pc & 31;
         oc = ((blk & 1) ? p.n_dst : 0) + (blk >> 1) * 32 + w;
     }
-    const unsigned off = (valid && lane < 32 && pc < p.n_out) ? (unsigned)oc * 4u : kLinOob;
+    const unsigned off = (valid && lane < 32 && pc < p.n_out) ? (unsigned)oc * 4u : kBufOob;
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rb, (__attribute__((address_space(3))) void*)(smem + LP_SLAB), 16, off, 0, 0, 0);
-}
-
-__device__ __forceinline__ u32x4 lp_load_res(const LinPPParams& p, unsigned off) {
-    const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.residual), 0, p.res_bytes, 0x00020000);
-    return __builtin_amdgcn_raw_buffer_load_b128(rr, off, 0, 0);
 }
 
 // two 16-byte stores the compiler's wait-count bookkeeping does not see (header).  Store data is read at issue on gfx9, but over
@@ -136,8 +118,8 @@ __device__ __forceinline__ void lp_store2(const u32x4& rdst, const u32x4& d0, un
                  ::"v"(d0), "v"(o0), "v"(d1), "v"(o1), "s"(rdst) : "memory");
 }
 
-template <typename T> __device__ __forceinline__ typename LpMma<T>::Frag lp_frag(const char* tile, int r, int kc) {
-    return *reinterpret_cast<const typename LpMma<T>::Frag*>(tile + r * 128 + ((kc ^ ((r >> 1) & 7)) << 4));
+template <typename T> __device__ __forceinline__ typename LinMma<T>::Frag lp_frag(const char* tile, int r, int kc) {
+    return *reinterpret_cast<const typename LinMma<T>::Frag*>(tile + r * 128 + ((kc ^ ((r >> 1) & 7)) << 4));
 }
 
 #ifdef MVLDM_EXPERIMENTS_NOGELU
@@ -148,18 +130,14 @@ template <typename T> __device__ __forceinline__ typename LpMma<T>::Frag lp_frag
 
 // epilogue-side coordinates of the finished tile, per lane (lane & 31 = row inside a 32-row block)
 struct LpEpi {
-    unsigned row_dst[2], row_res[2];   // byte offset of this lane's row in dst / residual for row block i, kRowNone past M
+    unsigned row_dst[2], row_res[2];   // byte offset of this lane's row in dst / residual for row block i, kLinRowNone past M
     int col0;                          // first output column of the wave (GEGLU: of the value / product columns)
 };
-
-__device__ __forceinline__ unsigned lp_off(unsigned row, int col, int n_dst) {
-    return (row != kRowNone && col < n_dst) ? row + (unsigned)col * 2u : kLinOob;
-}
 
 // epilogue slot SLOT of the finished tile.  plain / SiLU / GELU: SLOT = 2i + j = accumulator block (i, j).  GEGLU: SLOT = 2i + ph:
 // ph 0 = GELU of the gate block (i, 1) into `gl`, ph 1 = value block (i, 0) times `gl`.
 // In: accP (bias already inside, see the handover), res = the two residual chunks of this lane.  Out: two packed 16-byte chunks
-// and their dst offsets (kLinOob where nothing is to be stored).
+// and their dst offsets (kBufOob where nothing is to be stored).
 template <typename T, int EPI, bool RES, int SLOT>
 __device__ __forceinline__ void lp_epi_compute(const LinPPParams& p, const f32x16 (&accP)[2][2], const LpEpi& ep, const u32x4 (&res)[2], u32x4 (&out)[2],
                                                unsigned (&out_off)[2], float (&gl)[16], int hi) {
@@ -207,7 +185,7 @@ __device__ __forceinline__ void lp_epi_compute(const LinPPParams& p, const f32x1
             for (int e = 0; e < 8; ++e) oc.set(e, c[8 * g + e] * p.out_scale);
         }
         out[g] = oc.raw;
-        out_off[g] = lp_off(ep.row_dst[i], col, p.n_dst);
+        out_off[g] = lin_off(ep.row_dst[i], col, p.n_dst);
     }
 }
 
@@ -215,7 +193,7 @@ __device__ __forceinline__ void lp_epi_compute(const LinPPParams& p, const f32x1
 template <int SLOT> __device__ __forceinline__ void lp_res_fetch(const LinPPParams& p, const LpEpi& ep, u32x4 (&res)[2], int hi) {
     constexpr int i = SLOT >> 1, j = SLOT & 1;
 #pragma unroll
-    for (int g = 0; g < 2; ++g) res[g] = lp_load_res(p, lp_off(ep.row_res[i], ep.col0 + 32 * j + 16 * g + 8 * hi, p.n_dst));
+    for (int g = 0; g < 2; ++g) res[g] = lin_load_res(p.residual, p.res_bytes, lin_off(ep.row_res[i], ep.col0 + 32 * j + 16 * g + 8 * hi, p.n_dst));
 }
 
 // walks the tiles of a workgroup (all wave-uniform)
@@ -264,9 +242,9 @@ __global__ __launch_bounds__(512) void linear_pp_kernel(const LinPPParams p) {
     f32x16 accC[2][2], accP[2][2];
     float gl[16];
     u32x4 res[2][2], out[2];
-    unsigned out_off[2] = {kLinOob, kLinOob};
+    unsigned out_off[2] = {kBufOob, kBufOob};
     LpEpi ep;
-    ep.row_dst[0] = ep.row_dst[1] = ep.row_res[0] = ep.row_res[1] = kRowNone;
+    ep.row_dst[0] = ep.row_dst[1] = ep.row_res[0] = ep.row_res[1] = kLinRowNone;
     ep.col0 = 0;
 #pragma unroll
     for (int k = 0; k < 16; ++k) gl[k] = 0.f;
@@ -311,7 +289,7 @@ __global__ __launch_bounds__(512) void linear_pp_kernel(const LinPPParams p) {
     __builtin_amdgcn_s_barrier();
 #define LP_STORE_OUT()                                                        \
     lp_store2(rdst, out[0], out_off[0], out[1], out_off[1]);                    \
-    out_off[0] = out_off[1] = kLinOob;
+    out_off[0] = out_off[1] = kBufOob;
 #define LP_RING_ISSUE()                                                                                   \
     {                                                                                                     \
         if (++kt_i == p.k_tiles) {                                                                        \
@@ -325,11 +303,11 @@ __global__ __launch_bounds__(512) void linear_pp_kernel(const LinPPParams p) {
 // the 16 MFMAs of a step (transposed product: W fragment is the A operand)
 #define LP_MFMA_HALF(KK0)                                                                                 \
     _Pragma("unroll") for (int kk = (KK0); kk < (KK0) + 2; ++kk) {                                        \
-        typename LpMma<T>::Frag fa[2], fb[2];                                                             \
+        typename LinMma<T>::Frag fa[2], fb[2];                                                            \
         _Pragma("unroll") for (int i = 0; i < 2; ++i) fa[i] = lp_frag<T>(at, wm * 64 + i * 32 + l31, kk * 2 + hi); \
         _Pragma("unroll") for (int j = 0; j < 2; ++j) fb[j] = lp_frag<T>(bt, wn * 64 + j * 32 + l31, kk * 2 + hi); \
         _Pragma("unroll") for (int i = 0; i < 2; ++i) _Pragma("unroll") for (int j = 0; j < 2; ++j)       \
-            accC[i][j] = LpMma<T>::mma(fb[j], fa[i], accC[i][j]);                                         \
+            accC[i][j] = LinMma<T>::mma(fb[j], fa[i], accC[i][j]);                                        \
     }
 #define LP_STEP_END() rs = rs == 2 ? 0 : rs + 1;
 
@@ -409,8 +387,8 @@ __global__ __launch_bounds__(512) void linear_pp_kernel(const LinPPParams p) {
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
                 const int m = tm * LP_BM + wm * 64 + i * 32 + l31;
-                ep.row_dst[i] = m < p.M ? (unsigned)m * (unsigned)p.dst_ld * 2u : kRowNone;
-                ep.row_res[i] = m < p.M ? (unsigned)m * (unsigned)p.n_dst * 2u : kRowNone;
+                ep.row_dst[i] = m < p.M ? (unsigned)m * (unsigned)p.dst_ld * 2u : kLinRowNone;
+                ep.row_res[i] = m < p.M ? (unsigned)m * (unsigned)p.n_dst * 2u : kLinRowNone;
             }
             ep.col0 = GEGLU ? (tn * LP_BN + wn * 64) >> 1 : tn * LP_BN + wn * 64;
 #pragma unroll
@@ -461,33 +439,14 @@ template <typename T, int EPI, bool RES> static int linear_pp_launch(const LinPP
 int linear_pp_run(const mvldm_igemm_desc& d, hipStream_t s) {
     MVLDM_REQUIRE(linear_pp_applicable(d), "igemm: tile 12 (persistent pipelined Linear) does not apply to this problem");
     LinPPParams p;
-    p.a = d.src0; p.a1 = d.src1; p.w = d.weight; p.bias = d.bias; p.residual = d.residual; p.dst = d.dst;
-    p.M = d.n_img * d.h_out * d.w_out; p.K = d.c0 + d.c1; p.c0 = d.c0; p.c1 = d.c1; p.kt0 = d.c0 / 64; p.n_out = d.n_out; p.n_pad = d.n_pad;
-    p.n_dst = d.epilogue == MVLDM_EPI_GEGLU ? d.n_out / 2 : d.n_out;
-    p.dst_ld = d.dst_ld > 0 ? d.dst_ld : p.n_dst;
-    p.k_tiles = p.K / 64; p.out_scale = d.out_scale;
+    lin_fill_params2(p, d, kLppFake);
+    p.k_tiles = p.K / 64;
     p.tiles_m = (p.M + LP_BM - 1) / LP_BM; p.tiles_n = (d.n_pad + LP_BN - 1) / LP_BN;
     p.m_per = (p.tiles_m + 7) / 8;
-    p.a_bytes = (unsigned)((double)p.M * p.c0 * 2.0); p.a1_bytes = (unsigned)((double)p.M * p.c1 * 2.0); p.w_bytes = (unsigned)((double)d.n_pad * d.k_pad * 2.0);
-    p.bias_bytes = d.bias ? (unsigned)d.n_out * 4u : 0u;
-    p.res_bytes = d.residual ? (unsigned)((double)p.M * p.n_dst * 2.0) : 0u;
-    p.dst_bytes = (unsigned)((double)p.M * p.dst_ld * 2.0);
-    if (kLppFake & 1) p.a_bytes = p.a1_bytes = 0;
-    if (kLppFake & 2) p.w_bytes = 0;
-    if (kLppFake & 4) p.dst_bytes = 0;
-    static int n_cu = 0;
-    if (!n_cu) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-            n_cu = prop.multiProcessorCount;
-        else
-            n_cu = 256;
-    }
     // workgroups per XCD: one per CU, fewer when the busiest XCD has fewer tiles.  Unit length: the most consecutive column
     // tiles (= L2 hits on the activation rows) for which the row blocks in flight on an XCD -- ceil(wpx / units per row block)
     // + 1 of 256 x K x 2 bytes -- stay within about half of its 4 MB L2
-    const int wpx = std::max(1, std::min(n_cu / 8, p.m_per * p.tiles_n));
+    const int wpx = std::max(1, std::min(cu_count() / 8, p.m_per * p.tiles_n));
     const double rb_bytes = 256.0 * p.K * 2.0;
     p.cpt = 1;
     for (int c = p.tiles_n; c >= 1; --c) {

@@ -29,10 +29,9 @@
 // (BK = 64, the XOR-swizzled 128-byte LDS rows of igemm.hip) and the deepest ring 160 KB allow.  Write-back (not streaming) stores:
 // the L2 acknowledges a tile's store burst (160 KB per CU, every CU at once) long before HBM has taken it, which is what the next
 // tile's first counted wait needs (QKV 712 -> 552 us).
-#include <algorithm>
 #include <cstdlib>
 
-#include "common.h"
+#include "linear_common.h"
 
 namespace mvldm {
 
@@ -66,8 +65,6 @@ static constexpr int kPwFake = 0;
 #define PW_GELU(x) gelu_erf_16(x)
 #endif
 
-constexpr unsigned kPwOob = 0xFFFFFFF0u;
-constexpr unsigned kPwRowNone = 0xFFFFFFFFu;
 constexpr int PW_BM = 256, PW_NW = 8;
 #ifndef PW_SP3
 #define PW_SP3 4      // placement of a middle step's pieces (PwGeo::Q*; experiment builds override it: tools/pw_spread.sh, profiles/r06_pw_spread_variants.txt)
@@ -87,25 +84,6 @@ template <int TN> struct PwGeo {
     static constexpr int SLAB = RING;                   // bias of the tile's BN packed columns
     static constexpr int SMEM = SLAB + 2048;
 };
-
-constexpr int pw_wait(int n) { return (n & 15) | ((n >> 4) << 14) | 0x0F70; }   // s_waitcnt vmcnt(n), expcnt / lgkmcnt untouched (gfx9 encoding)
-
-template <typename T> struct PwMma;
-template <> struct PwMma<bf16_t> {
-    using Frag = bf16x8;
-    static __device__ __forceinline__ f32x16 mma(Frag a, Frag b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
-};
-template <> struct PwMma<f16_t> {
-    using Frag = f16x8;
-    static __device__ __forceinline__ f32x16 mma(Frag a, Frag b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
-};
-
-// MFMA M index mu (= lane & 31 of the W-fragment read) -> column of the 32-column block it is fed from (header).  The permutation
-// maps each 16-lane group of a ds_read_b128 onto the same SET of rows as the identity, so the swizzle stays conflict-free.
-__device__ __forceinline__ int pw_perm(int mu) {
-    const int a = mu >> 3, h = (mu >> 2) & 1, e = mu & 3;
-    return 16 * (a >> 1) + 8 * h + 4 * (a & 1) + e;
-}
 
 // Source addressing of a wave's DMA pieces.  Piece `it` of a wave covers tile rows (wave + 8 it) * 8 .. + 7, a lane fetches the
 // 16-byte chunk that belongs at its (linear) LDS position under the XOR swizzle; (row >> 1) & 7 does not depend on `it`, so ONE
@@ -135,7 +113,7 @@ __device__ __forceinline__ void pw_issue_a(const LinPWParams& p, char* smem, int
     const int row = wave * 8 + (lane >> 3);
 #pragma unroll
     for (int it = (LO > 0 ? LO : 0); it < (HI < G::A_IT ? HI : G::A_IT); ++it) {
-        const unsigned off = (ad.valid && ad.m0 + row + 64 * it < p.M) ? v : kPwOob;
+        const unsigned off = (ad.valid && ad.m0 + row + 64 * it < p.M) ? v : kBufOob;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (__attribute__((address_space(3))) void*)(stage + (wave + PW_NW * it) * 1024), 16, off,
                                                  soff + it * 128 * c, 0, 0);
     }
@@ -149,7 +127,7 @@ __device__ __forceinline__ void pw_issue_w(const LinPWParams& p, char* smem, int
 #pragma unroll
     for (int it = (LO > 0 ? LO : 0); it < (HI < G::W_IT ? HI : G::W_IT); ++it) {
         // (n_pad is a multiple of 64 = the row stride of the pieces: a piece is inside the packed weight or outside as a whole)
-        const unsigned off = (ad.valid && ad.n0 + 64 * it < p.n_pad) ? ad.w : kPwOob;
+        const unsigned off = (ad.valid && ad.n0 + 64 * it < p.n_pad) ? ad.w : kBufOob;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (__attribute__((address_space(3))) void*)(stage + (wave + PW_NW * it) * 1024), 16, off,
                                                  soff + it * 128 * p.K, 0, 0);
     }
@@ -179,7 +157,7 @@ __device__ __forceinline__ void pw_touch_a(const LinPWParams& p, char* smem, int
     const int c = second ? p.c1 : p.c0;
     const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(abase), 0, abytes, 0x00020000);
     const int m = tm * PW_BM + wave * 32 + (lane >> 1);
-    const unsigned off = (valid && m < p.M) ? ((unsigned)m * (unsigned)c * 2u + (unsigned)(lane & 1) * 64u) : kPwOob;
+    const unsigned off = (valid && m < p.M) ? ((unsigned)m * (unsigned)c * 2u + (unsigned)(lane & 1) * 64u) : kBufOob;
     __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (__attribute__((address_space(3))) void*)(smem + G::SLAB + 1792), 4, off,
                                              (second ? ks - p.kt0 : ks) * 128, 0, 0);
 }
@@ -199,7 +177,8 @@ __device__ __forceinline__ void pw_offsets(const LinPWParams& p, bool valid, int
     ad.valid = valid;
 }
 
-// byte offset (into the torch-layout bias) of packed columns 4t .. 4t+3 of tile column tn, out of range past the tile / the layer
+// byte offset (into the torch-layout bias) of packed columns 4t .. 4t+3 of tile column tn, out of range past the tile / the layer: what
+// lin_load_bias computes, for the inline-asm load of the next tile's bias in the last step
 template <int TN>
 __device__ __forceinline__ unsigned pw_bias_off(const LinPWParams& p, bool geglu, bool valid, int tn, int t) {
     using G = PwGeo<TN>;
@@ -209,22 +188,7 @@ __device__ __forceinline__ unsigned pw_bias_off(const LinPWParams& p, bool geglu
         const int blk = pc >> 5, w = pc & 31;
         oc = ((blk & 1) ? p.n_dst : 0) + (blk >> 1) * 32 + w;
     }
-    return (valid && 4 * t < G::BN && pc < p.n_out) ? (unsigned)oc * 4u : kPwOob;
-}
-
-// bias of the BN packed columns of tile column tn: thread t fetches packed columns 4t .. 4t+3 (zeros past the tile / without a bias)
-template <int TN>
-__device__ __forceinline__ u32x4 pw_load_bias(const LinPWParams& p, bool geglu, bool valid, int tn, int t) {
-    using G = PwGeo<TN>;
-    const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.bias), 0, p.bias_bytes, 0x00020000);
-    const int pc = tn * G::BN + 4 * t;                          // packed column
-    int oc = pc;                                                // column of the torch-layout bias
-    if (geglu) {
-        const int blk = pc >> 5, w = pc & 31;
-        oc = ((blk & 1) ? p.n_dst : 0) + (blk >> 1) * 32 + w;
-    }
-    const unsigned off = (valid && 4 * t < G::BN && pc < p.n_out) ? (unsigned)oc * 4u : kPwOob;
-    return __builtin_amdgcn_raw_buffer_load_b128(rb, off, 0, 0);
+    return (valid && 4 * t < G::BN && pc < p.n_out) ? (unsigned)oc * 4u : kBufOob;
 }
 
 // two 16-byte stores the compiler's wait-count bookkeeping does not see (header).  Every asm VMEM statement opens with `s_nop 4`: its
@@ -240,10 +204,6 @@ __device__ __forceinline__ void pw_store2(const u32x4& rdst, const u32x4& d0, un
     else
         asm volatile("s_nop 4\n\tbuffer_store_dwordx4 %0, %1, %4, 0 offen\n\tbuffer_store_dwordx4 %2, %3, %4, 0 offen\n\ts_nop 2"
                      ::"v"(d0), "v"(o0), "v"(d1), "v"(o1), "s"(rdst) : "memory");
-}
-
-template <typename T> __device__ __forceinline__ typename PwMma<T>::Frag pw_frag(const char* p) {
-    return *reinterpret_cast<const typename PwMma<T>::Frag*>(p);
 }
 
 // ---- whole-line epilogue traffic (round 6) ---------------------------------------------------------------------------------------------
@@ -283,64 +243,13 @@ __device__ __forceinline__ unsigned pw_line_off(int M, int tm, int wm, int i, in
     const int t = 2 * (j & 1) + half, k = l31 & 3;
     const int m = tm * PW_BM + wm * 64 + i * 32 + (l31 & ~3) + t;
     const int col = col0 + 32 * (j & ~1) + 8 * (2 * k + hi);
-    return (m < M && col < n_dst) ? ((unsigned)m * (unsigned)ld + (unsigned)col) * 2u : kPwOob;
-}
-__device__ __forceinline__ unsigned pw_off(unsigned row, int col, int n_dst) {
-    return (row != kPwRowNone && col < n_dst) ? row + (unsigned)col * 2u : kPwOob;
-}
-
-// Walks the tiles of a workgroup (all wave-uniform).  XCD x owns row blocks [x * m_per, (x+1) * m_per) and all column tiles.  Its tiles
-// form ONE list in block order -- gm x gn blocks of tiles, column chunks (nbn of them) fastest, inside a block the row fastest; ragged
-// blocks at the edges are packed densely -- and its wgx workgroups take list entries lid, lid + wgx, lid + 2 wgx ...: the workgroups an XCD
-// runs at the same time share about gm activation row blocks and gn weight panels in its L2 (with one row of 32 column tiles in flight the
-// 6.5 MB weight of the level-1 GEGLU projection streamed through the 4 MB L2 once per row block), and a round leaves no CU idle unless
-// the list ends.  (Rounds 4-5 walked whole blocks, one per round: a block shape that did not divide the XCD's tile grid idled workgroups
-// in EVERY round -- 27 of 32 on the 8 x 8 level QKV, 8 rounds for 6.75 rounds of work.)
-struct PwTileIter {
-    int r, tm, tn;
-    bool valid;
-    __device__ __forceinline__ void set(const LinPWParams& p, int r0, int lid, int m_lo, int m_cnt) {
-        r = r0;
-        const int i = r0 * p.wgx + lid;
-        valid = i < m_cnt * p.tiles_n;
-        if (valid) {
-            const int strip = p.gm * p.tiles_n;                          // tiles of a full strip of gm row blocks
-            const int sm = min(i / strip, (m_cnt + p.gm - 1) / p.gm - 1);
-            const int hm = min(p.gm, m_cnt - sm * p.gm);                 // rows of this strip (the last one may be lower)
-            const int is = i - sm * strip;
-            const int cn = is / (hm * p.gn);                             // column chunk (the last one may be narrower)
-            const int j = is - cn * hm * p.gn;
-            const int ln = j / hm;
-            tm = m_lo + sm * p.gm + (j - ln * hm);
-            tn = cn * p.gn + ln;
-        }
-    }
-};
-
-// one 32 x 32 block (GEGLU: one value / gate pair) of the finished tile -> two packed 16-byte chunks.  c[k]: the lane's 16 columns
-// in output order (registers 0..7 = columns 8h .. 8h+7, 8..15 = 16 + 8h .. of the block).  RES: residual chunks of the same columns
-template <typename T, bool RES>
-__device__ __forceinline__ void pw_pack(const float (&c)[16], float scale, const u32x4 (&res)[2], u32x4 (&out)[2]) {
-#pragma unroll
-    for (int g = 0; g < 2; ++g) {
-        Chunk<T> oc;
-        if constexpr (RES) {
-            Chunk<T> rc;
-            rc.raw = res[g];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) oc.set(e, c[8 * g + e] * scale + rc.get(e));
-        } else {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) oc.set(e, c[8 * g + e] * scale);
-        }
-        out[g] = oc.raw;
-    }
+    return (m < M && col < n_dst) ? ((unsigned)m * (unsigned)ld + (unsigned)col) * 2u : kBufOob;
 }
 
 template <typename T, int TN, int EPI, bool RES, bool NT>
 __global__ __launch_bounds__(512) void linear_pw_kernel(const LinPWParams p) {
     using G = PwGeo<TN>;
-    using Frag = typename PwMma<T>::Frag;
+    using Frag = typename LinMma<T>::Frag;
     constexpr bool GEGLU = EPI == MVLDM_EPI_GEGLU;
     static_assert(!GEGLU || TN % 2 == 0, "GEGLU pairs value / gate blocks inside a wave tile");
     static_assert(!(GEGLU && RES), "no caller");
@@ -350,11 +259,11 @@ __global__ __launch_bounds__(512) void linear_pw_kernel(const LinPWParams p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 1, wn = wave & 1;        // 4 x 2 waves of 64 rows x 32*TN columns
     const int hi = lane >> 5, l31 = lane & 31;
-    const int prm = pw_perm(l31);
+    const int prm = lin_perm(l31);
 
     const int xcd = blockIdx.x & 7, lid = blockIdx.x >> 3;
     const int m_lo = xcd * p.m_per, m_cnt = min(p.tiles_m, m_lo + p.m_per) - m_lo;
-    PwTileIter cur, nxt, iss;                    // compute side, the tile after it, issue side (newest ring step in flight)
+    LinTileIter<LinPWParams> cur, nxt, iss;       // compute side, the tile after it, issue side (newest ring step in flight)
     cur.set(p, 0, lid, m_lo, m_cnt);
     if (!cur.valid) return;
     nxt.set(p, cur.r + 1, lid, m_lo, m_cnt);
@@ -385,8 +294,8 @@ __global__ __launch_bounds__(512) void linear_pw_kernel(const LinPWParams p) {
             pw_issue_a<TN>(p, smem, g, wave, lane, g, ad);
             pw_issue_w<TN>(p, smem, g, wave, g, ad);
         }
-        const u32x4 b = pw_load_bias<TN>(p, GEGLU, true, cur.tn, tid);
-        __builtin_amdgcn_s_waitcnt(pw_wait(0));
+        const u32x4 b = lin_load_bias<G::BN>(p, GEGLU, true, cur.tn, tid);
+        __builtin_amdgcn_s_waitcnt(waitcnt_vmcnt(0));
         if (4 * tid < G::BN) *reinterpret_cast<u32x4*>(smem + G::SLAB + tid * 16) = b;
     }
     int rs = 0;                                  // ring slot the current step reads
@@ -406,15 +315,15 @@ __global__ __launch_bounds__(512) void linear_pw_kernel(const LinPWParams p) {
         const char* st_ = smem + (nslot_) * G::STAGE;                                                             \
         const int ao_ = a_off ^ ((nkk_) << 5), wo_ = w_off ^ ((nkk_) << 5);                                       \
         if (NEXT_) {                                                                                              \
-            na_[0] = pw_frag<T>(st_ + ao_);                                                                       \
-            na_[1] = pw_frag<T>(st_ + ao_ + 4096);                                                                \
-            nw_[0] = pw_frag<T>(st_ + wo_);                                                                       \
+            na_[0] = lin_frag<T>(st_ + ao_);                                                                      \
+            na_[1] = lin_frag<T>(st_ + ao_ + 4096);                                                               \
+            nw_[0] = lin_frag<T>(st_ + wo_);                                                                      \
         }                                                                                                         \
         _Pragma("unroll") for (int j = 0; j < TN; ++j) {                                                          \
             __builtin_amdgcn_sched_barrier(0);                                                                    \
-            acc[0][j] = PwMma<T>::mma(cw_[j], ca_[0], acc[0][j]);                                                 \
-            acc[1][j] = PwMma<T>::mma(cw_[j], ca_[1], acc[1][j]);                                                 \
-            if (NEXT_ && j + 1 < TN) nw_[j + 1] = pw_frag<T>(st_ + wo_ + (j + 1) * 4096);                         \
+            acc[0][j] = LinMma<T>::mma(cw_[j], ca_[0], acc[0][j]);                                                \
+            acc[1][j] = LinMma<T>::mma(cw_[j], ca_[1], acc[1][j]);                                                \
+            if (NEXT_ && j + 1 < TN) nw_[j + 1] = lin_frag<T>(st_ + wo_ + (j + 1) * 4096);                        \
             if ((MODE_) == 1 && j == 0) {                                                                         \
                 if (++ks_i == kT) {                                                                               \
                     ks_i = 0;                                                                                     \
@@ -469,9 +378,9 @@ __global__ __launch_bounds__(512) void linear_pw_kernel(const LinPWParams p) {
     const bool sp = p.spread && !p.touch && kT >= 4;
     Frag fa0[2], fw0[TN], fa1[2], fw1[TN];
     constexpr int kWaitLds = 0xC07F;                             // lgkmcnt(0) only
-    constexpr int kWaitFirst = pw_wait(4 * NOUT) & ~0x0F00;      // step 1 of the tile has landed: everything but the previous epilogue's 4 * NOUT stores
-    constexpr int kWaitStepT = pw_wait(0) & ~0x0F00;             // vmcnt(0) lgkmcnt(0): step g+1 has landed (and every older store)
-    constexpr int kWaitStep1 = pw_wait(1) & ~0x0F00;             // ... vmcnt(1): the step's own touch (younger) may be in flight
+    constexpr int kWaitFirst = waitcnt_vmcnt(4 * NOUT) & ~0x0F00;      // step 1 of the tile has landed: everything but the previous epilogue's 4 * NOUT stores
+    constexpr int kWaitStepT = waitcnt_vmcnt(0) & ~0x0F00;             // vmcnt(0) lgkmcnt(0): step g+1 has landed (and every older store)
+    constexpr int kWaitStep1 = waitcnt_vmcnt(1) & ~0x0F00;             // ... vmcnt(1): the step's own touch (younger) may be in flight
     constexpr int PW_TOUCH_AHEAD = 4;                            // the ring requests step g+2 in step g: the touch runs two steps ahead of it
 
     for (; cur.valid; cur = nxt, nxt.set(p, nxt.r + 1, lid, m_lo, m_cnt)) {
@@ -492,9 +401,9 @@ __global__ __launch_bounds__(512) void linear_pw_kernel(const LinPWParams p) {
         {
             const char* st0 = smem + rs * G::STAGE;
 #pragma unroll
-            for (int i = 0; i < 2; ++i) fa0[i] = pw_frag<T>(st0 + a_off + i * 4096);
+            for (int i = 0; i < 2; ++i) fa0[i] = lin_frag<T>(st0 + a_off + i * 4096);
 #pragma unroll
-            for (int j = 0; j < TN; ++j) fw0[j] = pw_frag<T>(st0 + w_off + j * 4096);
+            for (int j = 0; j < TN; ++j) fw0[j] = lin_frag<T>(st0 + w_off + j * 4096);
         }
         { const int ks_t = 0; PW_STEP(false, kWaitFirst, false, sp) }
         // (the middle steps carry one touch each: issued at the top of the step, i.e. younger than the pieces the step waits for)
@@ -519,8 +428,8 @@ __global__ __launch_bounds__(512) void linear_pw_kernel(const LinPWParams p) {
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
                 const int m = cur.tm * PW_BM + wm * 64 + i * 32 + l31;
-                row_dst[i] = m < p.M ? (unsigned)m * (unsigned)p.dst_ld * 2u : kPwRowNone;
-                row_res[i] = m < p.M ? (unsigned)m * (unsigned)p.n_dst * 2u : kPwRowNone;
+                row_dst[i] = m < p.M ? (unsigned)m * (unsigned)p.dst_ld * 2u : kLinRowNone;
+                row_res[i] = m < p.M ? (unsigned)m * (unsigned)p.n_dst * 2u : kLinRowNone;
             }
             u32x4 out[2][NOUT][2];
             if constexpr (RES) {
@@ -537,9 +446,9 @@ __global__ __launch_bounds__(512) void linear_pw_kernel(const LinPWParams p) {
 #define PW_RES_OFFS(b_)                                                                                                         \
         const bool pair_ = (((b_) % TN) | 1) < TN;                                                                              \
         const unsigned o0_ = pair_ ? pw_line_off(p.M, cur.tm, wm, (b_) / TN, (b_) % TN, 0, l31, hi, col0, p.n_dst, p.n_dst)     \
-                                   : pw_off(row_res[(b_) / TN], col0 + 32 * ((b_) % TN) + 8 * hi, p.n_dst);                     \
+                                   : lin_off(row_res[(b_) / TN], col0 + 32 * ((b_) % TN) + 8 * hi, p.n_dst);                    \
         const unsigned o1_ = pair_ ? pw_line_off(p.M, cur.tm, wm, (b_) / TN, (b_) % TN, 1, l31, hi, col0, p.n_dst, p.n_dst)     \
-                                   : pw_off(row_res[(b_) / TN], col0 + 32 * ((b_) % TN) + 16 + 8 * hi, p.n_dst);
+                                   : lin_off(row_res[(b_) / TN], col0 + 32 * ((b_) % TN) + 16 + 8 * hi, p.n_dst);
 #define PW_RES_ISSUE(b_)                                                                                                        \
     if constexpr ((b_) < NB) {                                                                                                  \
         PW_RES_OFFS(b_)                                                                                                         \
@@ -560,16 +469,16 @@ __global__ __launch_bounds__(512) void linear_pw_kernel(const LinPWParams p) {
         if constexpr (!paired_) {                                                                                               \
             float c_[16];                                                                                                       \
             _Pragma("unroll") for (int k = 0; k < 16; ++k) c_[k] = acc[i_][j_][k];                                              \
-            pw_pack<T, true>(c_, p.out_scale, r[(b_) < NB ? (b_) : 0], out[i_][j_]);                                            \
+            lin_pack<T, true>(c_, p.out_scale, r[(b_) < NB ? (b_) : 0], out[i_][j_]);                                           \
         } else if constexpr ((j_ & 1) == 1) {                                                                                   \
             /* the pair (b - 1, b) has landed: residual -> accumulator layout, both blocks packed, outputs -> line layout */    \
             constexpr int bp_ = (b_) > 0 ? (b_) - 1 : 0;                                                                        \
             pw_quad_transpose(r[bp_][0], r[bp_][1], r[(b_) < NB ? (b_) : 0][0], r[(b_) < NB ? (b_) : 0][1], q_odd, q_upper);    \
             float c_[16];                                                                                                       \
             _Pragma("unroll") for (int k = 0; k < 16; ++k) c_[k] = acc[i_][j_ - 1][k];                                          \
-            pw_pack<T, true>(c_, p.out_scale, r[bp_], out[i_][j_ - 1]);                                                         \
+            lin_pack<T, true>(c_, p.out_scale, r[bp_], out[i_][j_ - 1]);                                                        \
             _Pragma("unroll") for (int k = 0; k < 16; ++k) c_[k] = acc[i_][j_][k];                                              \
-            pw_pack<T, true>(c_, p.out_scale, r[(b_) < NB ? (b_) : 0], out[i_][j_]);                                            \
+            lin_pack<T, true>(c_, p.out_scale, r[(b_) < NB ? (b_) : 0], out[i_][j_]);                                           \
             pw_quad_transpose(out[i_][j_ - 1][0], out[i_][j_ - 1][1], out[i_][j_][0], out[i_][j_][1], q_odd, q_upper);          \
         }                                                                                                                       \
         PW_RES_ISSUE((b_) + PW_D)                                                                                               \
@@ -599,7 +508,7 @@ __global__ __launch_bounds__(512) void linear_pw_kernel(const LinPWParams p) {
                             for (int k = 0; k < 16; ++k) c[k] = acc[i][j][k];
                         }
                         const u32x4 none[2] = {u32x4{0u, 0u, 0u, 0u}, u32x4{0u, 0u, 0u, 0u}};
-                        pw_pack<T, false>(c, p.out_scale, none, out[i][j]);
+                        lin_pack<T, false>(c, p.out_scale, none, out[i][j]);
                         if ((j & 1) == 1) pw_quad_transpose(out[i][j - 1][0], out[i][j - 1][1], out[i][j][0], out[i][j][1], q_odd, q_upper);
                     }
             }
@@ -612,8 +521,8 @@ __global__ __launch_bounds__(512) void linear_pw_kernel(const LinPWParams p) {
                         pw_store2<NT>(rdst, out[i][j][0], pw_line_off(p.M, cur.tm, wm, i, j, 0, l31, hi, col0, p.dst_ld, p.n_dst), out[i][j][1],
                                       pw_line_off(p.M, cur.tm, wm, i, j, 1, l31, hi, col0, p.dst_ld, p.n_dst));
                     else
-                        pw_store2<NT>(rdst, out[i][j][0], pw_off(row_dst[i], col0 + 32 * j + 8 * hi, p.n_dst), out[i][j][1],
-                                      pw_off(row_dst[i], col0 + 32 * j + 16 + 8 * hi, p.n_dst));
+                        pw_store2<NT>(rdst, out[i][j][0], lin_off(row_dst[i], col0 + 32 * j + 8 * hi, p.n_dst), out[i][j][1],
+                                      lin_off(row_dst[i], col0 + 32 * j + 16 + 8 * hi, p.n_dst));
         }
     }
     // (the ring pieces issued past the last tile are out of range: zeros into slots nobody reads; nothing to drain but the stores,
@@ -658,27 +567,15 @@ template <typename T, int TN, int EPI, bool RES> static int linear_pw_launch(con
 int linear_pw_run(const mvldm_igemm_desc& d, hipStream_t s) {
     MVLDM_REQUIRE(linear_pw_applicable(d), "igemm: tile 13 (persistent wide Linear) does not apply to this problem");
     LinPWParams p;
-    p.a = d.src0; p.a1 = d.src1; p.w = d.weight; p.bias = d.bias; p.residual = d.residual; p.dst = d.dst;
-    p.M = d.n_img * d.h_out * d.w_out; p.K = d.c0 + d.c1; p.c0 = d.c0; p.c1 = d.c1; p.kt0 = d.c0 / 64; p.n_out = d.n_out; p.n_pad = d.n_pad;
-    p.n_dst = d.epilogue == MVLDM_EPI_GEGLU ? d.n_out / 2 : d.n_out;
-    p.dst_ld = d.dst_ld > 0 ? d.dst_ld : p.n_dst;
-    p.k_steps = p.K / 64; p.out_scale = d.out_scale;
+    lin_fill_params2(p, d, kPwFake);
+    p.k_steps = p.K / 64;
     // 256 x 320 when the packed width is a multiple of 320 (every channel count of this UNet), else 256 x 256; GEGLU pairs need an even
     // number of column blocks per wave.  Round 6: ... unless 256 x 256 tiles need clearly fewer MFMA cycles per CU -- a launch lasts
     // rounds x tile area, rounds = ceil(tiles of the XCD / its 32 CUs): the 8 x 8 level's N = 1280 Linears (36 864 rows: 72 tiles of
     // 256 x 320 per XCD = 2.25 rounds, run as 3) take 3 rounds of the SMALLER tile instead (90 tiles = 2.8 rounds), -20 %.
     const bool geglu = d.epilogue == MVLDM_EPI_GEGLU;
     static const int kForceTn = knob_int("MVLDM_PW_TN", 0);
-    static int n_cu = 0;
-    if (!n_cu) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-            n_cu = prop.multiProcessorCount;
-        else
-            n_cu = 256;
-    }
-    const int cu_x = std::max(1, n_cu / 8);
+    const int cu_x = std::max(1, cu_count() / 8);
     p.tiles_m = (p.M + PW_BM - 1) / PW_BM;
     p.m_per = (p.tiles_m + 7) / 8;
     auto launch_cost = [&](int tnb) {      // MFMA time of the busiest CU, in 256 x 64-column units
@@ -691,10 +588,6 @@ int linear_pw_run(const mvldm_igemm_desc& d, hipStream_t s) {
     if (kForceTn == 4 || (kForceTn == 5 && !geglu)) tn_blocks = kForceTn;
     const int bn = 64 * tn_blocks;
     p.tiles_n = (d.n_pad + bn - 1) / bn;
-    p.a_bytes = (unsigned)((double)p.M * p.c0 * 2.0); p.a1_bytes = (unsigned)((double)p.M * p.c1 * 2.0); p.w_bytes = (unsigned)((double)d.n_pad * d.k_pad * 2.0);
-    p.bias_bytes = d.bias ? (unsigned)d.n_out * 4u : 0u;
-    p.res_bytes = d.residual ? (unsigned)((double)p.M * p.n_dst * 2.0) : 0u;
-    p.dst_bytes = (unsigned)((double)p.M * p.dst_ld * 2.0);
     // write-back stores unless forced (header): MVLDM_STREAM_STORES=1 is the A/B knob
     static const int kNt = knob_int("MVLDM_STREAM_STORES", 0);
     p.nt_store = kNt == 1;
@@ -709,22 +602,9 @@ int linear_pw_run(const mvldm_igemm_desc& d, hipStream_t s) {
         p.trace_stagger = getenv("MVLDM_PW_STAGGER") ? atoi(getenv("MVLDM_PW_STAGGER")) : 0;
     }
 #endif
-    if (kPwFake & 1) p.a_bytes = p.a1_bytes = 0;
-    if (kPwFake & 2) p.w_bytes = 0;
-    if (kPwFake & 4) p.dst_bytes = 0;
-    // An XCD's workgroups (one per CU, fewer when it has fewer tiles) walk its tile list, which is ordered in gm x gn blocks (PwTileIter):
-    // the block shape of about one round's tiles that moves the fewest bytes into the XCD's L2 per round -- gm activation row blocks + gn
-    // weight panels
-    const double a_t = 256.0 * p.K * 2.0, w_t = (double)bn * p.K * 2.0;
+    // An XCD's workgroups (one per CU, fewer when it has fewer tiles) walk its tile list, which is ordered in gm x gn blocks (LinTileIter)
     p.wgx = std::min(cu_x, p.m_per * p.tiles_n);
-    double best_cost = 1e300;
-    p.gm = p.gn = 1;
-    for (int gm = 1; gm <= std::min(p.wgx, p.m_per); ++gm) {
-        const int gn = std::max(1, std::min(p.wgx / gm, p.tiles_n));
-        // (cost per tile of the block: a block smaller than a round shares less)
-        const double cost = (gm * a_t + gn * w_t) / (gm * gn);
-        if (cost < best_cost) { best_cost = cost; p.gm = gm; p.gn = gn; }
-    }
+    lin_block_shape(p, 256.0 * p.K * 2.0, (double)bn * p.K * 2.0);
     static const int kForceGm = knob_int("MVLDM_PW_GM", 0);   // tuning: force the block shape
     if (kForceGm > 0) { p.gm = std::min(std::min(kForceGm, p.wgx), p.m_per); p.gn = std::max(1, std::min(p.wgx / p.gm, p.tiles_n)); }
     p.nbn = (p.tiles_n + p.gn - 1) / p.gn;

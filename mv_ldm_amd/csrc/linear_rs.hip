@@ -19,10 +19,9 @@
 //   * every VMEM instruction is a compiler builtin (no LDS-DMA, no inline-asm loads): hipcc's own wait-count pass sees one in-order
 //     queue and emits the counted vmcnt in front of each ds_write -- nothing is counted by hand here.
 // K-steps per tile must be even (the two register sets / LDS slots alternate with the step parity, the loop is unrolled by two).
-#include <algorithm>
 #include <cstdlib>
 
-#include "common.h"
+#include "linear_common.h"
 
 namespace mvldm {
 
@@ -41,31 +40,12 @@ static const int kRsFake = knob_int("MVLDM_RS_FAKE", 0);   // wrong results by d
 static constexpr int kRsFake = 0;
 #endif
 
-constexpr unsigned kRsOob = 0xFFFFFFF0u;
-constexpr unsigned kRsRowNone = 0xFFFFFFFFu;
 constexpr int RS_BM = 256, RS_BN = 256, RS_NW = 4;
 constexpr int RS_A_SLOT = RS_BM * 128, RS_W_SLOT = RS_BN * 128, RS_STAGE = RS_A_SLOT + RS_W_SLOT;
 constexpr int RS_RING = 2 * RS_STAGE;                 // 128 KB
 constexpr int RS_SLAB = RS_RING;                      // 2 x 1 KB: bias of a tile's 256 packed columns, double-buffered over tiles
 constexpr int RS_SMEM = RS_RING + 2048;
 constexpr int RS_PIECES = 8;                          // 1 KiB pieces (8 rows of 128 bytes) per wave, operand and step
-
-template <typename T> struct RsMma;
-template <> struct RsMma<bf16_t> {
-    using Frag = bf16x8;
-    static __device__ __forceinline__ f32x16 mma(Frag a, Frag b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
-};
-template <> struct RsMma<f16_t> {
-    using Frag = f16x8;
-    static __device__ __forceinline__ f32x16 mma(Frag a, Frag b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
-};
-
-// MFMA M index mu (= lane & 31 of the W-fragment read) -> column of the 32-column block it is fed from (linear_pw.hip: registers 0..7 /
-// 8..15 of a lane become 8 + 8 CONSECUTIVE output columns; each 16-lane group reads the same set of rows as the identity)
-__device__ __forceinline__ int rs_perm(int mu) {
-    const int a = mu >> 3, h = (mu >> 2) & 1, e = mu & 3;
-    return 16 * (a >> 1) + 8 * h + 4 * (a & 1) + e;
-}
 
 // Source addressing of a wave's pieces.  Piece `it` of a wave covers tile rows (wave + 4 it) * 8 .. + 7; a lane fetches chunk (lane & 7) of
 // row (lane >> 3) of the piece and writes it to the swizzled LDS position -- (row >> 1) & 7 does not depend on `it`, so ONE per-lane
@@ -100,13 +80,13 @@ __device__ __forceinline__ void rs_load_a1(const LinRSParams& p, int ks, const R
     const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(abase), 0, abytes, 0x00020000);
     const int soff = (second ? ks - p.kt0 : ks) * 128;
     const unsigned v = second ? ad.a1 : ad.a0;
-    const unsigned off = (ad.valid && ad.m_lane + 32 * it < p.M) ? v : kRsOob;
+    const unsigned off = (ad.valid && ad.m_lane + 32 * it < p.M) ? v : kBufOob;
     r[it] = __builtin_amdgcn_raw_buffer_load_b128(ra, off, soff + it * 64 * c, 0);
 }
 __device__ __forceinline__ void rs_load_w1(const LinRSParams& p, int ks, const RsAddr& ad, u32x4 (&r)[RS_PIECES], int it) {
     const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.w), 0, p.w_bytes, 0x00020000);
     // (n_pad is a multiple of 64, a piece's 8 rows start at a multiple of 8 inside a 32-row group: inside the packed weight or outside as a whole)
-    const unsigned off = (ad.valid && ad.n0 + 32 * it < p.n_pad) ? ad.w : kRsOob;
+    const unsigned off = (ad.valid && ad.n0 + 32 * it < p.n_pad) ? ad.w : kBufOob;
     r[it] = __builtin_amdgcn_raw_buffer_load_b128(rw, off, ks * 128 + it * 64 * p.K, 0);
 }
 // the same piece -> its (swizzled) place in an operand's half of a ring slot
@@ -123,84 +103,15 @@ template <int J2> __device__ __forceinline__ void rs_write2(char* half_slot, int
     rs_write1(half_slot, wr_off, r, J2); rs_write1(half_slot, wr_off, r, J2 + 1);
 }
 
-// byte offset (into the torch-layout bias) of packed columns 4t .. 4t+3 of tile column tn, out of range past the tile / the layer
-__device__ __forceinline__ u32x4 rs_load_bias(const LinRSParams& p, bool geglu, bool valid, int tn, int t) {
-    const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.bias), 0, p.bias_bytes, 0x00020000);
-    const int pc = tn * RS_BN + 4 * t;                          // packed column
-    int oc = pc;                                                // column of the torch-layout bias
-    if (geglu) {
-        const int blk = pc >> 5, w = pc & 31;
-        oc = ((blk & 1) ? p.n_dst : 0) + (blk >> 1) * 32 + w;
-    }
-    const unsigned off = (valid && 4 * t < RS_BN && pc < p.n_out) ? (unsigned)oc * 4u : kRsOob;
-    return __builtin_amdgcn_raw_buffer_load_b128(rb, off, 0, 0);
-}
-
-__device__ __forceinline__ u32x4 rs_load_res(const LinRSParams& p, unsigned off) {
-    const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.residual), 0, p.res_bytes, 0x00020000);
-    return __builtin_amdgcn_raw_buffer_load_b128(rr, off, 0, 0);
-}
 // (write-back stores, not streaming ones: linear_pw.hip -- the L2 acknowledges a tile's store burst long before HBM has taken it)
 __device__ __forceinline__ void rs_store(const LinRSParams& p, const u32x4& v, unsigned off) {
     const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc(p.dst, 0, p.dst_bytes, 0x00020000);
     __builtin_amdgcn_raw_buffer_store_b128(v, rd, off, 0, 0);
 }
 
-template <typename T> __device__ __forceinline__ typename RsMma<T>::Frag rs_frag(const char* p) {
-    return *reinterpret_cast<const typename RsMma<T>::Frag*>(p);
-}
-
-__device__ __forceinline__ unsigned rs_off(unsigned row, int col, int n_dst) {
-    return (row != kRsRowNone && col < n_dst) ? row + (unsigned)col * 2u : kRsOob;
-}
-
-// Walks the tiles of a workgroup (all wave-uniform): linear_pw.hip's order.  XCD x owns row blocks [x * m_per, (x+1) * m_per) and all
-// column tiles; its tiles form one list in gm x gn block order (column chunks fastest, the row fastest inside a block, ragged edge
-// blocks packed densely) and its wgx workgroups take entries lid, lid + wgx, ...
-struct RsTileIter {
-    int r, tm, tn;
-    bool valid;
-    __device__ __forceinline__ void set(const LinRSParams& p, int r0, int lid, int m_lo, int m_cnt) {
-        r = r0;
-        const int i = r0 * p.wgx + lid;
-        valid = i < m_cnt * p.tiles_n;
-        if (valid) {
-            const int strip = p.gm * p.tiles_n;
-            const int sm = min(i / strip, (m_cnt + p.gm - 1) / p.gm - 1);
-            const int hm = min(p.gm, m_cnt - sm * p.gm);
-            const int is = i - sm * strip;
-            const int cn = is / (hm * p.gn);
-            const int j = is - cn * hm * p.gn;
-            const int ln = j / hm;
-            tm = m_lo + sm * p.gm + (j - ln * hm);
-            tn = cn * p.gn + ln;
-        }
-    }
-};
-
-// one 32 x 32 block (GEGLU: one value / gate pair) of the finished tile -> two packed 16-byte chunks.  c[k]: the lane's 16 columns
-// in output order (registers 0..7 = columns 8h .. 8h+7, 8..15 = 16 + 8h .. of the block).  RES: residual chunks of the same columns
-template <typename T, bool RES>
-__device__ __forceinline__ void rs_pack(const float (&c)[16], float scale, const u32x4 (&res)[2], u32x4 (&out)[2]) {
-#pragma unroll
-    for (int g = 0; g < 2; ++g) {
-        Chunk<T> oc;
-        if constexpr (RES) {
-            Chunk<T> rc;
-            rc.raw = res[g];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) oc.set(e, c[8 * g + e] * scale + rc.get(e));
-        } else {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) oc.set(e, c[8 * g + e] * scale);
-        }
-        out[g] = oc.raw;
-    }
-}
-
 template <typename T, int EPI, bool RES>
 __global__ __launch_bounds__(256) void linear_rs_kernel(const LinRSParams p) {
-    using M_ = RsMma<T>;
+    using M_ = LinMma<T>;
     using Frag = typename M_::Frag;
     constexpr bool GEGLU = EPI == MVLDM_EPI_GEGLU;
     static_assert(!(GEGLU && RES), "no caller");
@@ -210,11 +121,11 @@ __global__ __launch_bounds__(256) void linear_rs_kernel(const LinRSParams p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 1, wn = wave & 1;        // 2 x 2 waves of 128 rows x 128 columns
     const int hi = lane >> 5, l31 = lane & 31;
-    const int prm = rs_perm(l31);
+    const int prm = lin_perm(l31);
 
     const int xcd = blockIdx.x & 7, lid = blockIdx.x >> 3;
     const int m_lo = xcd * p.m_per, m_cnt = min(p.tiles_m, m_lo + p.m_per) - m_lo;
-    RsTileIter cur, nxt, nx2, iss;               // compute side, the two tiles after it, issue side (tile of the newest K-step in flight)
+    LinTileIter<LinRSParams> cur, nxt, nx2, iss;  // compute side, the two tiles after it, issue side (tile of the newest K-step in flight)
     cur.set(p, 0, lid, m_lo, m_cnt);
     if (!cur.valid) return;
     nxt.set(p, cur.r + 1, lid, m_lo, m_cnt);
@@ -246,8 +157,8 @@ __global__ __launch_bounds__(256) void linear_rs_kernel(const LinRSParams p) {
         rs_load_a2<0>(p, 0, ad, ra0); rs_load_a2<2>(p, 0, ad, ra0); rs_load_a2<4>(p, 0, ad, ra0); rs_load_a2<6>(p, 0, ad, ra0);
         rs_load_w2<0>(p, 0, ad, rw); rs_load_w2<2>(p, 0, ad, rw); rs_load_w2<4>(p, 0, ad, rw); rs_load_w2<6>(p, 0, ad, rw);
         rs_load_a2<0>(p, 1, ad, ra1); rs_load_a2<2>(p, 1, ad, ra1); rs_load_a2<4>(p, 1, ad, ra1); rs_load_a2<6>(p, 1, ad, ra1);
-        const u32x4 b = rs_load_bias(p, GEGLU, true, cur.tn, tid);
-        bn = rs_load_bias(p, GEGLU, nxt.valid, nxt.tn, tid);
+        const u32x4 b = lin_load_bias<RS_BN>(p, GEGLU, true, cur.tn, tid);
+        bn = lin_load_bias<RS_BN>(p, GEGLU, nxt.valid, nxt.tn, tid);
         rs_write2<0>(smem, wr_off, ra0); rs_write2<2>(smem, wr_off, ra0); rs_write2<4>(smem, wr_off, ra0); rs_write2<6>(smem, wr_off, ra0);
         rs_write2<0>(smem + RS_A_SLOT, wr_off, rw); rs_write2<2>(smem + RS_A_SLOT, wr_off, rw);
         rs_write2<4>(smem + RS_A_SLOT, wr_off, rw); rs_write2<6>(smem + RS_A_SLOT, wr_off, rw);
@@ -260,8 +171,8 @@ __global__ __launch_bounds__(256) void linear_rs_kernel(const LinRSParams p) {
         asm volatile("" ::: "memory");
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            fa0[j] = rs_frag<T>(smem + a_off + j * 4096);
-            fw0[j] = rs_frag<T>(smem + w_off + j * 4096);
+            fa0[j] = lin_frag<T>(smem + a_off + j * 4096);
+            fw0[j] = lin_frag<T>(smem + w_off + j * 4096);
         }
     }
 
@@ -280,8 +191,8 @@ __global__ __launch_bounds__(256) void linear_rs_kernel(const LinRSParams p) {
         const int ao_ = a_off ^ ((nkk_) << 5), wo_ = w_off ^ ((nkk_) << 5);                                       \
         _Pragma("unroll") for (int q = 0; q < 16; ++q) {                                                          \
             acc[q & 3][q >> 2] = M_::mma(cw_[q >> 2], ca_[q & 3], (Z_) ? kZero : acc[q & 3][q >> 2]);             \
-            if (q < 4) na_[q] = rs_frag<T>(st_ + ao_ + q * 4096);                                                 \
-            else if (q < 8) nw_[q - 4] = rs_frag<T>(st_ + wo_ + (q - 4) * 4096);                                  \
+            if (q < 4) na_[q] = lin_frag<T>(st_ + ao_ + q * 4096);                                                \
+            else if (q < 8) nw_[q - 4] = lin_frag<T>(st_ + wo_ + (q - 4) * 4096);                                 \
             OPS_                                                                                                  \
             __builtin_amdgcn_sched_barrier(0);                                                                    \
         }                                                                                                         \
@@ -334,21 +245,21 @@ __global__ __launch_bounds__(256) void linear_rs_kernel(const LinRSParams p) {
         // ---- epilogue: straight from the accumulators (a lane holds 8 + 8 consecutive columns of its row per 32 x 32 block).  The loads of
         //      the next tile's steps 1 and 2 are in flight, its step 0 is in the ring, its kk = 0 fragments in registers ----
         {
-            bn = rs_load_bias(p, GEGLU, nx2.valid, nx2.tn, tid);      // bias of the tile after the next (header of `bn`)
+            bn = lin_load_bias<RS_BN>(p, GEGLU, nx2.valid, nx2.tn, tid);      // bias of the tile after the next (header of `bn`)
             const int col0 = GEGLU ? (cur.tn * RS_BN + wn * 128) >> 1 : cur.tn * RS_BN + wn * 128;
             const float* slab = reinterpret_cast<const float*>(smem + RS_SLAB + par * 1024) + wn * 128 + 8 * hi;
             par ^= 1;
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int m = cur.tm * RS_BM + wm * 128 + i * 32 + l31;
-                const unsigned row_dst = m < p.M ? (unsigned)m * (unsigned)p.dst_ld * 2u : kRsRowNone;
-                const unsigned row_res = m < p.M ? (unsigned)m * (unsigned)p.n_dst * 2u : kRsRowNone;
+                const unsigned row_dst = m < p.M ? (unsigned)m * (unsigned)p.dst_ld * 2u : kLinRowNone;
+                const unsigned row_res = m < p.M ? (unsigned)m * (unsigned)p.n_dst * 2u : kLinRowNone;
                 u32x4 res[NOUT][2];
                 if constexpr (RES) {
 #pragma unroll
                     for (int j = 0; j < NOUT; ++j) {
-                        res[j][0] = rs_load_res(p, rs_off(row_res, col0 + 32 * j + 8 * hi, p.n_dst));
-                        res[j][1] = rs_load_res(p, rs_off(row_res, col0 + 32 * j + 16 + 8 * hi, p.n_dst));
+                        res[j][0] = lin_load_res(p.residual, p.res_bytes, lin_off(row_res, col0 + 32 * j + 8 * hi, p.n_dst));
+                        res[j][1] = lin_load_res(p.residual, p.res_bytes, lin_off(row_res, col0 + 32 * j + 16 + 8 * hi, p.n_dst));
                     }
                 }
 #pragma unroll
@@ -374,13 +285,13 @@ __global__ __launch_bounds__(256) void linear_rs_kernel(const LinRSParams p) {
                     }
                     u32x4 out[2];
                     if constexpr (RES) {
-                        rs_pack<T, true>(c, p.out_scale, res[j], out);
+                        lin_pack<T, true>(c, p.out_scale, res[j], out);
                     } else {
                         const u32x4 none[2] = {u32x4{0u, 0u, 0u, 0u}, u32x4{0u, 0u, 0u, 0u}};
-                        rs_pack<T, false>(c, p.out_scale, none, out);
+                        lin_pack<T, false>(c, p.out_scale, none, out);
                     }
-                    rs_store(p, out[0], rs_off(row_dst, col0 + 32 * j + 8 * hi, p.n_dst));
-                    rs_store(p, out[1], rs_off(row_dst, col0 + 32 * j + 16 + 8 * hi, p.n_dst));
+                    rs_store(p, out[0], lin_off(row_dst, col0 + 32 * j + 8 * hi, p.n_dst));
+                    rs_store(p, out[1], lin_off(row_dst, col0 + 32 * j + 16 + 8 * hi, p.n_dst));
                     __builtin_amdgcn_sched_barrier(0);      // (one block at a time: the in-flight register sets leave the epilogue ~60 VGPRs)
                 }
             }
@@ -418,42 +329,18 @@ template <typename T, int EPI, bool RES> static int linear_rs_launch(const LinRS
 int linear_rs_run(const mvldm_igemm_desc& d, hipStream_t s) {
     MVLDM_REQUIRE(linear_rs_applicable(d), "igemm: tile 19 (register-staged persistent Linear) does not apply to this problem");
     LinRSParams p;
-    p.a = d.src0; p.a1 = d.src1; p.w = d.weight; p.bias = d.bias; p.residual = d.residual; p.dst = d.dst;
-    p.M = d.n_img * d.h_out * d.w_out; p.K = d.c0 + d.c1; p.c0 = d.c0; p.c1 = d.c1; p.kt0 = d.c0 / 64; p.n_out = d.n_out; p.n_pad = d.n_pad;
-    p.n_dst = d.epilogue == MVLDM_EPI_GEGLU ? d.n_out / 2 : d.n_out;
-    p.dst_ld = d.dst_ld > 0 ? d.dst_ld : p.n_dst;
-    p.k_steps = p.K / 64; p.out_scale = d.out_scale;
+    lin_fill_params2(p, d, kRsFake);
+    if (kRsFake & 8) p.res_bytes = 0;
+    p.k_steps = p.K / 64;
     const bool geglu = d.epilogue == MVLDM_EPI_GEGLU;
     p.tiles_m = (p.M + RS_BM - 1) / RS_BM; p.tiles_n = (d.n_pad + RS_BN - 1) / RS_BN;
     p.m_per = (p.tiles_m + 7) / 8;
-    p.a_bytes = (unsigned)((double)p.M * p.c0 * 2.0); p.a1_bytes = (unsigned)((double)p.M * p.c1 * 2.0); p.w_bytes = (unsigned)((double)d.n_pad * d.k_pad * 2.0);
-    p.bias_bytes = d.bias ? (unsigned)d.n_out * 4u : 0u;
-    p.res_bytes = d.residual ? (unsigned)((double)p.M * p.n_dst * 2.0) : 0u;
-    p.dst_bytes = (unsigned)((double)p.M * p.dst_ld * 2.0);
-    if (kRsFake & 1) p.a_bytes = p.a1_bytes = 0;
-    if (kRsFake & 2) p.w_bytes = 0;
-    if (kRsFake & 4) p.dst_bytes = 0;
-    if (kRsFake & 8) p.res_bytes = 0;
-    static int n_cu = 0;
-    if (!n_cu) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-            n_cu = prop.multiProcessorCount;
-        else
-            n_cu = 256;
-    }
     // An XCD's workgroups (one per CU, fewer when it has fewer tiles) walk its tile list, ordered in gm x gn blocks of about one round's
-    // tiles: the block shape that moves the fewest bytes into the XCD's L2 per tile -- gm activation row blocks + gn weight panels
-    const int cu_x = std::max(1, n_cu / 8);
+    // tiles (a row block and a weight panel are the same 256 x K bytes here: the cost is 1 / gm + 1 / gn in those units)
+    const int cu_x = std::max(1, cu_count() / 8);
     p.wgx = std::min(cu_x, p.m_per * p.tiles_n);
-    double best_cost = 1e300;
-    p.gm = p.gn = 1;
-    for (int gm = 1; gm <= std::min(p.wgx, p.m_per); ++gm) {
-        const int gn = std::max(1, std::min(p.wgx / gm, p.tiles_n));
-        const double cost = 1.0 / gn + 1.0 / gm;      // (a row block and a weight panel are the same 256 x K bytes here)
-        if (cost < best_cost) { best_cost = cost; p.gm = gm; p.gn = gn; }
-    }
+    const double t_bytes = 256.0 * p.K * 2.0;
+    lin_block_shape(p, t_bytes, t_bytes);
     p.nbn = (p.tiles_n + p.gn - 1) / p.gn;
     const int grid = 8 * p.wgx;
     const bool res = d.residual != nullptr;

@@ -17,10 +17,9 @@
 // never held back by a load wait (VMEM returns in order per wave: see the loader's comment in the kernel).
 // GEGLU: a wave's 32 weight rows are 16 value + 16 gate columns (the packed weight alternates [32 value | 32 gate]); both halves use
 // the same permutation, so a lane holds value and gate of its 8 columns: one 16-byte store per lane and block.
-#include <algorithm>
 #include <cstdlib>
 
-#include "common.h"
+#include "linear_common.h"
 
 namespace mvldm {
 
@@ -44,31 +43,11 @@ static constexpr int kWsFake = 0;
 #define WS_GELU(x) gelu_erf_16(x)
 #endif
 
-constexpr unsigned kWsOob = 0xFFFFFFF0u;
 constexpr int WS_K = 320, WS_KS = WS_K / 16, WS_NW = 10, WS_BN = 320, WS_ROWS = 64;
 constexpr int WS_SLOT = WS_ROWS * WS_K * 2;             // 40 KB: [5 k-blocks][64 rows][128 B]
 constexpr int WS_RING = 3 * WS_SLOT;
 constexpr int WS_SLAB = WS_RING;                        // bias of the workgroup's 320 packed columns (fp32)
 constexpr int WS_SMEM = WS_SLAB + 2048;
-
-constexpr int ws_wait(int n) { return (n & 15) | ((n >> 4) << 14) | 0x0F70; }   // s_waitcnt vmcnt(n) only (gfx9 encoding)
-
-template <typename T> struct WsMma;
-template <> struct WsMma<bf16_t> {
-    using Frag = bf16x8;
-    static __device__ __forceinline__ f32x16 mma(Frag a, Frag b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
-};
-template <> struct WsMma<f16_t> {
-    using Frag = f16x8;
-    static __device__ __forceinline__ f32x16 mma(Frag a, Frag b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
-};
-
-// MFMA M index mu -> column of the wave's 32-column block it is fed from: registers 0..7 / 8..15 of a lane = columns 8h .. 8h+7 /
-// 16 + 8h .. of its row (linear_pw.hip).  GEGLU: mu < 16 -> value column, mu >= 16 -> gate column of the same 16-column group
-__device__ __forceinline__ int ws_perm(int mu) {
-    const int a = mu >> 3, h = (mu >> 2) & 1, e = mu & 3;
-    return 16 * (a >> 1) + 8 * h + 4 * (a & 1) + e;
-}
 
 // (buffer descriptors only in free functions: an opaque __amdgpu_buffer_rsrc_t inside a lambda trips hipcc's host pass)
 // the LOADER wave (below) issues all 40 pieces of a slot: piece q = k-block q / 8, rows (q % 8) * 8 .. + 7; a lane fetches the 16-byte
@@ -81,13 +60,9 @@ __device__ __forceinline__ void ws_issue(const LinWSParams& p, char* slot_base, 
         const int lrow = (q & 7) * 8 + (lane >> 3);
         const unsigned chunk = (unsigned)((lane & 7) ^ ((lrow >> 1) & 7));
         const unsigned aoff = (unsigned)lrow * (WS_K * 2) + (unsigned)(q >> 3) * 128u + chunk * 16u;
-        const unsigned off = (live && row0 + lrow < p.M) ? aoff : kWsOob;
+        const unsigned off = (live && row0 + lrow < p.M) ? aoff : kBufOob;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (__attribute__((address_space(3))) void*)(slot_base + q * 1024), 16, off, soff, 0, 0);
     }
-}
-
-template <typename T> __device__ __forceinline__ typename WsMma<T>::Frag ws_frag(const char* p) {
-    return *reinterpret_cast<const typename WsMma<T>::Frag*>(p);
 }
 
 // every asm VMEM statement opens with `s_nop 4` (an SGPR of its descriptor may have just come back from a spill lane: linear_pw.hip) and
@@ -99,7 +74,7 @@ template <bool NT> __device__ __forceinline__ void ws_store(const u32x4& rdst, c
 
 template <typename T, int EPI, bool RES, bool NT>
 __global__ __launch_bounds__(704) void linear_ws_kernel(const LinWSParams p) {
-    using Frag = typename WsMma<T>::Frag;
+    using Frag = typename LinMma<T>::Frag;
     constexpr bool GEGLU = EPI == MVLDM_EPI_GEGLU;
     static_assert(!(GEGLU && RES), "no caller");
     constexpr int NST = GEGLU ? 1 : 2;             // 16-byte stores per lane and block
@@ -126,14 +101,14 @@ __global__ __launch_bounds__(704) void linear_ws_kernel(const LinWSParams p) {
     if (wave == WS_NW) {
         ws_issue(p, smem, g * WS_ROWS, lane, true);
         ws_issue(p, smem + WS_SLOT, (g + G) * WS_ROWS, lane, my_slots > 1);
-        __builtin_amdgcn_s_waitcnt(ws_wait(0));
+        __builtin_amdgcn_s_waitcnt(waitcnt_vmcnt(0));
         __builtin_amdgcn_s_barrier();                                  // (1) slots 0 and 1 are in LDS (and the bias slab, written by the others)
         int fill = 2;                                                  // ring slot of t + 2
         for (int t = 0; t < my_slots; ++t) {
             if (t > 0) __builtin_amdgcn_s_barrier();                   // top of slot t: slot t - 1 has been read by every compute wave
             ws_issue(p, smem + fill * WS_SLOT, (g + (t + 2) * G) * WS_ROWS, lane, t + 2 < my_slots);
             fill = fill == 2 ? 0 : fill + 1;
-            __builtin_amdgcn_s_waitcnt(ws_wait(WS_SLOT / 1024));       // slot t + 1 has landed: everything but the 40 newest pieces
+            __builtin_amdgcn_s_waitcnt(waitcnt_vmcnt(WS_SLOT / 1024));       // slot t + 1 has landed: everything but the 40 newest pieces
         }
         return;
     }
@@ -148,11 +123,11 @@ __global__ __launch_bounds__(704) void linear_ws_kernel(const LinWSParams p) {
         int prow;                                              // packed weight row this lane feeds to M index l31
         if constexpr (GEGLU) {
             // the wave's 16 output columns: packed rows [value 16 | ... ] live in blocks of 32 value / 32 gate columns
-            const int oc = wave * 16 + (ws_perm(l31) & 15);    // output column within the slice's 160
-            const int gate = ws_perm(l31) >> 4;
+            const int oc = wave * 16 + (lin_perm(l31) & 15);    // output column within the slice's 160
+            const int gate = lin_perm(l31) >> 4;
             prow = slice * WS_BN + (oc >> 5) * 64 + gate * 32 + (oc & 31);
         } else {
-            prow = slice * WS_BN + wave * 32 + ws_perm(l31);
+            prow = slice * WS_BN + wave * 32 + lin_perm(l31);
         }
         const char* wp = reinterpret_cast<const char*>(p.w) + (size_t)prow * (WS_K * 2) + hi * 16;
         const bool ok = prow < p.n_pad;
@@ -189,7 +164,7 @@ __global__ __launch_bounds__(704) void linear_ws_kernel(const LinWSParams p) {
     f32x16 acc0, acc1;
     u32x4 res[2];                                     // residual chunks of the block whose epilogue comes next
     res[0] = res[1] = u32x4{0u, 0u, 0u, 0u};
-    unsigned rowoff_prev = kWsOob;                    // dst byte offset of this lane's row in the previous block
+    unsigned rowoff_prev = kBufOob;                    // dst byte offset of this lane's row in the previous block
 
 // bias -> accumulator (registers 4a + e of half-wave h = packed column 16 (a >> 1) + 8 h + 4 (a & 1) + e of the wave's 32)
 #define WS_INIT(acc_)                                                                                              \
@@ -225,25 +200,25 @@ __global__ __launch_bounds__(704) void linear_ws_kernel(const LinWSParams p) {
 #define WS_BLOCK(acc_cur_, acc_prev_, blk_base_, rowoff_new_, rowres_new_)                                         \
     {                                                                                                              \
         Frag fq_[PF + 1];                                                                                          \
-        _Pragma("unroll") for (int q = 0; q < PF; ++q) fq_[q] = ws_frag<T>(blk_base_ + (q >> 2) * 8192 + (a_off ^ ((q & 3) << 5)));   \
+        _Pragma("unroll") for (int q = 0; q < PF; ++q) fq_[q] = lin_frag<T>(blk_base_ + (q >> 2) * 8192 + (a_off ^ ((q & 3) << 5)));  \
         Chunk<T> oc0_, oc1_;                                                                                       \
         oc0_.zero(); oc1_.zero();                                                                                  \
         _Pragma("unroll") for (int kk = 0; kk < WS_KS; ++kk) {                                                     \
-            if (kk + PF < WS_KS) fq_[(kk + PF) % (PF + 1)] = ws_frag<T>(blk_base_ + ((kk + PF) >> 2) * 8192 + (a_off ^ (((kk + PF) & 3) << 5)));   \
+            if (kk + PF < WS_KS) fq_[(kk + PF) % (PF + 1)] = lin_frag<T>(blk_base_ + ((kk + PF) >> 2) * 8192 + (a_off ^ (((kk + PF) & 3) << 5)));  \
             __builtin_amdgcn_sched_barrier(0);                                                                     \
-            acc_cur_ = WsMma<T>::mma(wf[kk], fq_[kk % (PF + 1)], acc_cur_);                                        \
+            acc_cur_ = LinMma<T>::mma(wf[kk], fq_[kk % (PF + 1)], acc_cur_);                                       \
             if (kk == 4) {                                                                                         \
                 if constexpr (RES) asm volatile("s_waitcnt vmcnt(%2)" : "+v"(res[0]), "+v"(res[1]) : "n"(NST));   \
             }                                                                                                      \
             if (kk >= 4 && kk < 12) WS_MICRO(acc_prev_, kk - 4)                                                    \
             if (RES && kk == 12) {                                                                                 \
-                const unsigned o0_ = rowres_new_ != kWsOob ? rowres_new_ + (unsigned)col0 * 2u : kWsOob;           \
+                const unsigned o0_ = rowres_new_ != kBufOob ? rowres_new_ + (unsigned)col0 * 2u : kBufOob;         \
                 asm volatile("s_nop 4\n\tbuffer_load_dwordx4 %0, %2, %4, 0 offen\n\tbuffer_load_dwordx4 %1, %3, %4, 0 offen"                 \
-                             : "=&v"(res[0]), "=&v"(res[1]) : "v"(o0_), "v"(o0_ == kWsOob ? kWsOob : o0_ + 32u), "s"(rres));                   \
+                             : "=&v"(res[0]), "=&v"(res[1]) : "v"(o0_), "v"(o0_ == kBufOob ? kBufOob : o0_ + 32u), "s"(rres));                    \
             }                                                                                                      \
             if (kk == 13) {                                                                                        \
-                ws_store<NT>(rdst, oc0_.raw, rowoff_prev == kWsOob ? kWsOob : rowoff_prev + (unsigned)col0 * 2u);  \
-                if constexpr (NST == 2) ws_store<NT>(rdst, oc1_.raw, rowoff_prev == kWsOob ? kWsOob : rowoff_prev + (unsigned)col0 * 2u + 32u);   \
+                ws_store<NT>(rdst, oc0_.raw, rowoff_prev == kBufOob ? kBufOob : rowoff_prev + (unsigned)col0 * 2u); \
+                if constexpr (NST == 2) ws_store<NT>(rdst, oc1_.raw, rowoff_prev == kBufOob ? kBufOob : rowoff_prev + (unsigned)col0 * 2u + 32u);  \
             }                                                                                                      \
         }                                                                                                          \
         __builtin_amdgcn_sched_barrier(0);                                                                         \
@@ -260,15 +235,15 @@ __global__ __launch_bounds__(704) void linear_ws_kernel(const LinWSParams p) {
         const char* sb = smem + rsl * WS_SLOT;
         {
             const int m = row0 + l31;
-            const unsigned ro = m < p.M ? (unsigned)m * (unsigned)p.dst_ld * 2u : kWsOob;
-            const unsigned rr = m < p.M ? (unsigned)m * (unsigned)p.n_dst * 2u : kWsOob;
+            const unsigned ro = m < p.M ? (unsigned)m * (unsigned)p.dst_ld * 2u : kBufOob;
+            const unsigned rr = m < p.M ? (unsigned)m * (unsigned)p.n_dst * 2u : kBufOob;
             WS_INIT(acc0)
             WS_BLOCK(acc0, acc1, sb, ro, rr)
         }
         {
             const int m = row0 + 32 + l31;
-            const unsigned ro = m < p.M ? (unsigned)m * (unsigned)p.dst_ld * 2u : kWsOob;
-            const unsigned rr = m < p.M ? (unsigned)m * (unsigned)p.n_dst * 2u : kWsOob;
+            const unsigned ro = m < p.M ? (unsigned)m * (unsigned)p.dst_ld * 2u : kBufOob;
+            const unsigned rr = m < p.M ? (unsigned)m * (unsigned)p.n_dst * 2u : kBufOob;
             WS_INIT(acc1)
             WS_BLOCK(acc1, acc0, sb + 4096, ro, rr)
         }
@@ -281,8 +256,8 @@ __global__ __launch_bounds__(704) void linear_ws_kernel(const LinWSParams p) {
         if constexpr (RES) asm volatile("s_waitcnt vmcnt(0)" : "+v"(res[0]), "+v"(res[1]));
 #pragma unroll
         for (int m = 0; m < 8; ++m) WS_MICRO(acc1, m)
-        ws_store<NT>(rdst, oc0_.raw, rowoff_prev == kWsOob ? kWsOob : rowoff_prev + (unsigned)col0 * 2u);
-        if constexpr (NST == 2) ws_store<NT>(rdst, oc1_.raw, rowoff_prev == kWsOob ? kWsOob : rowoff_prev + (unsigned)col0 * 2u + 32u);
+        ws_store<NT>(rdst, oc0_.raw, rowoff_prev == kBufOob ? kBufOob : rowoff_prev + (unsigned)col0 * 2u);
+        if constexpr (NST == 2) ws_store<NT>(rdst, oc1_.raw, rowoff_prev == kBufOob ? kBufOob : rowoff_prev + (unsigned)col0 * 2u + 32u);
     }
 #undef WS_INIT
 #undef WS_MICRO
@@ -318,33 +293,14 @@ template <typename T, int EPI, bool RES> static int linear_ws_launch(const LinWS
 int linear_ws_run(const mvldm_igemm_desc& d, hipStream_t s) {
     MVLDM_REQUIRE(linear_ws_applicable(d), "igemm: tile 14 (weight-stationary Linear, K = 320) does not apply to this problem");
     LinWSParams p;
-    p.a = d.src0; p.w = d.weight; p.bias = d.bias; p.residual = d.residual; p.dst = d.dst;
-    p.M = d.n_img * d.h_out * d.w_out; p.n_out = d.n_out; p.n_pad = d.n_pad;
-    p.n_dst = d.epilogue == MVLDM_EPI_GEGLU ? d.n_out / 2 : d.n_out;
-    p.dst_ld = d.dst_ld > 0 ? d.dst_ld : p.n_dst;
-    p.out_scale = d.out_scale;
+    lin_fill_params(p, d, kWsFake & 5);      // (c0 == k_pad == WS_K here; the weights are read once through a plain pointer: no knob for them)
     p.n_slices = d.n_pad / WS_BN;
     p.n_slots = (p.M + WS_ROWS - 1) / WS_ROWS;
-    static int n_cu = 0;
-    if (!n_cu) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-            n_cu = prop.multiProcessorCount;
-        else
-            n_cu = 256;
-    }
-    const int cu_x = std::max(1, n_cu / 8);
+    const int cu_x = std::max(1, cu_count() / 8);
     MVLDM_REQUIRE(p.n_slices <= cu_x, "igemm: tile 14: %d column slices exceed the %d CUs of an XCD", p.n_slices, cu_x);
     p.groups = std::max(1, std::min(cu_x / p.n_slices, (p.n_slots + 7) / 8));
-    p.a_bytes = (unsigned)((double)p.M * WS_K * 2.0); p.w_bytes = (unsigned)((double)d.n_pad * WS_K * 2.0);
-    p.bias_bytes = d.bias ? (unsigned)d.n_out * 4u : 0u;
-    p.res_bytes = d.residual ? (unsigned)((double)p.M * p.n_dst * 2.0) : 0u;
-    p.dst_bytes = (unsigned)((double)p.M * p.dst_ld * 2.0);
     static const int kNt = knob_int("MVLDM_STREAM_STORES", 0);
     p.nt_store = kNt == 1;
-    if (kWsFake & 1) p.a_bytes = 0;
-    if (kWsFake & 4) p.dst_bytes = 0;
     const int grid = 8 * p.groups * p.n_slices;
     const bool res = d.residual != nullptr;
     return dispatch_dtype(d.act_dtype, [&](auto t) -> int {

@@ -53,8 +53,6 @@ static const int kSkFake = knob_int("MVLDM_SK_FAKE", 0);   // 1 no W traffic, 2 
 static constexpr int kSkFake = 0;
 #endif
 
-constexpr unsigned kSkOob = 0xFFFFFFF0u;
-
 template <typename T> struct SkMma;
 template <> struct SkMma<bf16_t> {
     using Frag = bf16x8;
@@ -64,8 +62,6 @@ template <> struct SkMma<f16_t> {
     using Frag = f16x8;
     static __device__ __forceinline__ f32x4 mma(Frag a, Frag b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
 };
-
-constexpr int sk_vm(int n) { return (n & 15) | ((n >> 4) << 14) | 0x0F70; }   // s_waitcnt vmcnt(n) only (gfx9 encoding)
 
 // compile-time geometry of one instantiation.  (A "balanced" 3x3 form -- 8 waves, 4 channel blocks per stage, wave w owns tap w of all 8
 // (channel block, k-step) pairs plus tap 8 of pair w: 27 MFMAs per barrier instead of 6 -- was built and measured EQUAL to the
@@ -223,7 +219,7 @@ __device__ __forceinline__ void sk_issue_a1(const SkParams& p, const SkStreams<C
         const int cb = cb_first + st.a_cbl[pp];
         const bool in_k = cb < p.n_cbs;               // channel blocks past K (the stages past the end, a ragged last stage) read zeros
         char* dst = st.a_dst[pp] >= 0 ? slot_base + st.a_dst[pp] : smem + C::DUMP;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(r0, (__attribute__((address_space(3))) void*)dst, 16, in_k ? st.a_voff[pp] : kSkOob, cb * 128, 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(r0, (__attribute__((address_space(3))) void*)dst, 16, in_k ? st.a_voff[pp] : kBufOob, cb * 128, 0, 0);
     }
 }
 // two sources concatenated along the channels: a piece reads the source its channel block lies in
@@ -241,7 +237,7 @@ __device__ __forceinline__ void sk_issue_a2(const SkParams& p, const SkStreams<C
         const unsigned bytes = from0 ? p.src0_bytes : p.src1_bytes;
         const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, bytes, 0x00020000);
         const unsigned v = from0 ? st.a_voff[pp] : st.a_voff1[pp];
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)dst, 16, in_k ? v : kSkOob, (from0 ? cb : cb - p.cb0) * 128, 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)dst, 16, in_k ? v : kBufOob, (from0 ? cb : cb - p.cb0) * 128, 0, 0);
     }
 }
 template <typename C>
@@ -333,8 +329,8 @@ __global__ __launch_bounds__(C::NW * 64) void skinny_kernel(const SkParams p) {
         const int row = pr * 8 + (lane >> 3);
         const unsigned chunk = (unsigned)((lane & 7) ^ ((row >> 1) & 7));
         const bool ok = live && row < src_rows;
-        st.a_voff[pp] = ok ? (unsigned)(src_row0 + row) * (unsigned)(p.c0 * 2) + chunk * 16u : kSkOob;
-        st.a_voff1[pp] = (C::DUAL && ok) ? (unsigned)(src_row0 + row) * (unsigned)(p.c1 * 2) + chunk * 16u : kSkOob;
+        st.a_voff[pp] = ok ? (unsigned)(src_row0 + row) * (unsigned)(p.c0 * 2) + chunk * 16u : kBufOob;
+        st.a_voff1[pp] = (C::DUAL && ok) ? (unsigned)(src_row0 + row) * (unsigned)(p.c1 * 2) + chunk * 16u : kBufOob;
         st.a_dst[pp] = live ? cbl * C::CBS + pr * 1024 : -1;
         st.a_cbl[pp] = cbl;
     }
@@ -417,7 +413,7 @@ __global__ __launch_bounds__(C::NW * 64) void skinny_kernel(const SkParams p) {
             for (int j = 0; j < DS; ++j) {
                 const int s = rnd * DS + j;
                 SK_STAMP(0)
-                __builtin_amdgcn_s_waitcnt(sk_vm(C::WAIT));
+                __builtin_amdgcn_s_waitcnt(waitcnt_vmcnt(C::WAIT));
                 SK_STAMP(1)
                 __builtin_amdgcn_s_barrier();         // A(s) of every wave is in LDS; the slot of stage s-1 has been read by every wave
                 SK_STAMP(2)
@@ -439,7 +435,7 @@ __global__ __launch_bounds__(C::NW * 64) void skinny_kernel(const SkParams p) {
             for (int j = 0; j < DS; ++j) {
                 const int s = rnd * DS + j;
                 SK_STAMP(0)
-                __builtin_amdgcn_s_waitcnt(sk_vm(C::WAIT_B));
+                __builtin_amdgcn_s_waitcnt(waitcnt_vmcnt(C::WAIT_B));
                 SK_STAMP(1)
                 __builtin_amdgcn_s_barrier();
                 SK_STAMP(2)
@@ -457,7 +453,7 @@ __global__ __launch_bounds__(C::NW * 64) void skinny_kernel(const SkParams p) {
 #endif
     // ---- fold the waves' partial tiles through LDS (the ring is dead) in wave order, then bias / time-embedding row / activation /
     // residual (all requested at the top of the kernel) and the store
-    __builtin_amdgcn_s_waitcnt(sk_vm(0));             // the out-of-range refills of the last stages (they write zeros into the ring)
+    __builtin_amdgcn_s_waitcnt(waitcnt_vmcnt(0));     // the out-of-range refills of the last stages (they write zeros into the ring)
     __syncthreads();
 #pragma unroll
     for (int i = 0; i < MT; ++i)
@@ -509,7 +505,7 @@ __device__ __forceinline__ void iw_issue_a(const SkParams& p, const unsigned (&a
 #pragma unroll
     for (int pc = 0; pc < C::PPC; ++pc) {
         const unsigned v = from0 ? a_voff[pc] : a_voff1[pc];
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)(slot + pc * 1024), 16, in_k ? v : kSkOob, soff, 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)(slot + pc * 1024), 16, in_k ? v : kBufOob, soff, 0, 0);
     }
 }
 
@@ -522,7 +518,7 @@ __device__ __forceinline__ void iw_issue_w(const SkParams& p, u32x4 (&wf)[C::NT]
     for (int j = 0; j < C::NT; ++j) {
         const int nt = tile0 + j;
         const unsigned soff = ((unsigned)nt * (unsigned)p.ksteps + (unsigned)(cb * C::ITEMS + it)) * 1024u;
-        wf[j] = __builtin_amdgcn_raw_buffer_load_b128(rw, (in_k && nt < p.n_tiles) ? (unsigned)lane * 16u : kSkOob, soff, 0);
+        wf[j] = __builtin_amdgcn_raw_buffer_load_b128(rw, (in_k && nt < p.n_tiles) ? (unsigned)lane * 16u : kBufOob, soff, 0);
     }
 }
 
@@ -581,8 +577,8 @@ __global__ __launch_bounds__(C::NW * 64) void skinny_iws_kernel(const SkParams p
         const int row = pc * 8 + (lane >> 3);
         const unsigned chunk = (unsigned)((lane & 7) ^ ((row >> 1) & 7));
         const bool ok = row < src_rows;
-        a_voff[pc] = ok ? (unsigned)(src_row0 + row) * (unsigned)(p.c0 * 2) + chunk * 16u : kSkOob;
-        a_voff1[pc] = (C::DUAL && ok) ? (unsigned)(src_row0 + row) * (unsigned)(p.c1 * 2) + chunk * 16u : kSkOob;
+        a_voff[pc] = ok ? (unsigned)(src_row0 + row) * (unsigned)(p.c0 * 2) + chunk * 16u : kBufOob;
+        a_voff1[pc] = (C::DUAL && ok) ? (unsigned)(src_row0 + row) * (unsigned)(p.c1 * 2) + chunk * 16u : kBufOob;
     }
 
     SkEpi<T, NW, MT, NT> epi;
@@ -616,7 +612,7 @@ __global__ __launch_bounds__(C::NW * 64) void skinny_iws_kernel(const SkParams p
         for (int j = 0; j < DS; ++j) {
             const int q = rnd * DS + j;
             const int cb_next = wave + (q + DS) * NW;
-            __builtin_amdgcn_s_waitcnt(sk_vm(C::WAIT));       // A(q) -- and the older W(q, *) -- have landed
+            __builtin_amdgcn_s_waitcnt(waitcnt_vmcnt(C::WAIT));  // A(q) -- and the older W(q, *) -- have landed
             const char* sb = wb + j * C::SLOT;
             // items software-pipelined one ahead: the fragment reads of item it+1 are issued before the MFMAs of item it (sched_barrier
             // pins it: left alone hipcc sinks every ds_read next to its MFMA, which then waits a full LDS round trip)
@@ -645,7 +641,7 @@ __global__ __launch_bounds__(C::NW * 64) void skinny_iws_kernel(const SkParams p
 #ifdef MVLDM_EXPERIMENTS
     if (p.fake & 16) return;
 #endif
-    __builtin_amdgcn_s_waitcnt(sk_vm(0));             // the out-of-range refills of the last steps (they write zeros into the ring)
+    __builtin_amdgcn_s_waitcnt(waitcnt_vmcnt(0));     // the out-of-range refills of the last steps (they write zeros into the ring)
     __syncthreads();                                  // the rings are dead: the partial tiles are parked over them
 #pragma unroll
     for (int i = 0; i < MT; ++i)

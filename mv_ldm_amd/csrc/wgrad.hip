@@ -237,7 +237,6 @@ constexpr int WD_BN = 320, WD_BC = 128;
 constexpr int WD_DP = 704, WD_XP = 320;                         // row pitches (bytes): one pixel row of both tiles = 1 KB = one DMA piece
 constexpr int WD_RING = 128 * 1024;                             // LDS ring: BP pixels per slot, 128 / BP slots
 static_assert(WD_DP + WD_XP == 1024, "a pixel row of the stage is one 1 KB piece");
-constexpr unsigned kWdOob = 0xFFFFFFF0u;
 
 struct WgradDmaParams {
     WgradParams w;
@@ -271,7 +270,7 @@ __device__ __forceinline__ void wd_issue(const WgradDmaParams& q, char* stage, i
                 const int ox = m & wmask, oy = (m >> q.lw) & hmask;
                 ok = ok && (unsigned)(oy + ky - 1) < (unsigned)p.h_out && (unsigned)(ox + kx - 1) < (unsigned)p.w_out;
             }
-            const unsigned v = (ok && xcol[j] != kWdOob) ? (unsigned)(m + dy_disp) * (unsigned)p.ctot * 2u + xcol[j] : kWdOob;
+            const unsigned v = (ok && xcol[j] != kBufOob) ? (unsigned)(m + dy_disp) * (unsigned)p.ctot * 2u + xcol[j] : kBufOob;
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, dst, 16, v, 0, 0, 0);
         }
     }
@@ -303,7 +302,7 @@ __global__ __launch_bounds__(512) void wgrad_dma_kernel(const WgradDmaParams q) 
 #pragma unroll
     for (int j = 0; j < PW; ++j) {
         const int piece = wave + 8 * j;
-        dv[j] = kWdOob; xcol[j] = kWdOob; xrow[j] = 0;
+        dv[j] = kBufOob; xcol[j] = kBufOob; xrow[j] = 0;
         if (piece < DQ) {
             const int s = piece * 64 + lane, row = s / (WD_DP / 16), ch = s - row * (WD_DP / 16);
             const int n = tn * WD_BN + ch * 8;
@@ -481,7 +480,7 @@ static bool wgrad_wide_ok(const mvldm_wgrad_desc& d) {
     if (d.ksize == 3 && (d.pad != 1 || d.h_in != d.h_out || d.w_in != d.w_out || ilog2_exact(d.w_out) < 0 || ilog2_exact(d.h_out) < 0)) return false;
     if (d.ksize == 1 && (d.pad != 0 || d.h_in != d.h_out || d.w_in != d.w_out)) return false;
     const size_t xb = (size_t)d.n_img * d.h_in * d.w_in * d.c0 * 2u;
-    return xb < 0xFFFFFFF0ull;
+    return xb < kBufOob;
 }
 
 static int wgrad_run_wide(const mvldm_wgrad_desc& d, hipStream_t s, int tcode = 0) {
