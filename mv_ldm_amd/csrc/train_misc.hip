@@ -18,6 +18,19 @@ __device__ __forceinline__ float gelu_grad_f(float x) {
     return phi + x * 0.3989422804014327f * __expf(-0.5f * x * x);
 }
 
+// sum of one fp64 value per thread over the 256 threads of a workgroup, returned to every thread: LDS, halving tree from 128 -- one
+// fixed order of additions, the same on every run
+__device__ __forceinline__ double block_sum(double acc) {
+    __shared__ double s_red[256];
+    s_red[threadIdx.x] = acc;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (threadIdx.x < o) s_red[threadIdx.x] += s_red[threadIdx.x + o];
+        __syncthreads();
+    }
+    return s_red[0];
+}
+
 // ---- column sums ------------------------------------------------------------------------------------
 // x [n_seg * rows_per_seg][ld] (activation dtype), columns [0, n): part[seg][chunk][n] = sum over the chunk's rows.
 // A thread owns one 16-byte chunk column; the block sweeps RB rows at a time; deterministic (fixed order, no atomics to HBM).
@@ -179,7 +192,6 @@ template <typename T>
 __global__ __launch_bounds__(256) void mse_kernel(const float* __restrict__ pred, const float* __restrict__ noise, const int32_t* __restrict__ tgt_img,
                                                   int n_tgt, int hw, int c, double* __restrict__ partial, T* __restrict__ dpred, int dc, float gscale,
                                                   const float* __restrict__ amp_scale) {
-    __shared__ double s_red[256];
     const size_t per = (size_t)hw * c, total = (size_t)n_tgt * per;
     if (amp_scale) gscale *= amp_scale[0];       // f16 loss scaling: dY carries S before its rounding (S: a power of two by default)
     double acc = 0.0;
@@ -192,32 +204,20 @@ __global__ __launch_bounds__(256) void mse_kernel(const float* __restrict__ pred
         acc += (double)d * (double)d;
         if (dpred) dpred[((size_t)img * hw + pix) * dc + ch] = from_f32<T>(gscale * d);
     }
-    s_red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (threadIdx.x < o) s_red[threadIdx.x] += s_red[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) partial[blockIdx.x] = s_red[0];
+    const double sum = block_sum(acc);
+    if (threadIdx.x == 0) partial[blockIdx.x] = sum;
 }
 // out[0] (+)= scale * sum(partial[0..n))
 __global__ __launch_bounds__(256) void sum_finish_kernel(const double* __restrict__ partial, int n, double scale, float* __restrict__ out, int accumulate) {
-    __shared__ double s_red[256];
     double acc = 0.0;
     for (int i = threadIdx.x; i < n; i += 256) acc += partial[i];
-    s_red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (threadIdx.x < o) s_red[threadIdx.x] += s_red[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[0] = (accumulate ? out[0] : 0.f) + (float)(scale * s_red[0]);
+    const double sum = block_sum(acc);
+    if (threadIdx.x == 0) out[0] = (accumulate ? out[0] : 0.f) + (float)(scale * sum);
 }
 
 // ---- optimizer ----------------------------------------------------------------------------------------------
 // sum of squares of a flat fp32 buffer -> partial[block] (fp64)
 __global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ g, size_t n, double* __restrict__ partial) {
-    __shared__ double s_red[256];
     double acc = 0.0;
     const size_t n4 = n / 4, step = (size_t)gridDim.x * 256;
     size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -236,75 +236,95 @@ __global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ g,
         acc += (double)v[0] * v[0] + (double)v[1] * v[1] + (double)v[2] * v[2] + (double)v[3] * v[3];
     }
     if (blockIdx.x == 0 && threadIdx.x < (int)(n - n4 * 4)) { const float v = g[n4 * 4 + threadIdx.x]; acc += (double)v * v; }
-    s_red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (threadIdx.x < o) s_red[threadIdx.x] += s_red[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) partial[blockIdx.x] = s_red[0];
+    const double sum = block_sum(acc);
+    if (threadIdx.x == 0) partial[blockIdx.x] = sum;
 }
-// torch.nn.utils.clip_grad_norm_: total = sqrt(extra_sumsq + sum partial) [extra: other ranks' shards, already all-reduced];
-// norm_out[0] = total, norm_out[1] = clip coefficient min(1, max_norm / (total + 1e-6))  (max_norm <= 0: no clipping)
-__global__ __launch_bounds__(256) void clip_coef_kernel(const double* __restrict__ partial, int n, const float* __restrict__ sumsq_in, float max_norm,
-                                                        float* __restrict__ norm_out) {
-    __shared__ double s_red[256];
-    double acc = 0.0;
-    for (int i = threadIdx.x; i < n; i += 256) acc += partial[i];
-    s_red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (threadIdx.x < o) s_red[threadIdx.x] += s_red[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        const double tot2 = sumsq_in ? (double)sumsq_in[0] : s_red[0];
-        const float total = (float)sqrt(tot2);
-        norm_out[0] = total;
-        norm_out[1] = max_norm > 0.f ? fminf(1.0f, max_norm / (total + 1e-6f)) : 1.0f;
-        norm_out[2] = (float)s_red[0];      // this buffer's own sum of squares (what a sharded optimizer all-reduces)
-    }
-}
-// the same on gradients that carry the loss scale S: the fp64 sums are unscaled (x 1/S^2) before anything is rounded to fp32, and
+// torch.nn.utils.clip_grad_norm_: total = sqrt(sumsq_in, or else this buffer's own sum) [sumsq_in: all ranks' shards, already all-reduced];
+// norm_out[0] = total, norm_out[1] = clip coefficient min(1, max_norm / (total + 1e-6))  (max_norm <= 0: no clipping).
+// With a loss scaler's record the gradients carry S: the fp64 sum is unscaled (x 1/S^2) before anything is rounded to fp32, and
 // found_inf = the total is not finite.  1/S as torch's GradScaler.unscale_ forms it (fp64 reciprocal, rounded to fp32).
-__global__ __launch_bounds__(256) void clip_coef_amp_kernel(const double* __restrict__ partial, int n, const float* __restrict__ sumsq_in,
-                                                            float max_norm, float* __restrict__ norm_out, mvldm_amp_state* __restrict__ amp) {
-    __shared__ double s_red[256];
+__global__ __launch_bounds__(256) void clip_coef_kernel(const double* __restrict__ partial, int n, const float* __restrict__ sumsq_in, float max_norm,
+                                                        float* __restrict__ norm_out, mvldm_amp_state* __restrict__ amp) {
     double acc = 0.0;
     for (int i = threadIdx.x; i < n; i += 256) acc += partial[i];
-    s_red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (threadIdx.x < o) s_red[threadIdx.x] += s_red[threadIdx.x + o];
-        __syncthreads();
-    }
+    double own = block_sum(acc);
     if (threadIdx.x == 0) {
-        const double inv = (double)(float)(1.0 / (double)amp->scale);
-        const double own = s_red[0] * inv * inv;
+        if (amp) {
+            const double inv = (double)(float)(1.0 / (double)amp->scale);
+            own = own * inv * inv;
+        }
         const double tot2 = sumsq_in ? (double)sumsq_in[0] : own;
         const float total = (float)sqrt(tot2);
         norm_out[0] = total;
         norm_out[1] = max_norm > 0.f ? fminf(1.0f, max_norm / (total + 1e-6f)) : 1.0f;
-        norm_out[2] = (float)own;
-        amp->found_inf = isfinite(tot2) ? 0 : 1;
+        norm_out[2] = (float)own;      // this buffer's own sum of squares (what a sharded optimizer all-reduces)
+        if (amp) amp->found_inf = isfinite(tot2) ? 0 : 1;
     }
 }
+
 // torch.optim.AdamW (decoupled weight decay, no amsgrad), one launch over the flat fp32 master parameters:
-//   g *= gscale * clip;  p *= 1 - lr * wd;  m = b1 m + (1 - b1) g;  v = b2 v + (1 - b2) g^2;
-//   p -= (lr / bc1) * m / (sqrt(v) / sqrt(bc2) + eps)          (bc = 1 - beta^step, computed on the host in fp64)
-__global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                                                    size_t n, float lr, float b1, float b2, float eps, float wd, float step_size, float inv_sqrt_bc2,
-                                                    float gscale, const float* __restrict__ clip) {
-    const float gs = gscale * (clip ? clip[1] : 1.0f);
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
-        const float gi = g[i] * gs;
-        float pi = p[i] * (1.0f - lr * wd);
-        const float mi = b1 * m[i] + (1.0f - b1) * gi;
-        const float vi = b2 * v[i] + (1.0f - b2) * gi * gi;
-        m[i] = mi;
-        v[i] = vi;
+//   g *= gs;  p *= 1 - lr * wd;  m = b1 m + (1 - b1) g;  v = b2 v + (1 - b2) g^2;
+//   p -= (lr / bc1) * m / (sqrt(v) / sqrt(bc2) + eps)          (bc = 1 - beta^step)
+struct AdamW {
+    float lr, b1, b2, eps, wd, step_size, inv_sqrt_bc2, gs;      // step_size = lr / bc1, inv_sqrt_bc2 = 1 / sqrt(bc2);  gs: see prepare()
+
+    // Completes the constants with what only the device knows: gs = grad_scale * clip coefficient and, under a loss scaler's record,
+    // / S, with the bias correction of step adam_step + 1 formed here in fp64 (as adamw_run forms it on the host without a record).
+    // false: a found_inf step -- the whole grid returns before loading anything, p, m, v stay untouched.
+    __device__ __forceinline__ bool prepare(const float* __restrict__ clip, const mvldm_amp_state* __restrict__ amp) {
+        gs = gs * (clip ? clip[1] : 1.0f);
+        if (!amp) return true;
+        if (amp->found_inf) return false;
+        const int step = amp->adam_step + 1;
+        const double bc1 = 1.0 - pow((double)b1, step), bc2 = 1.0 - pow((double)b2, step);
+        step_size = (float)(lr / bc1);
+        inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
+        gs = gs * (float)(1.0 / (double)amp->scale);
+        return true;
+    }
+    __device__ __forceinline__ void update(float& p, float g, float& m, float& v) const {
+        const float gi = g * gs;
+        float pi = p * (1.0f - lr * wd);
+        const float mi = b1 * m + (1.0f - b1) * gi;
+        const float vi = b2 * v + (1.0f - b2) * gi * gi;
+        m = mi;
+        v = vi;
         pi -= step_size * (mi / (sqrtf(vi) * inv_sqrt_bc2 + eps));
-        p[i] = pi;
+        p = pi;
+    }
+};
+
+__global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                                    size_t n, AdamW a, const float* __restrict__ clip, const mvldm_amp_state* __restrict__ amp) {
+    if (!a.prepare(clip, amp)) return;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) a.update(p[i], g[i], m[i], v[i]);
+}
+// 16-byte form of the same update: four parameters per thread and memory instruction (7 streams x 3.7 GB per step: the scalar
+// kernel moved them at 4.2 TB/s)
+template <bool NT>
+__global__ __launch_bounds__(256) void adamw_kernel4(f32x4* __restrict__ p, const f32x4* __restrict__ g, f32x4* __restrict__ m, f32x4* __restrict__ v,
+                                                     size_t n4, AdamW a, const float* __restrict__ clip, const mvldm_amp_state* __restrict__ amp) {
+    if (!a.prepare(clip, amp)) return;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
+        // streamed once per step, 26 GB in all: nothing here is worth a cache line (MVLDM_ADAMW_NT=0: plain loads / stores, A/B)
+        const f32x4 g4 = NT ? __builtin_nontemporal_load(g + i) : g[i];
+        f32x4 m4 = NT ? __builtin_nontemporal_load(m + i) : m[i], v4 = NT ? __builtin_nontemporal_load(v + i) : v[i];
+        f32x4 p4 = NT ? __builtin_nontemporal_load(p + i) : p[i];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            float pe = p4[e], me = m4[e], ve = v4[e];       // (a reference cannot bind to a vector element)
+            a.update(pe, g4[e], me, ve);
+            p4[e] = pe, m4[e] = me, v4[e] = ve;
+        }
+        if (NT) {
+            __builtin_nontemporal_store(m4, m + i);
+            __builtin_nontemporal_store(v4, v + i);
+            __builtin_nontemporal_store(p4, p + i);
+        } else {
+            m[i] = m4;
+            v[i] = v4;
+            p[i] = p4;
+        }
     }
 }
 
@@ -314,87 +334,6 @@ __global__ __launch_bounds__(256) void ema_kernel(float* __restrict__ avg, const
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
         const float a = avg[i], q = p[i], d = __fsub_rn(q, a);
         avg[i] = w < 0.5f ? fmaf(w, d, a) : fmaf(-d, __fsub_rn(1.0f, w), q);      // ATen's lerp: fmadd(weight, diff, start) in its vectorised form
-    }
-}
-
-// 16-byte form of the same update: four parameters per thread and memory instruction (7 streams x 3.7 GB per step: the scalar
-// kernel moved them at 4.2 TB/s)
-template <bool NT>
-__global__ __launch_bounds__(256) void adamw_kernel4(f32x4* __restrict__ p, const f32x4* __restrict__ g, f32x4* __restrict__ m, f32x4* __restrict__ v,
-                                                     size_t n4, float lr, float b1, float b2, float eps, float wd, float step_size, float inv_sqrt_bc2,
-                                                     float gscale, const float* __restrict__ clip) {
-    const float gs = gscale * (clip ? clip[1] : 1.0f);
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
-        // streamed once per step, 26 GB in all: nothing here is worth a cache line (MVLDM_ADAMW_NT=0: plain loads / stores, A/B)
-        const f32x4 g4 = NT ? __builtin_nontemporal_load(g + i) : g[i], m4 = NT ? __builtin_nontemporal_load(m + i) : m[i],
-                    v4 = NT ? __builtin_nontemporal_load(v + i) : v[i];
-        f32x4 p4 = NT ? __builtin_nontemporal_load(p + i) : p[i], mo, vo;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float gi = g4[e] * gs;
-            float pi = p4[e] * (1.0f - lr * wd);
-            const float mi = b1 * m4[e] + (1.0f - b1) * gi;
-            const float vi = b2 * v4[e] + (1.0f - b2) * gi * gi;
-            mo[e] = mi;
-            vo[e] = vi;
-            pi -= step_size * (mi / (sqrtf(vi) * inv_sqrt_bc2 + eps));
-            p4[e] = pi;
-        }
-        if (NT) {
-            __builtin_nontemporal_store(mo, m + i);
-            __builtin_nontemporal_store(vo, v + i);
-            __builtin_nontemporal_store(p4, p + i);
-        } else {
-            m[i] = mo;
-            v[i] = vo;
-            p[i] = p4;
-        }
-    }
-}
-
-// AdamW under the loss scaler: the step count and the skip decision come from the device record.  A found_inf step leaves p, m, v
-// untouched (the whole grid returns before loading anything); otherwise g' = g * gscale * clip / S and the bias correction of step
-// adam_step + 1 is formed here in fp64, as adamw_run does on the host.
-__global__ __launch_bounds__(256) void adamw_amp_kernel4(f32x4* __restrict__ p, const f32x4* __restrict__ g, f32x4* __restrict__ m,
-                                                         f32x4* __restrict__ v, const float* __restrict__ gp, float* __restrict__ pp,
-                                                         float* __restrict__ mp, float* __restrict__ vp, size_t n, float lr, float b1, float b2,
-                                                         float eps, float wd, float gscale, const float* __restrict__ clip,
-                                                         const mvldm_amp_state* __restrict__ amp) {
-    if (amp->found_inf) return;
-    const int step = amp->adam_step + 1;
-    const double bc1 = 1.0 - pow((double)b1, step), bc2 = 1.0 - pow((double)b2, step);
-    const float step_size = (float)(lr / bc1), inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
-    const float gs = gscale * (clip ? clip[1] : 1.0f) * (float)(1.0 / (double)amp->scale);
-    const size_t n4 = p ? n / 4 : 0;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
-        const f32x4 g4 = __builtin_nontemporal_load(g + i), m4 = __builtin_nontemporal_load(m + i), v4 = __builtin_nontemporal_load(v + i);
-        f32x4 p4 = __builtin_nontemporal_load(p + i), mo, vo;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float gi = g4[e] * gs;
-            float pi = p4[e] * (1.0f - lr * wd);
-            const float mi = b1 * m4[e] + (1.0f - b1) * gi;
-            const float vi = b2 * v4[e] + (1.0f - b2) * gi * gi;
-            mo[e] = mi;
-            vo[e] = vi;
-            pi -= step_size * (mi / (sqrtf(vi) * inv_sqrt_bc2 + eps));
-            p4[e] = pi;
-        }
-        __builtin_nontemporal_store(mo, m + i);
-        __builtin_nontemporal_store(vo, v + i);
-        __builtin_nontemporal_store(p4, p + i);
-    }
-    // unaligned / non-multiple-of-4 form: the scalar pointers (p == nullptr selects it)
-    const size_t ns = p ? 0 : n;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < ns; i += (size_t)gridDim.x * 256) {
-        const float gi = gp[i] * gs;
-        float pi = pp[i] * (1.0f - lr * wd);
-        const float mi = b1 * mp[i] + (1.0f - b1) * gi;
-        const float vi = b2 * vp[i] + (1.0f - b2) * gi * gi;
-        mp[i] = mi;
-        vp[i] = vi;
-        pi -= step_size * (mi / (sqrtf(vi) * inv_sqrt_bc2 + eps));
-        pp[i] = pi;
     }
 }
 
@@ -548,36 +487,13 @@ int mse_run(const float* pred, const float* noise, const int32_t* tgt_img, int n
 }
 
 constexpr int kNormBlocks = 1024;
-int grad_norm_run(const float* g, size_t n, const float* sumsq_in, float max_norm, float* norm_out, double* ws, hipStream_t s) {
+// amp: the loss scaler's device record, or null (gradients that carry no scale)
+int grad_norm_run(const float* g, size_t n, const float* sumsq_in, float max_norm, float* norm_out, mvldm_amp_state* amp, double* ws, hipStream_t s) {
     MVLDM_REQUIRE(g && norm_out && ws, "grad_norm: null pointer");
     hipLaunchKernelGGL(sumsq_kernel, dim3(kNormBlocks), dim3(256), 0, s, g, n, ws);
     int rc = check_launch();
     if (rc) return rc;
-    hipLaunchKernelGGL(clip_coef_kernel, dim3(1), dim3(256), 0, s, ws, kNormBlocks, sumsq_in, max_norm, norm_out);
-    return check_launch();
-}
-
-int grad_norm_amp_run(const float* g, size_t n, const float* sumsq_in, float max_norm, float* norm_out, mvldm_amp_state* amp, double* ws, hipStream_t s) {
-    MVLDM_REQUIRE(g && norm_out && ws && amp, "grad_norm_amp: null pointer");
-    hipLaunchKernelGGL(sumsq_kernel, dim3(kNormBlocks), dim3(256), 0, s, g, n, ws);
-    int rc = check_launch();
-    if (rc) return rc;
-    hipLaunchKernelGGL(clip_coef_amp_kernel, dim3(1), dim3(256), 0, s, ws, kNormBlocks, sumsq_in, max_norm, norm_out, amp);
-    return check_launch();
-}
-
-int adamw_amp_run(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2, float eps, float weight_decay,
-                  float grad_scale, const float* clip, const mvldm_amp_state* amp, hipStream_t s) {
-    if (n == 0) return MVLDM_OK;
-    MVLDM_REQUIRE(p && g && m && v && amp, "adamw_amp: bad arguments");
-    const bool vec = n % 4 == 0 && (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0;
-    if (vec)
-        hipLaunchKernelGGL(adamw_amp_kernel4, dim3(grid_for(n / 4, 2048)), dim3(256), 0, s, reinterpret_cast<f32x4*>(p), reinterpret_cast<const f32x4*>(g),
-                           reinterpret_cast<f32x4*>(m), reinterpret_cast<f32x4*>(v), nullptr, nullptr, nullptr, nullptr, n, lr, beta1, beta2, eps,
-                           weight_decay, grad_scale, clip, amp);
-    else
-        hipLaunchKernelGGL(adamw_amp_kernel4, dim3(grid_for(n, 1024)), dim3(256), 0, s, nullptr, nullptr, nullptr, nullptr, g, p, m, v, n, lr, beta1,
-                           beta2, eps, weight_decay, grad_scale, clip, amp);
+    hipLaunchKernelGGL(clip_coef_kernel, dim3(1), dim3(256), 0, s, ws, kNormBlocks, sumsq_in, max_norm, norm_out, amp);
     return check_launch();
 }
 
@@ -587,24 +503,24 @@ int amp_update_run(mvldm_amp_state* amp, float growth, float backoff, int interv
     return check_launch();
 }
 
+// amp null: the bias correction of `step` is formed here; otherwise on the device, from the record's own count (`step` is not read)
 int adamw_run(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
-              float grad_scale, const float* clip, hipStream_t s) {
+              float grad_scale, const float* clip, const mvldm_amp_state* amp, hipStream_t s) {
     if (n == 0) return MVLDM_OK;
-    MVLDM_REQUIRE(p && g && m && v && step >= 1, "adamw: bad arguments");
-    const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
+    MVLDM_REQUIRE(p && g && m && v && (amp || step >= 1), "adamw: bad arguments");
+    AdamW a = {lr, beta1, beta2, eps, weight_decay, 0.f, 0.f, grad_scale};
+    if (!amp) {
+        const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
+        a.step_size = (float)(lr / bc1);
+        a.inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
+    }
     const bool vec = n % 4 == 0 && (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0;
     static const bool nt = knob_int("MVLDM_ADAMW_NT", 1) != 0;
-    if (vec && nt)
-        hipLaunchKernelGGL(adamw_kernel4<true>, dim3(grid_for(n / 4, 2048)), dim3(256), 0, s, reinterpret_cast<f32x4*>(p), reinterpret_cast<const f32x4*>(g),
-                           reinterpret_cast<f32x4*>(m), reinterpret_cast<f32x4*>(v), n / 4, lr, beta1, beta2, eps, weight_decay, (float)(lr / bc1),
-                           (float)(1.0 / sqrt(bc2)), grad_scale, clip);
-    else if (vec)
-        hipLaunchKernelGGL(adamw_kernel4<false>, dim3(grid_for(n / 4, 2048)), dim3(256), 0, s, reinterpret_cast<f32x4*>(p), reinterpret_cast<const f32x4*>(g),
-                           reinterpret_cast<f32x4*>(m), reinterpret_cast<f32x4*>(v), n / 4, lr, beta1, beta2, eps, weight_decay, (float)(lr / bc1),
-                           (float)(1.0 / sqrt(bc2)), grad_scale, clip);
+    if (vec)
+        hipLaunchKernelGGL(nt ? adamw_kernel4<true> : adamw_kernel4<false>, dim3(grid_for(n / 4, 2048)), dim3(256), 0, s, reinterpret_cast<f32x4*>(p),
+                           reinterpret_cast<const f32x4*>(g), reinterpret_cast<f32x4*>(m), reinterpret_cast<f32x4*>(v), n / 4, a, clip, amp);
     else
-        hipLaunchKernelGGL(adamw_kernel, dim3(grid_for(n, 1024)), dim3(256), 0, s, p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, (float)(lr / bc1),
-                           (float)(1.0 / sqrt(bc2)), grad_scale, clip);
+        hipLaunchKernelGGL(adamw_kernel, dim3(grid_for(n, 1024)), dim3(256), 0, s, p, g, m, v, n, a, clip, amp);
     return check_launch();
 }
 
@@ -646,23 +562,25 @@ extern "C" int mvldm_mse_loss_amp(const float* pred, const float* noise, const i
     return mse_run(pred, noise, tgt_img, n_tgt, hw, c, loss, accumulate, loss_scale, dpred, dpred_c, dpred_dtype, grad_scale, amp_scale, workspace,
                    (hipStream_t)stream);
 }
+extern "C" int mvldm_grad_norm(const float* g, size_t n, const float* sumsq_in, float max_norm, float* norm_out, double* workspace, mvldm_stream_t stream) {
+    return grad_norm_run(g, n, sumsq_in, max_norm, norm_out, nullptr, workspace, (hipStream_t)stream);
+}
 extern "C" int mvldm_grad_norm_amp(const float* g, size_t n, const float* sumsq_in, float max_norm, float* norm_out, mvldm_amp_state* amp,
                                    double* workspace, mvldm_stream_t stream) {
-    return grad_norm_amp_run(g, n, sumsq_in, max_norm, norm_out, amp, workspace, (hipStream_t)stream);
-}
-extern "C" int mvldm_adamw_step_amp(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2, float eps,
-                                    float weight_decay, float grad_scale, const float* clip, const mvldm_amp_state* amp, mvldm_stream_t stream) {
-    return adamw_amp_run(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, grad_scale, clip, amp, (hipStream_t)stream);
-}
-extern "C" int mvldm_amp_update(mvldm_amp_state* amp, float growth_factor, float backoff_factor, int growth_interval, mvldm_stream_t stream) {
-    return amp_update_run(amp, growth_factor, backoff_factor, growth_interval, (hipStream_t)stream);
-}
-extern "C" int mvldm_grad_norm(const float* g, size_t n, const float* sumsq_in, float max_norm, float* norm_out, double* workspace, mvldm_stream_t stream) {
-    return grad_norm_run(g, n, sumsq_in, max_norm, norm_out, workspace, (hipStream_t)stream);
+    MVLDM_REQUIRE(amp, "grad_norm_amp: null record");
+    return grad_norm_run(g, n, sumsq_in, max_norm, norm_out, amp, workspace, (hipStream_t)stream);
 }
 extern "C" int mvldm_adamw_step(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2, float eps, float weight_decay,
                                 int step, float grad_scale, const float* clip, mvldm_stream_t stream) {
-    return adamw_run(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale, clip, (hipStream_t)stream);
+    return adamw_run(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale, clip, nullptr, (hipStream_t)stream);
+}
+extern "C" int mvldm_adamw_step_amp(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2, float eps,
+                                    float weight_decay, float grad_scale, const float* clip, const mvldm_amp_state* amp, mvldm_stream_t stream) {
+    MVLDM_REQUIRE(amp || n == 0, "adamw_amp: null record");
+    return adamw_run(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, 0, grad_scale, clip, amp, (hipStream_t)stream);
+}
+extern "C" int mvldm_amp_update(mvldm_amp_state* amp, float growth_factor, float backoff_factor, int growth_interval, mvldm_stream_t stream) {
+    return amp_update_run(amp, growth_factor, backoff_factor, growth_interval, (hipStream_t)stream);
 }
 extern "C" int mvldm_ema_update(float* avg, const float* p, size_t n, float weight, mvldm_stream_t stream) {
     return ema_run(avg, p, n, weight, (hipStream_t)stream);

@@ -540,35 +540,38 @@ def zero_insert2x(x):
     return out
 
 
-def grad_norm(flat_grad, max_norm: float, norm_out=None, sumsq_in=None):
-    """norm_out fp32 [4]: [total norm, clip coefficient, this buffer's sum of squares, -]"""
-    norm_out = torch.zeros(4, dtype=torch.float32, device=flat_grad.device) if norm_out is None else norm_out
-    ws = workspace(1024 * 8, flat_grad.device, "norm")
-    L.check(L.load().mvldm_grad_norm(flat_grad.data_ptr(), flat_grad.numel(), ptr(sumsq_in), max_norm, norm_out.data_ptr(), ws.data_ptr(), stream()))
+def _grad_norm(g, n: int, max_norm: float, norm_out, sumsq_in, amp_state):
+    ws = workspace(1024 * 8, g.device, "norm")
+    args = (g.data_ptr(), n, ptr(sumsq_in), max_norm, norm_out.data_ptr())
+    if amp_state is None:
+        L.check(L.load().mvldm_grad_norm(*args, ws.data_ptr(), stream()))
+    else:
+        L.check(L.load().mvldm_grad_norm_amp(*args, amp_state.data_ptr(), ws.data_ptr(), stream()))
     return norm_out
 
 
-def adamw_step(p, g, m, v, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, step=1, grad_scale=1.0, clip=None):
-    assert all(t.dtype == torch.float32 and t.is_contiguous() and t.numel() == p.numel() for t in (p, g, m, v))
-    L.check(L.load().mvldm_adamw_step(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), lr, betas[0], betas[1], eps,
-                                      weight_decay, step, grad_scale, ptr(clip), stream()))
-
-
-def grad_norm_amp(flat_grad, max_norm: float, amp_state, norm_out=None, sumsq_in=None):
-    """`grad_norm` of gradients that carry the loss scale of `amp_state` (mvldm_amp_state, int32 [8] device tensor): the norm, clip
-    coefficient and sum of squares of the UNSCALED gradients; sets the record's found_inf when the total is not finite"""
+def grad_norm(flat_grad, max_norm: float, norm_out=None, sumsq_in=None, amp_state=None):
+    """norm_out fp32 [4]: [total norm, clip coefficient, this buffer's sum of squares, -].  `amp_state` (mvldm_amp_state, int32 [8] device
+    tensor): the gradients carry that record's loss scale -- norm, coefficient and sum of squares are those of the UNSCALED gradients,
+    and the record's found_inf is set when the total is not finite"""
     norm_out = torch.zeros(4, dtype=torch.float32, device=flat_grad.device) if norm_out is None else norm_out
-    ws = workspace(1024 * 8, flat_grad.device, "norm")
-    L.check(L.load().mvldm_grad_norm_amp(flat_grad.data_ptr(), flat_grad.numel(), ptr(sumsq_in), max_norm, norm_out.data_ptr(),
-                                         amp_state.data_ptr(), ws.data_ptr(), stream()))
-    return norm_out
+    return _grad_norm(flat_grad, flat_grad.numel(), max_norm, norm_out, sumsq_in, amp_state)
 
 
-def adamw_step_amp(p, g, m, v, lr, amp_state, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, grad_scale=1.0, clip=None):
-    """`adamw_step` with the step count, 1/S and the skip decision read from the loss scaler's device record"""
+def clip_from_sumsq(sumsq, max_norm: float, norm_out, amp_state=None):
+    """total norm + clip coefficient (+ found_inf under `amp_state`) from an already all-reduced, unscaled sum of squares (fp32 [1]):
+    the same kernels on an empty buffer"""
+    return _grad_norm(sumsq, 0, max_norm, norm_out, sumsq, amp_state)
+
+
+def adamw_step(p, g, m, v, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, step=1, grad_scale=1.0, clip=None, amp_state=None):
+    """`amp_state`: the step count (`step` is not used), 1/S and the skip decision are read from the loss scaler's device record"""
     assert all(t.dtype == torch.float32 and t.is_contiguous() and t.numel() == p.numel() for t in (p, g, m, v))
-    L.check(L.load().mvldm_adamw_step_amp(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), lr, betas[0], betas[1], eps,
-                                          weight_decay, grad_scale, ptr(clip), amp_state.data_ptr(), stream()))
+    args = (p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), lr, betas[0], betas[1], eps, weight_decay)
+    if amp_state is None:
+        L.check(L.load().mvldm_adamw_step(*args, step, grad_scale, ptr(clip), stream()))
+    else:
+        L.check(L.load().mvldm_adamw_step_amp(*args, grad_scale, ptr(clip), amp_state.data_ptr(), stream()))
 
 
 def amp_update(amp_state, growth_factor: float, backoff_factor: float, growth_interval: int):

@@ -944,7 +944,8 @@ class DistributedOptimizer:
     the master weights with its slice of the moments, and the slices are all-gathered back.  world = 1 without a process
     group: no collectives; world = 1 WITH a group (`collective=True`): the same reduce-scatter / all-gather calls on a one-rank
     communicator -- the RCCL branch end to end on a single GPU (tests/test_hip_train.py), bit-identical to the plain step.
-    `update` / `sumsq` default to the HIP kernels; the CPU tests inject torch implementations (there is no CPU product path).
+    `ops`: the four device operations of a step (`HipOptimizerOps`, the HIP kernels); the CPU tests inject the same four in torch (there
+    is no CPU product path).
 
     f16 dynamic loss scaling (`scaler`: an enabled `GradScalerCfg`) -- torch.amp.GradScaler under Lightning's automatic optimisation.
     All scaler state is one device record, `amp_state` (include/mvldm.h mvldm_amp_state: S, growth tracker, AdamW's own step count,
@@ -957,13 +958,12 @@ class DistributedOptimizer:
     the trainer's `global_step`: Lightning steps the scheduler and counts the optimizer step whether or not `scaler.step` skipped
     `optimizer.step` (and the EMA update at the start of the next window still happens).  AdamW's bias-correction step is the record's
     count, `adam_step`, which only advances on a taken step.  The 16-bit parameter gather still runs on a skipped step (it gathers
-    unchanged weights: reading the flag on the host to avoid that would cost a sync).
-    `amp`: the four scaler operations (`HipAmpOps` interface: sumsq / clip / update / update_scale); the CPU tests inject torch forms."""
+    unchanged weights: reading the flag on the host to avoid that would cost a sync)."""
 
     def __init__(self, flat: FlatParams, cfg: OptimizerCfg = None, world: int = 1, rank: int = 0, group=None,
-                 bucket_bytes: int = 256 << 20, max_norm: float = 0.1, update=None, sumsq=None, clip=None,
+                 bucket_bytes: int = 256 << 20, max_norm: float = 0.1, ops=None,
                  collective: Optional[bool] = None, effective_batch_size: Optional[int] = None, gather_dtype: Optional[torch.dtype] = None,
-                 scaler: Optional[GradScalerCfg] = None, amp=None):
+                 scaler: Optional[GradScalerCfg] = None):
         cfg = cfg or OptimizerCfg()
         if cfg.name != "AdamW":
             raise NotImplementedError(f"optimizer {cfg.name}: the released config trains with AdamW (baseline.yaml:63)")
@@ -989,13 +989,12 @@ class DistributedOptimizer:
         self.exp_avg = torch.zeros(n_own, dtype=torch.float32, device=dev)
         self.exp_avg_sq = torch.zeros(n_own, dtype=torch.float32, device=dev)
         self.norm = torch.zeros(4, dtype=torch.float32, device=dev)
-        self._update, self._sumsq, self._clip = update or _hip_adamw, sumsq or _hip_sumsq, clip or _hip_clip
+        self._ops = ops or HipOptimizerOps()
         self.scaler = scaler if (scaler is not None and scaler.enabled) else None
         self.amp_state = None                  # int32 [8] = mvldm_amp_state (S at [0] as fp32 bits)
         if self.scaler is not None:
             self.amp_state = torch.zeros(8, dtype=torch.int32, device=dev)
             self.amp_state[0:1].view(torch.float32).fill_(float(self.scaler.init_scale))
-        self._amp = amp or HipAmpOps()
         self._pending = []
         # ---- 16-bit parameter gather (round 6).  What the next forward needs from the other ranks is their slice of the 16-bit weight
         # PACKS -- a per-layer permutation of RNE_16(master) -- not their fp32 masters (ZeRO-1: a master is only ever updated by its
@@ -1022,11 +1021,12 @@ class DistributedOptimizer:
         # does in a training loop.  The byte counters are plain integers and always on.
         self.account_comm = False
 
-    # ---- learning rate (LinearLR: factor after `step_count` scheduler steps) ----
+    # ---- learning rate (LinearLR: factor after `n` scheduler steps; `lr()`: after the `step_count` taken so far) ----
+    def _lr_after(self, n: int) -> float:
+        return self.lr0 if self.sched is None else self.lr0 * linear_lr_factor(n, **self.sched.get("kwargs", {}))
+
     def lr(self) -> float:
-        if self.sched is None:
-            return self.lr0
-        return self.lr0 * linear_lr_factor(self.step_count, **self.sched.get("kwargs", {}))
+        return self._lr_after(self.step_count)
 
     # ---- gradient exchange ----
     def reduce_bucket(self, k: int, stream=None):
@@ -1047,17 +1047,21 @@ class DistributedOptimizer:
         else:                                           # RCCL, in place: recvbuff == sendbuff + rank * recvcount
             self._pending.append(dist.reduce_scatter_tensor(g[oa:ob], g[a:b], op=dist.ReduceOp.SUM, group=self.group, async_op=True))
 
-    def wait(self):
-        timed = self.account_comm and bool(self._pending) and self.flat.grad.is_cuda
+    def _wait(self, works):
+        """make the compute stream wait for outstanding collectives; under `account_comm` the wait is timed as exposed communication"""
+        timed = self.account_comm and bool(works) and self.flat.grad.is_cuda
         if timed:
             e0 = torch.cuda.Event(enable_timing=True)
             e0.record()
-        for w in self._pending:
+        for w in works:
             w.wait()
         if timed:
             e1 = torch.cuda.Event(enable_timing=True)
             e1.record()
             self._exposed.append((e0, e1))
+
+    def wait(self):
+        self._wait(self._pending)
         self._pending = []
 
     def comm_stats(self, reset: bool = True) -> dict:
@@ -1091,89 +1095,76 @@ class DistributedOptimizer:
         a checkpoint, a state dict, an EMA switched on later.  A no-op while the masters are exact."""
         if self.masters_exact or not self.collective:
             return
-        import torch.distributed as dist
-        p = self.flat.flat
         self.flat.wait_readers()
-        if dist.get_backend(self.group) == "gloo":
-            for (a, b) in self.buckets:
-                n = (b - a) // self.world
-                dist.all_gather([p[a + r * n:a + (r + 1) * n] for r in range(self.world)], p[a + self.rank * n:a + (self.rank + 1) * n].clone(),
-                                group=self.group)
-        else:
-            for (a, b), (oa, ob) in zip(self.buckets, self.owned):
-                dist.all_gather_into_tensor(p[a:b], p[oa:ob], group=self.group)
+        self._all_gather(self.flat.flat, range(len(self.buckets)))
         self.masters_exact = True
+
+    def _all_gather(self, src: torch.Tensor, ks, async_op: bool = False) -> list:
+        """all-gather, in place, every rank's owned slice of the buckets `ks` of `src` (the flat parameters or their 16-bit copy);
+        -> the outstanding works when `async_op`"""
+        import torch.distributed as dist
+        gloo, es = dist.get_backend(self.group) == "gloo", 1
+        if gloo and src.element_size() == 2:
+            src, es = src.view(torch.uint8), 2          # (gloo moves bytes: the 16-bit slices travel as uint8)
+        works = []
+        for k in ks:
+            (a, b), (oa, ob) = self.buckets[k], self.owned[k]
+            if gloo:                                    # list form: one output per rank, the owned slice sent from a copy
+                n = ob - oa
+                works.append(dist.all_gather([src[es * (a + r * n):es * (a + (r + 1) * n)] for r in range(self.world)],
+                                             src[es * oa:es * ob].clone(), group=self.group, async_op=async_op))
+            else:                                       # RCCL, in place: sendbuff == recvbuff + rank * sendcount
+                works.append(dist.all_gather_into_tensor(src[a:b], src[oa:ob], group=self.group, async_op=async_op))
+        return works if async_op else []
 
     def step(self):
         """clip (global norm over ALL ranks' slices) + AdamW on the owned slices + all-gather of the weights"""
         self.wait()
         self.flat.wait_readers()          # a re-pack running ahead on the side stream reads the parameters this step overwrites
         g, p = self.flat.grad, self.flat.flat
-        amp = self.amp_state
+        amp = self.amp_state                              # (amp None: no scaler -- the same step with S = 1 and never a found-inf)
         own_sq = torch.zeros(1, dtype=torch.float32, device=g.device)
         for oa, ob in self.owned:                           # (a handful of scalars: bookkeeping, not the data path)
-            own_sq += self._sumsq(g[oa:ob]) if amp is None else self._amp.sumsq(g[oa:ob], amp)      # (scaled: the unscaled sum)
-        if self.collective:
-            import torch.distributed as dist
-            dist.all_reduce(own_sq, op=dist.ReduceOp.SUM, group=self.group)
-        if amp is None:
-            self._clip(own_sq, self.max_norm or 0.0, self.norm)     # norm[0] = total norm, norm[1] = clip coefficient
-        else:                                                       # ... and found-inf into the record
-            self._amp.clip(own_sq, self.max_norm or 0.0, self.norm, amp)
-        total = self.norm[0]
-        self.step_count += 1
-        lr, off = self._lr_for_step(), 0
+            own_sq += self._ops.sumsq(g[oa:ob], amp)              # (under the scaler: the unscaled sum)
         dist = gloo = None
         if self.collective:
             import torch.distributed as dist
             gloo = dist.get_backend(self.group) == "gloo"
+            dist.all_reduce(own_sq, op=dist.ReduceOp.SUM, group=self.group)
+        self._ops.clip(own_sq, self.max_norm or 0.0, self.norm, amp)      # norm[0] = total norm, norm[1] = clip coefficient; found-inf into the record
+        total = self.norm[0]
+        self.step_count += 1
+        lr, off = self._lr_after(self.step_count - 1), 0    # the factor in force for optimizer step t (1-based) is the one after t-1 scheduler steps
         works = []
         g16 = self.gather_dtype is not None
         if g16 and self._p16 is None:
             self._init_gather16()
-        for (a, b), (oa, ob) in zip(self.buckets, self.owned):
+        src = self._p16 if g16 else p                       # what the other ranks receive
+        for k, (oa, ob) in enumerate(self.owned):
             n = ob - oa
-            if amp is None:
-                self._update(p[oa:ob], g[oa:ob], self.exp_avg[off:off + n], self.exp_avg_sq[off:off + n], lr, self.betas, self.eps,
-                             self.weight_decay, self.step_count, self.norm)
-            else:
-                self._amp.update(p[oa:ob], g[oa:ob], self.exp_avg[off:off + n], self.exp_avg_sq[off:off + n], lr, self.betas, self.eps,
-                                 self.weight_decay, self.norm, amp)
+            self._ops.update(p[oa:ob], g[oa:ob], self.exp_avg[off:off + n], self.exp_avg_sq[off:off + n], lr, self.betas, self.eps,
+                             self.weight_decay, self.step_count, self.norm, amp)
             off += n
             if g16:
                 self._p16[oa:ob].copy_(p[oa:ob])             # RNE to the pack type
             if self.collective and not gloo:
-                # in place (sendbuff == recvbuff + rank * sendcount), issued as soon as THIS bucket's slice is updated: RCCL's
-                # stream picks up behind the AdamW kernel just enqueued, so the gather of bucket k runs under the update of k+1
-                src = self._p16 if g16 else p
-                works.append(dist.all_gather_into_tensor(src[a:b], src[oa:ob], group=self.group, async_op=True))
-                self.bytes_gathered += (b - a) * (2 if g16 else 4)
+                # issued as soon as THIS bucket's slice is updated: RCCL's stream picks up behind the AdamW kernel just enqueued, so
+                # the gather of bucket k runs under the update of k+1
+                works += self._all_gather(src, [k], async_op=True)
         if amp is not None:         # after every bucket's AdamW launch (they read the flag and the step count it advances)
             sc = self.scaler
-            self._amp.update_scale(amp, sc.growth_factor, sc.backoff_factor, sc.growth_interval)
-        if self.collective and gloo:
-            src, es = (self._p16.view(torch.uint8), 2) if g16 else (p, 1)      # (gloo moves bytes: the 16-bit slices travel as uint8)
-            for (a, b) in self.buckets:
-                n = (b - a) // self.world
-                dist.all_gather([src[es * (a + r * n):es * (a + (r + 1) * n)] for r in range(self.world)],
-                                src[es * (a + self.rank * n):es * (a + (self.rank + 1) * n)].clone(), group=self.group)
-                self.bytes_gathered += (b - a) * (2 if g16 else 4)
+            self._ops.update_scale(amp, sc.growth_factor, sc.backoff_factor, sc.growth_interval)
+        if self.collective:
+            if gloo:
+                self._all_gather(src, range(len(self.buckets)))
+            self.bytes_gathered += sum(b - a for a, b in self.buckets) * src.element_size()
         small = None
         if g16 and self._direct_idx.numel():
             # the fp32-consumed parameters, exactly: every rank contributes the elements it owns, zeros elsewhere; integer sum
             small = p.index_select(0, self._direct_idx).view(torch.int32) * self._direct_own
             dist.all_reduce(small, op=dist.ReduceOp.SUM, group=self.group)
             self.bytes_gathered += small.numel() * 4
-        timed = self.account_comm and bool(works) and p.is_cuda
-        if timed:
-            e0 = torch.cuda.Event(enable_timing=True)
-            e0.record()
-        for w in works:
-            w.wait()
-        if timed:
-            e1 = torch.cuda.Event(enable_timing=True)
-            e1.record()
-            self._exposed.append((e0, e1))
+        self._wait(works)
         if g16:
             for (a, b), (oa, ob) in zip(self.buckets, self.owned):     # the other ranks' slices, widened (exact: 16-bit -> fp32)
                 if oa > a:
@@ -1232,12 +1223,6 @@ class DistributedOptimizer:
         self.amp_state[0:1].view(torch.float32).fill_(float(sd["scale"]))
         self.amp_state[1:2].fill_(int(sd["_growth_tracker"]))
 
-    def _lr_for_step(self) -> float:
-        # the factor in force for optimizer step t (1-based) is the one after t-1 scheduler steps
-        if self.sched is None:
-            return self.lr0
-        return self.lr0 * linear_lr_factor(self.step_count - 1, **self.sched.get("kwargs", {}))
-
 
 def make_buckets(numel: int, world: int, bucket_elems: int) -> List[Tuple[int, int]]:
     """contiguous [a, b) ranges covering [0, numel), every length a multiple of world*4 (numel is padded by the caller's
@@ -1254,42 +1239,24 @@ def make_buckets(numel: int, world: int, bucket_elems: int) -> List[Tuple[int, i
     return out
 
 
-def _hip_sumsq(g: torch.Tensor) -> torch.Tensor:
-    n = ops.grad_norm(g, 0.0)
-    return n[2:3].clone()
-
-
-def _hip_clip(sumsq: torch.Tensor, max_norm: float, norm_out: torch.Tensor):
-    """total norm + clip coefficient from an (all-reduced) sum of squares: the HIP kernel with an empty buffer"""
-    ws = ops.workspace(1024 * 8, sumsq.device, "norm")
-    L.check(L.load().mvldm_grad_norm(sumsq.data_ptr(), 0, sumsq.data_ptr(), max_norm, norm_out.data_ptr(), ws.data_ptr(), ops.stream()))
-
-
-def _hip_adamw(p, g, m, v, lr, betas, eps, wd, step, norm):
-    ops.adamw_step(p, g, m, v, lr, betas, eps, wd, step, 1.0, norm)
-
-
-class HipAmpOps:
-    """the loss scaler's four operations on the device record `state` (mvldm_amp_state) -- the HIP kernels.  The CPU tests inject an
-    object with the same methods written in torch (tests/test_grad_scaler_cpu.py)."""
+class HipOptimizerOps:
+    """the device operations of one optimizer step -- the HIP kernels.  `state`: the loss scaler's device record (mvldm_amp_state) or
+    None.  The CPU tests inject an object with the same methods written in torch (tests/torch_optimizer_ops.py)."""
 
     @staticmethod
-    def sumsq(g: torch.Tensor, state: torch.Tensor) -> torch.Tensor:
-        """unscaled sum of squares of a slice of the scaled gradient (fp32 [1])"""
-        n = ops.grad_norm_amp(g, 0.0, state)
-        return n[2:3].clone()
+    def sumsq(g: torch.Tensor, state) -> torch.Tensor:
+        """(unscaled) sum of squares of a slice of the gradient (fp32 [1])"""
+        return ops.grad_norm(g, 0.0, amp_state=state)[2:3].clone()
 
     @staticmethod
-    def clip(sumsq: torch.Tensor, max_norm: float, norm_out: torch.Tensor, state: torch.Tensor):
+    def clip(sumsq: torch.Tensor, max_norm: float, norm_out: torch.Tensor, state):
         """total norm + clip coefficient from the (all-reduced, unscaled) sum of squares; found-inf = it is not finite"""
-        ws = ops.workspace(1024 * 8, sumsq.device, "norm")
-        L.check(L.load().mvldm_grad_norm_amp(sumsq.data_ptr(), 0, sumsq.data_ptr(), max_norm, norm_out.data_ptr(), state.data_ptr(),
-                                             ws.data_ptr(), ops.stream()))
+        ops.clip_from_sumsq(sumsq, max_norm, norm_out, state)
 
     @staticmethod
-    def update(p, g, m, v, lr, betas, eps, wd, norm, state):
-        """AdamW on g * clip / S with the record's step count; nothing moves on found-inf"""
-        ops.adamw_step_amp(p, g, m, v, lr, state, betas, eps, wd, 1.0, norm)
+    def update(p, g, m, v, lr, betas, eps, wd, step, norm, state):
+        """AdamW on g * clip [/ S, with the record's step count instead of `step`; nothing moves on found-inf]"""
+        ops.adamw_step(p, g, m, v, lr, betas, eps, wd, step, 1.0, norm, state)
 
     @staticmethod
     def update_scale(state, growth_factor, backoff_factor, growth_interval):

@@ -10,6 +10,7 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 
 from mv_ldm_amd.dist import gather_counts, max_over_ranks, shard_scenes
+from torch_optimizer_ops import TorchOptimizerOps
 
 
 def _free_port():
@@ -128,22 +129,6 @@ def test_two_ranks_together_produce_exactly_the_frames_of_one():
 
 
 # ---- DDP training: bucketed reduce-scatter / sharded AdamW / all-gather (training row) ---------------------
-def _torch_update(p, g, m, v, lr, betas, eps, wd, step, norm):
-    """test stand-in for mvldm_adamw_step (same arithmetic in torch; there is no CPU product path)"""
-    gi = g * norm[1]
-    p.mul_(1 - lr * wd)
-    m.mul_(betas[0]).add_(gi, alpha=1 - betas[0])
-    v.mul_(betas[1]).addcmul_(gi, gi, value=1 - betas[1])
-    bc1, bc2 = 1 - betas[0] ** step, 1 - betas[1] ** step
-    p.addcdiv_(m, v.sqrt() / bc2 ** 0.5 + eps, value=-lr / bc1)
-
-
-def _torch_clip(sumsq, max_norm, norm_out):
-    total = sumsq.sqrt()
-    norm_out[0:1] = total
-    norm_out[1:2] = torch.clamp(max_norm / (total + 1e-6), max=1.0) if max_norm > 0 else 1.0
-
-
 def _grad_mask(flat):
     """1 at the positions parameters occupy, 0 in the alignment gaps / tail padding (real gradients never touch those)"""
     m = torch.zeros(flat.numel)
@@ -165,8 +150,7 @@ def _ddp_worker(rank, world, port, q):
     model.pretrained_from = None
     flat = _flat_padded(model, world)
     opt = DistributedOptimizer(flat, OptimizerCfg(lr=1e-2, scheduler={"name": "LinearLR", "kwargs": {"start_factor": 0.5, "total_iters": 2}}),
-                               world, rank, bucket_bytes=4096, max_norm=0.1, update=_torch_update,
-                               sumsq=lambda g: (g.double() ** 2).sum().float().reshape(1), clip=_torch_clip)
+                               world, rank, bucket_bytes=4096, max_norm=0.1, ops=TorchOptimizerOps())
     assert len(opt.buckets) > 3 and all((b - a) % (world * 4) == 0 for a, b in opt.buckets)
     for step in range(3):
         g = torch.Generator().manual_seed(100 * step + rank)
@@ -228,8 +212,8 @@ def _g16_worker(rank, world, port, q):
         model = _toy_model()
         model.pretrained_from = None
         flat = _flat_padded(model, world)
-        opt = DistributedOptimizer(flat, OptimizerCfg(lr=1e-2, scheduler=None), world, rank, bucket_bytes=4096, max_norm=0.1, update=_torch_update,
-                                   sumsq=lambda g: (g.double() ** 2).sum().float().reshape(1), clip=_torch_clip, gather_dtype=gd)
+        opt = DistributedOptimizer(flat, OptimizerCfg(lr=1e-2, scheduler=None), world, rank, bucket_bytes=4096, max_norm=0.1, ops=TorchOptimizerOps(),
+                                   gather_dtype=gd)
         assert (opt.gather_dtype is not None) == (gd is not None)
         for step in range(3):
             g = torch.Generator().manual_seed(100 * step + rank)

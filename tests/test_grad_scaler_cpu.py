@@ -1,7 +1,7 @@
 """CPU: f16 dynamic loss scaling of the training path (`GradScalerCfg`, DistributedOptimizer's scaler) against torch's own
 `torch.amp.GradScaler` under Lightning's automatic optimisation (`16-mixed`): scale / growth tracker / skip decisions, AdamW's step
 count, the weights, the LR schedule; the ZeRO-1 skip on gloo world 2; the `GradScaler.state_dict()` round trip.  The scaler's four
-device operations are injected in torch form (`TorchAmpOps`: the arithmetic of the HIP kernels in train_misc.hip)."""
+device operations are injected in torch form (tests/torch_optimizer_ops.py: the arithmetic of the HIP kernels in train_misc.hip)."""
 import os
 import socket
 
@@ -11,48 +11,9 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
+from torch_optimizer_ops import TorchOptimizerOps
+
 GRAD_ENABLED = True       # tests/conftest.py::_grad_mode: the torch reference runs scaler.scale(loss).backward()
-
-
-class TorchAmpOps:
-    """test stand-in for HipAmpOps (mvldm_grad_norm_amp / mvldm_adamw_step_amp / mvldm_amp_update) on the int32 [8] record
-    (mvldm_amp_state: [0] S as fp32 bits, [1] growth tracker, [2] AdamW steps taken, [3] found-inf, [4] skipped steps)"""
-
-    @staticmethod
-    def _inv(state):
-        return float(torch.tensor(1.0 / float(state[0:1].view(torch.float32)[0]), dtype=torch.float32))
-
-    @staticmethod
-    def sumsq(g, state):
-        inv = TorchAmpOps._inv(state)
-        return ((g.double() ** 2).sum() * inv * inv).float().reshape(1)
-
-    @staticmethod
-    def clip(sumsq, max_norm, norm_out, state):
-        total = sumsq.sqrt()
-        norm_out[0:1] = total
-        norm_out[1:2] = torch.clamp(max_norm / (total + 1e-6), max=1.0) if max_norm > 0 else 1.0
-        state[3] = 0 if bool(torch.isfinite(sumsq).all()) else 1
-
-    @staticmethod
-    def update(p, g, m, v, lr, betas, eps, wd, norm, state):
-        if int(state[3]):
-            return
-        step = int(state[2]) + 1
-        gi = g * TorchAmpOps._inv(state) * norm[1]
-        p.mul_(1 - lr * wd)
-        m.mul_(betas[0]).add_(gi, alpha=1 - betas[0])
-        v.mul_(betas[1]).addcmul_(gi, gi, value=1 - betas[1])
-        bc1, bc2 = 1 - betas[0] ** step, 1 - betas[1] ** step
-        p.addcdiv_(m, v.sqrt() / bc2 ** 0.5 + eps, value=-lr / bc1)
-
-    @staticmethod
-    def update_scale(state, growth_factor, backoff_factor, growth_interval):
-        found = int(state[3])
-        scale = state[0:1].view(torch.float32)
-        torch._amp_update_scale_(scale, state[1:2], torch.tensor([float(found)]), growth_factor, backoff_factor, growth_interval)
-        state[4 if found else 2] += 1
-        state[3] = 0
 
 
 def _model():
@@ -75,7 +36,7 @@ def _make_opt(model, world=1, rank=0, **scaler_kw):
     flat = _flat_padded(model, world)
     sched = {"name": "LinearLR", "kwargs": {"start_factor": 0.5, "total_iters": 4}}
     opt = DistributedOptimizer(flat, OptimizerCfg(lr=1e-2, scheduler=sched), world, rank, bucket_bytes=256, max_norm=0.1,
-                               scaler=GradScalerCfg(**scaler_kw), amp=TorchAmpOps())
+                               scaler=GradScalerCfg(**scaler_kw), ops=TorchOptimizerOps())
     return flat, opt
 
 

@@ -310,16 +310,25 @@ def test_adamw_and_gradient_clipping_match_torch(ops):
     """mvldm_adamw_step + mvldm_grad_norm against torch.optim.AdamW + clip_grad_norm_(0.1) (Lightning's
     gradient_clip_val, src/main.py:131): (a) the released schedule (lr 2e-5, LinearLR warm-up from 5e-4 over 200 steps,
     baseline.yaml:62-73) -- there the update (~1e-8) is below fp32 resolution of O(1) weights, so the weights themselves are
-    compared; (b) lr 1e-2 without warm-up, where the UPDATE is compared"""
+    compared; (b) lr 1e-2 without warm-up, where the UPDATE is compared.
+    Each on a buffer the scalar kernel takes (n = 10007) and on one the 16-byte kernel takes (n % 4 == 0, aligned), without a loss
+    scaler's record and with one (S = 2^10, the gradient handed over as S x g; same torch reference: the record's own step count,
+    1/S and the unscaled norm must give what the plain step gives).  With a record, a 7th step whose gradient holds an inf: found_inf
+    is set, p / m / v stay bit-identical, and mvldm_amp_update counts a skip, backs S off and leaves AdamW's step count alone."""
     from mv_ldm_amd.train import linear_lr_factor
-    n = 10007
-    for lr0, warm in ((2e-5, True), (1e-2, False)):
+    S = 2.0 ** 10
+    for n, scaled, (lr0, warm) in [(n, sc, sched) for n in (10007, 1 << 16) for sc in (False, True) for sched in ((2e-5, True), (1e-2, False))]:
         g = G(38)
         p0 = torch.randn(n, generator=g)
         ref = torch.nn.Parameter(p0.clone())
         opt = torch.optim.AdamW([ref], lr=lr0)
         sch = torch.optim.lr_scheduler.LinearLR(opt, start_factor=5e-4, total_iters=200) if warm else None
         p, m, v = p0.clone().cuda(), torch.zeros(n, device="cuda"), torch.zeros(n, device="cuda")
+        assert all(t.data_ptr() % 16 == 0 for t in (p, m, v))
+        state = None                    # mvldm_amp_state: [0] S (fp32 bits), [1] growth tracker, [2] AdamW steps, [3] found_inf, [4] skipped
+        if scaled:
+            state = torch.zeros(8, dtype=torch.int32, device="cuda")
+            state[0:1].view(torch.float32).fill_(S)
         for step in range(1, 7):
             grad = torch.randn(n, generator=g) * (0.01 if step % 2 else 1e-4)
             ref.grad = grad.clone()
@@ -330,14 +339,28 @@ def test_adamw_and_gradient_clipping_match_torch(ops):
             opt.step()
             if warm:
                 sch.step()
-            gg = grad.cuda()
-            norm = ops.grad_norm(gg, 0.1)
+            gg = (grad * S).cuda() if scaled else grad.cuda()
+            assert gg.data_ptr() % 16 == 0
+            norm = ops.grad_norm(gg, 0.1, amp_state=state)
             assert abs(float(norm[0]) - float(total)) < 1e-5 * float(total)
             assert abs(float(norm[1]) - min(1.0, 0.1 / (float(total) + 1e-6))) < 1e-5
-            ops.adamw_step(p, gg, m, v, lr, step=step, clip=norm)
-            assert relerr(p, ref.data) < 1e-6
+            ops.adamw_step(p, gg, m, v, lr, step=step, clip=norm, amp_state=state)     # (with a record `step` is not what counts)
+            if scaled:
+                assert state.tolist()[1:5] == [step - 1, step - 1, 0, 0]
+                ops.amp_update(state, 2.0, 0.5, 2000)
+            assert relerr(p, ref.data) < 1e-6, (n, scaled, lr0, step)
         if not warm:
-            assert relerr(p - p0.cuda(), ref.data - p0) < 2e-5
+            assert relerr(p - p0.cuda(), ref.data - p0) < 2e-5, (n, scaled)
+        if scaled:
+            gg = (torch.randn(n, generator=g) * 0.01 * S).cuda()
+            gg[n // 2] = float("inf")
+            before = [t.clone() for t in (p, m, v)]
+            norm = ops.grad_norm(gg, 0.1, amp_state=state)
+            assert state.tolist()[1:5] == [6, 6, 1, 0] and not math.isfinite(float(norm[0]))
+            ops.adamw_step(p, gg, m, v, lr0, step=7, clip=norm, amp_state=state)
+            assert all(torch.equal(t, t0) for t, t0 in zip((p, m, v), before)), (n, lr0)
+            ops.amp_update(state, 2.0, 0.5, 2000)
+            assert state.tolist()[1:5] == [0, 6, 0, 1] and float(state[0:1].view(torch.float32)) == S * 0.5
 
 
 # ------------------------------------------------------------------------------------------------ production shapes

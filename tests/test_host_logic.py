@@ -98,13 +98,14 @@ def test_scale_lr_multiplies_by_the_effective_batch_size_or_refuses():
     from torch import nn
     from mv_ldm_amd.train import DistributedOptimizer, FlatParams, OptimizerCfg
     flat = FlatParams(nn.Linear(4, 4))
-    noop = lambda *a, **k: None
+    from torch_optimizer_ops import TorchOptimizerOps
+    ops = TorchOptimizerOps()
     with pytest.raises(ValueError, match="effective_batch_size"):
-        DistributedOptimizer(flat, OptimizerCfg(lr=2e-5, scale_lr=True), update=noop, sumsq=noop, clip=noop)
-    opt = DistributedOptimizer(flat, OptimizerCfg(lr=2e-5, scale_lr=True, scheduler=None), update=noop, sumsq=noop, clip=noop,
+        DistributedOptimizer(flat, OptimizerCfg(lr=2e-5, scale_lr=True), ops=ops)
+    opt = DistributedOptimizer(flat, OptimizerCfg(lr=2e-5, scale_lr=True, scheduler=None), ops=ops,
                                effective_batch_size=2 * 8 * 4)
     assert abs(opt.lr() - 2e-5 * 64) < 1e-12
-    assert abs(DistributedOptimizer(flat, OptimizerCfg(lr=2e-5, scheduler=None), update=noop, sumsq=noop, clip=noop).lr() - 2e-5) < 1e-15
+    assert abs(DistributedOptimizer(flat, OptimizerCfg(lr=2e-5, scheduler=None), ops=ops).lr() - 2e-5) < 1e-15
 
 
 def test_weight_epochs_are_per_module():
