@@ -1223,6 +1223,139 @@ class DistributedOptimizer:
         self.amp_state[0:1].view(torch.float32).fill_(float(sd["scale"]))
         self.amp_state[1:2].fill_(int(sd["_growth_tracker"]))
 
+    # ---- checkpoint: the moments in `torch.optim.AdamW.state_dict()`'s layout, the LR position in `LinearLR.state_dict()`'s ----
+    def _indexed_params(self) -> Tuple[int, List[Tuple[int, str, nn.Parameter]]]:
+        """(number of parameters of the module, [(i, name, p)] of the TRAINED ones): i = the position in
+        `list(module.parameters())`, i.e. the index torch gives the parameter when the reference hands `self.denoiser.parameters()`
+        to AdamW (diffusion_wrapper.py:1115)"""
+        named = list(self.flat.module.named_parameters())
+        index = {id(p): (i, n) for i, (n, p) in enumerate(named)}
+        return len(named), sorted((index[id(p)] + (p,) for p in self.flat.params), key=lambda t: t[0])
+
+    def _consolidated(self, own: torch.Tensor) -> torch.Tensor:
+        """a full-size flat buffer holding every rank's owned slices of a moment (`own`: this rank's, bucket after bucket)"""
+        full = torch.zeros(self.flat.numel, dtype=torch.float32, device=own.device)
+        off = 0
+        for oa, ob in self.owned:
+            full[oa:ob].copy_(own[off:off + ob - oa])
+            off += ob - oa
+        if self.collective:
+            self._all_gather(full, range(len(self.buckets)))
+        return full
+
+    def state_dict(self) -> dict:
+        """The AdamW state in the layout of `torch.optim.AdamW(module.parameters()).state_dict()`: `state[i]` = {"step" (0-d fp32:
+        `adam_step`), "exp_avg", "exp_avg_sq"} (fp32, parameter-shaped, on the CPU) for exactly the trained parameters -- the ones
+        outside the flat buffer never get a gradient in the reference either, and torch keeps no state for those -- and one param
+        group with every key torch's AdamW needs to step after `load_state_dict` (`lr` = the current `lr()`, `initial_lr` = the base
+        LR).  The ZeRO-1 shards are consolidated: one moment at a time goes through a temporary full-size flat buffer (owned slices
+        placed, all-gathered in place, cut per parameter; alignment gaps and tail padding dropped), so the peak extra device memory
+        is one flat buffer.  A COLLECTIVE when the optimizer is (`collective`): every rank must call it, every rank gets the same dict."""
+        n_all, trained = self._indexed_params()
+        step = float(self.adam_step)
+        state = {i: {"step": torch.tensor(step, dtype=torch.float32)} for i, _, _ in trained}
+        for key in ("exp_avg", "exp_avg_sq"):
+            full = self._consolidated(getattr(self, key))
+            for i, _, p in trained:
+                o = self.flat.offset[id(p)]
+                state[i][key] = full[o:o + p.numel()].view(p.shape).to("cpu", copy=True)
+            del full          # (before the second moment's buffer is allocated)
+        group = {"lr": self.lr(), "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.weight_decay, "amsgrad": False,
+                 "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None,
+                 "decoupled_weight_decay": True, "initial_lr": self.lr0, "params": list(range(n_all))}
+        return {"state": state, "param_groups": [group]}
+
+    def _scatter_owned(self, dst: torch.Tensor, starts: List[int], local: List[int], o: int, src: torch.Tensor):
+        """copy the intersections of the flat range [o, o + src.numel()) with this rank's owned slices from `src` into `dst`"""
+        import bisect
+        e = o + src.numel()
+        k = max(0, bisect.bisect_right(starts, o) - 1)
+        while k < len(self.owned) and self.owned[k][0] < e:
+            oa, ob = self.owned[k]
+            lo, hi = max(o, oa), min(e, ob)
+            if lo < hi:
+                dst[local[k] + lo - oa:local[k] + hi - oa].copy_(src[lo - o:hi - o])
+            k += 1
+
+    def load_state_dict(self, sd: dict, strict: bool = True):
+        """Load an AdamW state dict -- `state_dict()`'s own, from any world size / rank / bucket size, or a real
+        `torch.optim.AdamW.state_dict()` over the same `module.parameters()` (a Lightning checkpoint's `optimizer_states[0]`) -- into
+        this rank's shards: per parameter only the intersections of its flat range with the owned slices are copied, gaps and padding
+        are zero.  No collective.
+        * every state tensor must have its parameter's shape (2-D <-> 4-D of equal size is reshaped, as `checkpoint.load_module_state`
+          does for 1x1 convs): a mismatch raises ValueError naming the parameter.  The index -> parameter map is positional, so this
+          check is what guards against a foreign checkpoint whose parameter order differs from `module.parameters()` here.
+        * all `step` values must be equal (the fused kernel has ONE step count) and become `adam_step`; unequal -> ValueError.
+        * a trained parameter without an entry while others have one -> ValueError; under `strict=False` it gets zero moments and the
+          shared step count (torch would start such a parameter at step 0: its bias correction differs for the first few hundred
+          steps).  State for a parameter that is not trained here -> ValueError, ignored under `strict=False`.
+        * an empty `state` (a fresh optimizer): zero moments, `adam_step` = 0.
+        * the LIVE optimizer's betas / eps / weight_decay / LR configuration win; a saved value that differs is only warned about
+          (changing the LR on resume is legitimate)."""
+        import warnings
+        state = dict(sd.get("state", {}))
+        _, trained = self._indexed_params()
+        mine = {i for i, _, _ in trained}
+        foreign = sorted(k for k in state if k not in mine)
+        if foreign:
+            msg = f"optimizer state for {len(foreign)} parameter index(es) that are not trained here (first: {foreign[:3]})"
+            if strict:
+                raise ValueError(msg + ": the checkpoint's parameter order is not this module's")
+            warnings.warn(msg + ": ignored")
+        have = [(i, n, p) for i, n, p in trained if i in state]
+        missing = [n for i, n, _ in trained if i not in state]
+        if have and missing:
+            msg = f"optimizer state misses {len(missing)} trained parameter(s) (first: {missing[:3]})"
+            if strict:
+                raise ValueError(msg)
+            warnings.warn(msg + ": zero moments, the shared step count")
+        steps = {float(state[i]["step"]) for i, _, _ in have}
+        if len(steps) > 1:
+            raise ValueError(f"optimizer state holds different step counts {sorted(steps)[:4]}: the fused AdamW step has one")
+        tensors = {}
+        for i, n, p in have:
+            for key in ("exp_avg", "exp_avg_sq"):
+                t = state[i][key]
+                if tuple(t.shape) != tuple(p.shape) and not (t.numel() == p.numel() and {t.dim(), p.dim()} == {2, 4}):
+                    raise ValueError(f"optimizer state {key} of parameter {i} ({n}) has shape {tuple(t.shape)}, expected {tuple(p.shape)}: "
+                                     "not this module's parameter order?")
+                tensors[i, key] = t
+        groups = sd.get("param_groups") or [{}]
+        saved = groups[0]
+        live = {"betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.weight_decay}
+        live["initial_lr" if "initial_lr" in saved or self.sched is not None else "lr"] = self.lr0
+        for k, v in live.items():
+            if k in saved and (tuple(saved[k]) if k == "betas" else saved[k]) != v:
+                warnings.warn(f"optimizer checkpoint has {k} = {saved[k]}, this optimizer keeps its own {v}")
+        starts, local, off = [oa for oa, _ in self.owned], [], 0
+        for oa, ob in self.owned:
+            local.append(off)
+            off += ob - oa
+        for key in ("exp_avg", "exp_avg_sq"):
+            dst = getattr(self, key)
+            dst.zero_()
+            for i, _, p in have:
+                self._scatter_owned(dst, starts, local, self.flat.offset[id(p)], tensors[i, key].reshape(-1).to(torch.float32))
+        self.adam_step = int(round(steps.pop())) if steps else 0
+
+    def lr_scheduler_state_dict(self) -> Optional[dict]:
+        """the LR position in `torch.optim.lr_scheduler.LinearLR.state_dict()`'s keys (None without a scheduler)"""
+        if self.sched is None:
+            return None
+        kw = self.sched.get("kwargs", {})
+        return {"start_factor": kw.get("start_factor", 1.0 / 3), "end_factor": kw.get("end_factor", 1.0), "total_iters": kw.get("total_iters", 5),
+                "base_lrs": [self.lr0], "last_epoch": self.step_count, "_step_count": self.step_count + 1, "_last_lr": [self.lr()]}
+
+    def load_lr_scheduler_state_dict(self, sd: dict):
+        """`last_epoch` becomes `step_count` (the scheduler steps taken); the live LinearLR configuration wins, a differing saved one
+        is warned about"""
+        import warnings
+        mine = self.lr_scheduler_state_dict() or {"base_lrs": [self.lr0]}
+        for k in ("start_factor", "end_factor", "total_iters", "base_lrs"):
+            if k in sd and k in mine and (list(sd[k]) if k == "base_lrs" else sd[k]) != mine[k]:
+                warnings.warn(f"lr scheduler checkpoint has {k} = {sd[k]}, this optimizer keeps its own {mine[k]}")
+        self.step_count = int(sd["last_epoch"])
+
 
 def make_buckets(numel: int, world: int, bucket_elems: int) -> List[Tuple[int, int]]:
     """contiguous [a, b) ranges covering [0, numel), every length a multiple of world*4 (numel is padded by the caller's
@@ -1535,9 +1668,145 @@ class MVLDMTrainer:
         self.flat.wait_readers()
         out = self.denoiser.load_state_dict(state_dict, strict=strict)
         self.opt.masters_exact = True             # (every rank has just loaded the same exact values)
+        if self.opt._p16 is not None:             # the 16-bit gather's copy of the parameters follows the masters
+            self.opt._p16.copy_(self.flat.flat)
         self._weights_gen += 1
         self.flat.bump()
         return out
+
+    # ---- the whole trainer state: a checkpoint in the reference's (Lightning) container layout -----------------------
+    _SCALER_KEYS = ("MixedPrecision", "MixedPrecisionPlugin", "mv_ldm_amd_grad_scaler")
+
+    def _at_step_boundary(self, what: str):
+        if self.micro % self.cfg.accumulate_grad_batches:
+            raise RuntimeError(f"{what} in the middle of an accumulation window (micro-batch {self.micro % self.cfg.accumulate_grad_batches} of "
+                               f"{self.cfg.accumulate_grad_batches}): checkpoints are taken at optimizer-step boundaries, as Lightning does")
+
+    def _param_names(self) -> List[str]:
+        return [n for n, _ in self.denoiser.named_parameters()]
+
+    def state_dict(self, include_autoencoder: bool = False) -> dict:
+        """Everything a run needs to continue, as the plain dict Lightning writes for the reference's `DiffusionWrapper`
+        (`torch.load(..., weights_only=True)` reads it; `checkpoint.load_pipeline_checkpoint` samples from it):
+            "state_dict"        `denoiser.<key>`: the exact fp32 masters (after `sync_masters()`); `autoencoder.<key>` with
+                                `include_autoencoder`; `ema.module.<key>` / `ema.n_averaged` when the trainer keeps an EMA
+            "optimizer_states"  [`DistributedOptimizer.state_dict()`]: the ZeRO-1 shards consolidated into torch AdamW's layout
+            "lr_schedulers"     [`LinearLR.state_dict()`'s keys, `last_epoch` = the scheduler steps taken] ([] without a scheduler)
+            "global_step", "epoch" (0)
+            "MixedPrecision"    `scaler_state_dict()` (Lightning 2.x's key for its GradScaler): only an f16 trainer with the scaler on
+            "mv_ldm_amd"        {"version": 1, "adam_step", "skipped_steps", "param_names" (index order), "dtype", "world",
+                                 "accumulate_grad_batches"}
+        A COLLECTIVE for a multi-rank trainer -- it enters `sync_masters()` and the optimizer's consolidation, so every rank must call
+        it, and every rank gets the same dict (a multi-rank checkpoint equals the fp32-gather run's).  Only at an optimizer-step
+        boundary (RuntimeError inside an accumulation window).  RNG streams are not part of it (Lightning saves none either)."""
+        self._at_step_boundary("state_dict()")
+        self.sync_masters()
+        sd = {"denoiser." + k: v.detach().to("cpu", copy=True) for k, v in self.denoiser.state_dict().items()}
+        if include_autoencoder:
+            sd.update({"autoencoder." + k: v.detach().to("cpu", copy=True) for k, v in self.autoencoder.state_dict().items()})
+        if self.ema is not None:
+            sd.update({"ema." + k: v.detach().to("cpu", copy=True) for k, v in self.ema.state_dict().items()})
+        sched = self.opt.lr_scheduler_state_dict()
+        skipped = self.skipped_steps
+        out = {"state_dict": sd, "optimizer_states": [self.opt.state_dict()], "lr_schedulers": [] if sched is None else [sched],
+               "global_step": int(self.global_step), "epoch": 0}
+        if self.opt.scaler is not None:
+            out["MixedPrecision"] = self.scaler_state_dict()
+        out["mv_ldm_amd"] = {"version": 1, "adam_step": int(self.adam_step), "skipped_steps": 0 if skipped is None else int(skipped),
+                             "param_names": self._param_names(), "dtype": str(self.dtype).replace("torch.", ""), "world": int(self.world),
+                             "accumulate_grad_batches": int(self.cfg.accumulate_grad_batches)}
+        return out
+
+    def load_state_dict(self, ckpt: dict, strict: bool = True):
+        """Continue from `state_dict()`'s container -- written by any world size and bucket size; bit-identically when the world
+        size is unchanged -- or from a reference / Lightning checkpoint, which has no "mv_ldm_amd" entry and is read through the
+        same keys (`state_dict`, `optimizer_states[0]`, `lr_schedulers[0]`, `global_step`, `MixedPrecision`).  Restores the masters
+        (`load_denoiser_state_dict`: pending re-pack, 16-bit gather copy, plan invalidation), the moments and `adam_step`, the LR
+        position (`opt.step_count` = `last_epoch`), `global_step`, the scaler record with its skipped-step counter, and the EMA.
+        `autoencoder.*` entries are not read: the frozen VAE is the one the trainer was built with.  Every rank loads the same
+        file; no collective.
+        Checks: "param_names", when present, must equal the live names (ValueError); an EMA in the file but not in the trainer is
+        warned about and ignored; an EMA in the trainer but not in the file is a ValueError -- under `strict=False` it restarts from
+        the loaded weights with `n_averaged` = 0; a scaler in the trainer but no record in the file likewise (`strict=False`: the
+        configured initial scale).  The optimizer state is positional (`DistributedOptimizer.load_state_dict`): whether
+        `denoiser.parameters()` here enumerates in the order of the reference's diffusers modules is NOT pinned by a test (neither
+        library nor a real checkpoint is available to this repository) -- the per-parameter shape check is the guard."""
+        import warnings
+        from .checkpoint import split_wrapper_state
+        self._at_step_boundary("load_state_dict()")
+        meta = ckpt.get("mv_ldm_amd") or {}
+        names = meta.get("param_names")
+        if names is not None and list(names) != self._param_names():
+            live = self._param_names()
+            bad = next((i for i, (a, b) in enumerate(zip(names, live)) if a != b), min(len(names), len(live)))
+            raise ValueError(f"checkpoint parameter names differ from this denoiser's ({len(names)} vs {len(live)} names, first difference "
+                             f"at index {bad}): the optimizer state would land on other parameters")
+        parts = split_wrapper_state(ckpt["state_dict"])
+        den_sd = dict(parts["denoiser"] or parts["other"])
+        for k, dst in self.denoiser.state_dict().items():        # 1x1 convs stored as Linear weights or the reverse (checkpoint.load_module_state)
+            src = den_sd.get(k)
+            if src is not None and src.shape != dst.shape and src.numel() == dst.numel() and {src.dim(), dst.dim()} == {2, 4}:
+                den_sd[k] = src.reshape(dst.shape)
+        has_ema = any(k.startswith("module.") for k in parts["ema"])
+        if self.ema is not None and not has_ema and strict:
+            raise ValueError("the trainer keeps an EMA but the checkpoint has no `ema.module.*` tensors (strict=False restarts the average)")
+        rec = next((ckpt[k] for k in self._SCALER_KEYS if ckpt.get(k)), None)
+        adam_step = meta.get("adam_step")
+        if rec is not None and "scaler" in rec:                  # the earlier binding's record: {"scaler": GradScaler layout, "adam_step"}
+            rec, adam_step = rec["scaler"], rec.get("adam_step", adam_step)
+        if self.opt.scaler is not None and not rec and strict:
+            raise ValueError("an f16 trainer under the loss scaler, but the checkpoint has no scaler record (strict=False keeps the initial scale)")
+        self.load_denoiser_state_dict(den_sd, strict=strict)
+        opt_states = ckpt.get("optimizer_states") or []
+        if opt_states:
+            self.opt.load_state_dict(opt_states[0], strict=strict)
+        elif strict:
+            raise ValueError("the checkpoint has no optimizer state (strict=False starts the moments at zero)")
+        else:
+            self.opt.load_state_dict({"state": {}}, strict=False)
+        if adam_step is not None:
+            self.opt.adam_step = int(adam_step)
+        scheds = ckpt.get("lr_schedulers") or []
+        if scheds:
+            self.opt.load_lr_scheduler_state_dict(scheds[0])
+        elif "global_step" in ckpt:
+            self.opt.step_count = int(ckpt["global_step"])
+        self.global_step = int(ckpt.get("global_step", self.opt.step_count))
+        if self.opt.scaler is not None:
+            if rec:
+                self.load_scaler_state_dict(rec)
+            # every scheduler step is either a taken or a skipped optimizer step
+            self.opt.amp_state[4:5].fill_(int(meta.get("skipped_steps", max(0, self.opt.step_count - self.opt.adam_step))))
+        elif rec:
+            warnings.warn("the checkpoint carries a loss-scaler record; this trainer does not scale (not f16, or the scaler is off): ignored")
+        if self.ema is None:
+            if has_ema:
+                warnings.warn("the checkpoint carries EMA weights; this trainer keeps no EMA (ema_decay=None): ignored")
+        elif has_ema:
+            self.ema.load_state_dict(parts["ema"])
+        else:
+            self.ema.avg.copy_(self.flat.flat)
+            self.ema.n_averaged = 0
+
+    def save_checkpoint(self, path, include_autoencoder: bool = False):
+        """`state_dict()` written with `torch.save` by rank 0 (to a temporary file, then `os.replace`: a job killed mid-write leaves the
+        previous checkpoint intact).  Every rank must call it -- building the dict is a collective -- and the other ranks wait at a
+        barrier until the file is in place."""
+        sd = self.state_dict(include_autoencoder=include_autoencoder)
+        if self.rank == 0:
+            path = os.fspath(path)
+            tmp = f"{path}.tmp.{os.getpid()}"
+            torch.save(sd, tmp)
+            os.replace(tmp, path)
+        if self.opt.collective:
+            import torch.distributed as dist
+            dist.barrier(group=self.opt.group)
+
+    def load_checkpoint(self, path, strict: bool = True) -> dict:
+        """`load_state_dict` of a checkpoint file (every rank reads it); returns the container, for whatever else the caller stored in it"""
+        ckpt = torch.load(os.fspath(path), map_location="cpu", weights_only=True)
+        self.load_state_dict(ckpt, strict=strict)
+        return ckpt
 
     def _fresh(self, tp: TrainPlan):
         ev = tp.__dict__.pop("_repack_event", None)
