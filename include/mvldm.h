@@ -84,13 +84,13 @@ typedef struct mvldm_igemm_desc {
     int32_t act_dtype;  /* dtype of src/weight/residual */
     int32_t dst_dtype;  /* act_dtype or MVLDM_F32 */
     int32_t splitk;     /* >= 1; 0 = let the library choose (needs workspace) */
-    int32_t tile;       /* 0 = auto; else force a tile config (tests / tuning / plan-time selection): 1..11 igemm.hip tiles,
+    int32_t tile;       /* 0 = auto; else force a tile config (tests / tuning / plan-time selection): 1..11 implicit-GEMM tiles (igemm_small.hip: 1..5, igemm_large.hip: 6..8, igemm_xl.hip: 9..10, igemm_halo.hip: 11),
                            12 = persistent Linear with the epilogue pipelined under the next tile (linear_pp.hip: 1x1, one or two
                            sources, K >= 320 a multiple of 64, 16-bit in and out; any other problem is an error, not a fallback),
                            13 = persistent wide Linear (linear_pw.hip), 14 = weight-stationary Linear for K = 320 (linear_ws.hip),
-                           17 = 256 x 320 tile with the pixel halo resident in LDS (igemm.hip, round 5: one-source 3x3 / stride 1 / pad 1 convs
+                           17 = 256 x 320 tile with the pixel halo resident in LDS (igemm_halo.hip, round 5: one-source 3x3 / stride 1 / pad 1 convs
                                 on maps up to 24 pixels wide; anything else runs as tile 7, same values),
-                           18 = 192 x 128 tile with a 4-slot ring (igemm.hip; 1x1 / 3x3, no upsampling forms, no GEGLU: refused),
+                           18 = 192 x 128 tile with a 4-slot ring (igemm_xl.hip; 1x1 / 3x3, no upsampling forms, no GEGLU: refused),
                            19 = register-staged persistent Linear (linear_rs.hip, round 6: 256 x 256 tiles, 4 waves of 128 x 128, the K-steps in
                                 flight held in registers; 1x1, one or two sources, K >= 256 a multiple of 128, 16-bit in and out, bias /
                                 residual / GEGLU; any other problem is an error, not a fallback),

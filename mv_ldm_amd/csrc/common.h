@@ -98,6 +98,17 @@ template <typename T> __device__ __forceinline__ Chunk<T> load_chunk(const T* p)
 template <typename T> __device__ __forceinline__ void store_chunk(T* p, const Chunk<T>& c) {
     *reinterpret_cast<u32x4*>(p) = c.raw;
 }
+// MFMA 32x32x16 on 16-bit operands: the fragment type and the builtin (igemm_common.h adds its LDS tile policy, linear_common.h uses it as is)
+template <typename T> struct Mfma16;
+template <> struct Mfma16<bf16_t> {
+    using Frag = bf16x8;
+    static __device__ __forceinline__ f32x16 mma(Frag a, Frag b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
+};
+template <> struct Mfma16<f16_t> {
+    using Frag = f16x8;
+    static __device__ __forceinline__ f32x16 mma(Frag a, Frag b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
+};
+
 // host: should a kernel that writes `bytes` of output use streaming stores?  Outputs of half the 256 MB Infinity Cache or more;
 // MVLDM_STREAM_STORES=0 / 1 forces it (A/B knob).
 // A/B and tuning knobs of decisions already made exist in EXPERIMENT builds only (-DMVLDM_EXPERIMENTS: tools/*_probe.sh,

@@ -14,16 +14,8 @@ namespace mvldm {
 
 constexpr unsigned kLinRowNone = 0xFFFFFFFFu;      // byte offset of a row past M (lin_off turns it into kBufOob)
 
-// MFMA 32x32x16 on 16-bit operands
-template <typename T> struct LinMma;
-template <> struct LinMma<bf16_t> {
-    using Frag = bf16x8;
-    static __device__ __forceinline__ f32x16 mma(Frag a, Frag b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
-};
-template <> struct LinMma<f16_t> {
-    using Frag = f16x8;
-    static __device__ __forceinline__ f32x16 mma(Frag a, Frag b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
-};
+// MFMA 32x32x16 on 16-bit operands (common.h)
+template <typename T> using LinMma = Mfma16<T>;
 
 // one fragment (16 bytes = 8 K values of a row) from its LDS address
 template <typename T> __device__ __forceinline__ typename LinMma<T>::Frag lin_frag(const char* p) {
