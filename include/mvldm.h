@@ -28,8 +28,9 @@ extern "C" {
  * MVLDM_OP_GATHER_ROWS / MVLDM_OP_ATTN_MERGE; bits 8-9 of mvldm_wgrad_desc.accumulate select the weight-gradient kernel form.  Everything of version 2 is
  * unchanged (additive).
  * 4 (round 5): + mvldm_pack_skinny and tile 15 / k_order 2 of mvldm_igemm_fwd (the skinny-M weight-streaming GEMM); additive over 3.
- * 5 (round 6): + tile 19 of mvldm_igemm_fwd (register-staged Linear), tile 13's bits 13 / 14, mvldm_build_flags; additive over 4. */
-#define MVLDM_ABI_VERSION 6
+ * 5 (round 6): + tile 19 of mvldm_igemm_fwd (register-staged Linear), tile 13's bits 13 / 14, mvldm_build_flags; additive over 4.
+ * 7: + mvldm_image_metrics, mvldm_image_metrics_workspace_bytes; additive over 6. */
+#define MVLDM_ABI_VERSION 7
 
 typedef void* mvldm_stream_t; /* hipStream_t */
 
@@ -456,6 +457,22 @@ int mvldm_gather_rows(const void* src, void* dst, const int32_t* src_index, cons
 int mvldm_attention_merge(const void* oa, const float* lse_a, const void* ob, const float* lse_b, void* out, const int32_t* a_img,
                           const int32_t* b_img, const int32_t* out_img, int n_img, int tokens, int heads, int head_dim, int ld_a, int ld_b,
                           int ld_o, int lse_ld_a, int lse_ld_b, int dtype, mvldm_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Image metrics: PSNR and SSIM of n_img image pairs, fp32 NCHW [n_img][c][h][w] contiguous (what last_stage_decode returns and
+ * the batches carry), one launch plus a fold; psnr[n_img], ssim[n_img] fp32.
+ *   replaces  compute_psnr (src/evaluation/metrics.py:17-24): both images clipped to [0, 1], -10 log10(mean squared difference
+ *             over c h w); identical images give +inf;
+ *             compute_ssim (src/evaluation/metrics.py:58-73): skimage.metrics.structural_similarity(win_size=11,
+ *             gaussian_weights=True, channel_axis=0, data_range=1.0) per image, NOT clipped: Gaussian taps of sigma 1.5 (11, normalised),
+ *             S = (2 ux uy + C1)(2 vxy + C2) / ((ux^2 + uy^2 + C1)(vx + vy + C2)), C1 = 1e-4, C2 = 9e-4, variances scaled by 121/120 when
+ *             use_sample_covariance != 0 (skimage's default), averaged over the map cropped by 5 pixels per side and over channels.
+ * The sums are fp64 partials in `workspace` (mvldm_image_metrics_workspace_bytes; 0 for a refused shape), folded in a fixed order:
+ * no atomics, bit-identical from run to run, and an image's scores do not depend on n_img or its position.  Refused: h or w < 11,
+ * c < 1, a null pointer, a workspace that is too small. */
+size_t mvldm_image_metrics_workspace_bytes(int n_img, int c, int h, int w);
+int mvldm_image_metrics(const float* pred, const float* gt, int n_img, int c, int h, int w, int use_sample_covariance, float* psnr,
+                        float* ssim, double* workspace, size_t workspace_bytes, mvldm_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Plans: a whole forward (UNet walk, VAE decoder, DDIM step) as a flat list of the ops above with

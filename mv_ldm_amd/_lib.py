@@ -11,7 +11,7 @@ from pathlib import Path
 
 LIB_PATH = Path(__file__).resolve().parent / "csrc" / "libmvldm_hip.so"
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 F32, BF16, F16 = 0, 1, 2
 EPI_NONE, EPI_SILU, EPI_GEGLU, EPI_GELU = 0, 1, 2, 3
 RAYS_RAW, RAYS_POSITIONAL, RAYS_SRT = 0, 1, 2
@@ -225,6 +225,8 @@ SIGNATURES = {
     "mvldm_attention_merge": (C.c_int, [vp] * 8 + [C.c_int] * 10 + [vp]),
     "mvldm_ddpm_cfg_step": (C.c_int, [vp, vp, vp, vp, vp, sz, f32, vp, f32, vp]),
     "mvldm_ema_update": (C.c_int, [vp, vp, sz, f32, vp]),
+    "mvldm_image_metrics_workspace_bytes": (sz, [C.c_int] * 4),
+    "mvldm_image_metrics": (C.c_int, [vp, vp] + [C.c_int] * 5 + [vp, vp, vp, sz, vp]),
     "mvldm_nchw_to_nhwc": (C.c_int, [vp, vp] + [C.c_int] * 6 + [f32, f32, vp, vp]),
     "mvldm_ray_channels": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "mvldm_ray_encode": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp] + [C.c_int] * 4 + [vp]),

@@ -62,3 +62,10 @@ def decode_png(data: bytes) -> np.ndarray:
     rows = np.frombuffer(zlib.decompress(idat), np.uint8).reshape(h, 1 + w * c)
     assert (rows[:, 0] == 0).all()
     return rows[:, 1:].reshape(h, w, c).copy()
+
+
+def load_image(path: Union[Path, str]) -> torch.Tensor:
+    """a PNG written by `save_image` -> float32 [3, H, W] in [0, 1] (k / 255; an alpha channel is dropped): the inverse the metric
+    tool scores PNG trees with (src/evaluation/metric_computer.py reads the same files through torchvision)"""
+    pixels = decode_png(Path(path).read_bytes())
+    return torch.from_numpy(pixels[..., :3]).permute(2, 0, 1).float() / 255

@@ -1,0 +1,130 @@
+"""Image quality of sampled views on the device: the counterpart of `src/evaluation/metrics.py` (`compute_psnr` :17-24,
+`compute_ssim` :58-73) and of `metric_computer.test_step`, which walks the PNG tree `test_step` wrote.
+
+The reference pulls every image to the host and runs skimage one image at a time; here both scores of a whole batch come from
+one launch of `csrc/metrics.hip` (`ops.image_metrics`).  LPIPS / DISTS / FID need pretrained networks and are not provided.
+
+    python -m mv_ldm_amd.metrics --pred DIR --gt DIR [--json OUT]
+
+pairs `DIR/<scene>/color/<index>.png` of the two trees by scene and frame index and prints per-scene and overall means.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+from pathlib import Path
+from typing import Dict, List, Tuple
+
+import torch
+
+from . import ops
+
+
+def image_metrics(ground_truth: torch.Tensor, predicted: torch.Tensor, use_sample_covariance: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(psnr, ssim) of `[batch, c, h, w]` -> `[batch]`, or of `[b, v, c, h, w]` -> `[b, v]`, fp32 on the inputs' device, one launch"""
+    if ground_truth.shape != predicted.shape:
+        raise ValueError(f"ground truth {tuple(ground_truth.shape)} against prediction {tuple(predicted.shape)}")
+    if ground_truth.dim() not in (4, 5):
+        raise ValueError(f"expected [batch, c, h, w] or [b, v, c, h, w], got {tuple(ground_truth.shape)}")
+    if not (ground_truth.is_contiguous() and predicted.is_contiguous()):
+        raise ValueError("image_metrics: inputs must be contiguous (call .contiguous() first)")
+    lead = ground_truth.shape[:-3]
+    flat = lambda t: t.reshape(-1, *t.shape[-3:])
+    psnr, ssim = ops.image_metrics(flat(predicted), flat(ground_truth), use_sample_covariance)
+    return psnr.reshape(lead), ssim.reshape(lead)
+
+
+def compute_psnr(ground_truth: torch.Tensor, predicted: torch.Tensor) -> torch.Tensor:
+    """src/evaluation/metrics.py:17-24: both clipped to [0, 1], -10 log10 of the mean squared difference; `+inf` for identical images"""
+    return image_metrics(ground_truth, predicted)[0]
+
+
+def compute_ssim(ground_truth: torch.Tensor, predicted: torch.Tensor, use_sample_covariance: bool = True) -> torch.Tensor:
+    """src/evaluation/metrics.py:58-73: skimage's Gaussian-window SSIM (win_size 11, data_range 1.0, not clipped), mean over channels.
+    `use_sample_covariance` is skimage's default `True` (variances scaled by 121 / 120): DESIGN.md §5, "parity unpinned"."""
+    return image_metrics(ground_truth, predicted, use_sample_covariance)[1]
+
+
+# ---- PNG trees ---------------------------------------------------------------------------------------------------
+def scan_tree(root) -> Dict[str, Dict[int, Path]]:
+    """{scene: {frame index: path}} of `root/<scene>/color/<index>.png`; the index is the file stem as an integer (`000012.png`
+    and `12.png` are both frame 12), files whose stem is no integer are ignored"""
+    out: Dict[str, Dict[int, Path]] = {}
+    root = Path(root)
+    if not root.is_dir():
+        return out
+    for scene in sorted(p for p in root.iterdir() if (p / "color").is_dir()):
+        frames = {int(f.stem): f for f in sorted((scene / "color").glob("*.png")) if f.stem.isdigit()}
+        if frames:
+            out[scene.name] = frames
+    return out
+
+
+def pair_trees(pred: Dict[str, Dict[int, object]], gt: Dict[str, Dict[int, object]]):
+    """Pair two `scan_tree` results by scene and frame index.  Returns (pairs, missing): pairs = {scene: [(index, pred item, gt
+    item), ...]} in index order for every scene both sides have with at least one common frame; missing = a sorted list of
+    ("scene" | "frame", scene, index | None, side that lacks it)."""
+    pairs, missing = {}, []
+    for scene in sorted(set(pred) | set(gt)):
+        if scene not in pred or scene not in gt:
+            missing.append(("scene", scene, None, "pred" if scene not in pred else "gt"))
+            continue
+        p, g = pred[scene], gt[scene]
+        for i in sorted(set(p) ^ set(g)):
+            missing.append(("frame", scene, i, "pred" if i not in p else "gt"))
+        both = [(i, p[i], g[i]) for i in sorted(set(p) & set(g))]
+        if both:
+            pairs[scene] = both
+    return pairs, missing
+
+
+def summarize(per_frame: Dict[str, Dict[int, List[float]]]) -> dict:
+    """{scene: {index: [psnr, ssim]}} -> the report: per-scene means, the overall mean over all frames"""
+    mean = lambda v: sum(v) / len(v) if v else float("nan")
+    scenes = {s: {"psnr": mean([a for a, _ in f.values()]), "ssim": mean([b for _, b in f.values()]), "frames": len(f), "per_frame": f}
+              for s, f in per_frame.items()}
+    every = [v for f in per_frame.values() for v in f.values()]
+    return {"scenes": scenes, "overall": {"psnr": mean([a for a, _ in every]), "ssim": mean([b for _, b in every]), "frames": len(every)}}
+
+
+def score_trees(pred_dir, gt_dir, device="cuda", batch: int = 64) -> dict:
+    """`metric_computer.test_step` over two PNG trees: every paired frame scored on the device, `batch` frames per launch"""
+    from .image_io import load_image
+    pairs, missing = pair_trees(scan_tree(pred_dir), scan_tree(gt_dir))
+    per_frame: Dict[str, Dict[int, List[float]]] = {}
+    for scene, items in pairs.items():
+        per_frame[scene] = {}
+        for i0 in range(0, len(items), batch):
+            chunk = items[i0:i0 + batch]
+            p = torch.stack([load_image(a) for _, a, _ in chunk]).to(device)
+            g = torch.stack([load_image(b) for _, _, b in chunk]).to(device)
+            psnr, ssim = image_metrics(g, p)
+            for (i, _, _), a, b in zip(chunk, psnr.tolist(), ssim.tolist()):
+                per_frame[scene][i] = [a, b]
+    rep = summarize(per_frame)
+    rep["missing"] = [list(m) for m in missing]
+    return rep
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description="PSNR / SSIM of DIR/<scene>/color/<index>.png against a ground-truth tree of the same layout")
+    ap.add_argument("--pred", required=True)
+    ap.add_argument("--gt", required=True)
+    ap.add_argument("--json", default=None, help="write the full report (per frame) here")
+    args = ap.parse_args(argv)
+    if not torch.cuda.is_available():
+        raise SystemExit("metrics needs a GPU (the HIP path has no CPU fallback)")
+    rep = score_trees(args.pred, args.gt)
+    for kind, scene, index, side in rep["missing"]:
+        print(f"skipped {kind} {scene}" + ("" if index is None else f"/{index}") + f": missing in --{side}")
+    for s, r in rep["scenes"].items():
+        print(f"{s}: psnr {r['psnr']:.4f} ssim {r['ssim']:.6f} ({r['frames']} frames)")
+    o = rep["overall"]
+    print(f"overall: psnr {o['psnr']:.4f} ssim {o['ssim']:.6f} ({o['frames']} frames)")
+    if args.json:
+        Path(args.json).write_text(json.dumps(rep, indent=1))
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())

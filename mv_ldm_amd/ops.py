@@ -583,3 +583,41 @@ def ema_update(avg, p, weight: float):
     """avg.lerp_(p, weight) on flat fp32 buffers (torch.optim.swa_utils EMA: weight = 1 - decay)"""
     assert avg.dtype == p.dtype == torch.float32 and avg.is_contiguous() and p.is_contiguous() and avg.numel() == p.numel()
     L.check(L.load().mvldm_ema_update(avg.data_ptr(), p.data_ptr(), avg.numel(), float(weight), stream()))
+
+
+# ------------------------------------------------------------------------------------------ image metrics
+IMAGE_METRICS_TILE = 32          # csrc/metrics.hip kTile: the output tile edge of one workgroup (the tests pick shapes around it)
+IMAGE_METRICS_WINDOW = 11
+
+
+def image_metrics_workspace_bytes(n_img: int, c: int, h: int, w: int) -> int:
+    return int(L.load().mvldm_image_metrics_workspace_bytes(n_img, c, h, w))
+
+
+def image_metrics(pred: torch.Tensor, gt: torch.Tensor, use_sample_covariance: bool = True, out=None, ws: Optional[torch.Tensor] = None):
+    """(psnr, ssim), fp32 `[n_img]` each, of the image pairs `pred`, `gt` `[n_img, c, h, w]` (compute_psnr / compute_ssim,
+    src/evaluation/metrics.py:17-24, 58-73; csrc/metrics.hip).  fp32 contiguous inputs are read in place; bf16 / f16 go through the
+    elementwise convert first; anything else (uint8, strided views) is refused.  `out` = (psnr, ssim) and `ws` (uint8, at least
+    `image_metrics_workspace_bytes`) let a captured graph own its buffers; by default the shared grow-only workspace is used."""
+    for name, t in (("pred", pred), ("gt", gt)):
+        if not t.is_cuda:
+            raise RuntimeError("mv_ldm_amd modules run only on a HIP device (no CPU fallback): move the module and its inputs to 'cuda'")
+        if t.dim() != 4:
+            raise ValueError(f"image_metrics: {name} must be [n_img, c, h, w], got {tuple(t.shape)}")
+        if t.dtype not in _DT:
+            raise TypeError(f"image_metrics: {name} is {t.dtype}; float32, bfloat16 or float16 images in [0, 1] are scored")
+        if not t.is_contiguous():
+            raise ValueError(f"image_metrics: {name} must be contiguous NCHW (got strides {t.stride()}); call .contiguous() first")
+    if pred.shape != gt.shape or pred.device != gt.device:
+        raise ValueError(f"image_metrics: pred {tuple(pred.shape)} on {pred.device} against gt {tuple(gt.shape)} on {gt.device}")
+    pred = pred if pred.dtype == torch.float32 else convert(pred, torch.float32)
+    gt = gt if gt.dtype == torch.float32 else convert(gt, torch.float32)
+    n, c, h, w = pred.shape
+    psnr, ssim = out if out is not None else (torch.empty(n, dtype=torch.float32, device=pred.device) for _ in range(2))
+    assert psnr.dtype == ssim.dtype == torch.float32 and psnr.numel() == ssim.numel() == n and psnr.is_contiguous() and ssim.is_contiguous()
+    need = image_metrics_workspace_bytes(n, c, h, w)
+    if ws is None:
+        ws = workspace(need, pred.device, "metrics")
+    L.check(L.load().mvldm_image_metrics(pred.data_ptr(), gt.data_ptr(), n, c, h, w, int(bool(use_sample_covariance)), psnr.data_ptr(),
+                                         ssim.data_ptr(), ws.data_ptr(), ws.numel() * ws.element_size(), stream()))
+    return psnr, ssim

@@ -27,7 +27,7 @@ the updated weights (RCCL over xGMI via torch.distributed; gloo in the CPU tests
 from __future__ import annotations
 
 import contextlib
-
+import copy
 import ctypes as C
 import math
 import os
@@ -1491,6 +1491,8 @@ class MVLDMTrainer:
         # `model.ema` (diffusion_wrapper.py:138-142): Lightning calls on_before_zero_grad -> ema.update_parameters at the START of
         # every accumulation window (before its zero_grad), so the average sees theta_0 first and lags the optimizer by one step
         self.ema = EMAWeights(self.flat, ema_decay) if ema_decay is not None else None
+        self._val_pipe = None          # validation_step's MVLDMPipeline over this trainer's modules, built on first use
+        self._val_gen = None           # (weights generation, parameter epoch) its sampler plans were recorded for
 
     # ---- plans -------------------------------------------------------------------------------------------
     def plan_for(self, b, v_c, v_t, hl, wl) -> TrainPlan:
@@ -1807,6 +1809,79 @@ class MVLDMTrainer:
         ckpt = torch.load(os.fspath(path), map_location="cpu", weights_only=True)
         self.load_state_dict(ckpt, strict=strict)
         return ckpt
+
+    # ---- validation: sample held-out scenes with the current weights and score them ------------------------------------
+    def validation_step(self, batch, num_inference_steps: Optional[int] = None, x_T=None, encode_noise=None, *, second: Optional[int] = None,
+                        roundtrip_noise=None, use_ema: bool = False, sampler_cfg=None) -> dict:
+        """`DiffusionWrapper.validation_step` (diffusion_wrapper.py:492-544) without the logger: keep ONE context view
+        (`sample_indices(batch, 1, random=True)`, :505-506; the others join the targets), convert to poses relative to it (:509-511),
+        sample the targets with the weights of the last optimizer step (:513-514) and VAE-round-trip the target images (:519-520).
+        Returns {"sampled", "targets", "targets_roundtrip" [b, v_t, 3, H, W], "context" [b, 1, 3, H, W], "psnr" / "ssim" [b, v_t] of the
+        sampled views against the raw targets, "psnr_roundtrip" / "ssim_roundtrip" against the round trip (the ceiling the VAE
+        allows), "batch": the sliced batch `sample()` saw}; all on the device, scored by `metrics.image_metrics`.
+
+        `x_T` / `encode_noise`: the explicit noise of `MVLDMPipeline.sample`; `second`: which context view is kept (the torch.randint
+        of `sample_indices`); `roundtrip_noise`: the posterior draw of the target round trip.  What is not given is drawn inside a
+        forked RNG scope, so the training run's own random streams do not move.  `sampler_cfg`: a `pipeline.SamplerCfg` (default: the
+        released CFG values); `num_inference_steps` overrides its step count.
+
+        Training is left untouched: the sampler runs through an `MVLDMPipeline` over the trainer's own denoiser, autoencoder and
+        scheduler, whose packs and recorded plans key on the parameters' in-place epoch (`FlatParams.bump`); the sampler's own plans
+        are dropped when the weights moved since the last call, the frozen VAE's plans (which training encodes with) are kept, and
+        every VAE call waits for a window being encoded ahead on the side stream.  The training plans, a prefetched window, the
+        gradient and moment buffers, the scheduler's timestep grid and the compute dtype are as they were on return.  Only at an optimizer-step boundary (RuntimeError inside an accumulation window).
+        Under a multi-rank trainer this is a COLLECTIVE (it enters `sync_masters()`): every rank calls it, with its own scenes."""
+        from .metrics import image_metrics
+        from .pipeline import MVLDMPipeline, SamplerCfg, absolute_to_relative_camera
+        from .runtime import compute_dtype
+        if use_ema:
+            raise NotImplementedError("validation_step samples with the live weights; sampling from the EMA (model.use_ema_sampling) is not built")
+        self._at_step_boundary("validation_step()")
+        if not self.opt.masters_exact and self.opt.collective:      # the other ranks' slices are 16-bit precise after a step with the 16-bit gather
+            self.sync_masters()
+            self.flat.bump()
+        dev = self.flat.flat.device
+        if self._val_pipe is None:
+            self._val_pipe = MVLDMPipeline(self.denoiser, self.autoencoder, self.scheduler, rays=self.rays)
+        pipe = self._val_pipe
+        if self._val_gen != (self._weights_gen, self.flat.epoch):
+            # the sampler plans of the old denoiser weights point at packs nothing else uses any more.  Only those: the frozen VAE's
+            # plans are the ones training encodes with (a window encoded ahead may be running in their buffers on the side stream),
+            # they key on their own weights and stay; every VAE call below waits for that side-stream user (`_busy_event`) first.
+            pipe._plans.clear()
+            if isinstance(getattr(self.denoiser, "_plans", None), dict):
+                self.denoiser._plans.clear()
+            self._val_gen = (self._weights_gen, self.flat.epoch)
+        cfg = copy.copy(sampler_cfg) if sampler_cfg is not None else SamplerCfg()
+        if num_inference_steps is not None:
+            cfg.num_inference_steps = int(num_inference_steps)
+        if cfg != pipe.cfg:
+            pipe.cfg = cfg
+        sch = self.scheduler
+        keep = {k: sch.__dict__[k] for k in ("num_inference_steps", "timesteps", "_dev") if k in sch.__dict__}
+        with torch.no_grad(), torch.random.fork_rng(devices=[torch.cuda.current_device() if dev.index is None else dev.index]), compute_dtype(self.dtype):
+            try:
+                ctx, tgt = batch["context"], batch["target"]
+                c_img, c_ext, c_int, t_img, t_ext, t_int, rel_index = sample_indices(ctx, tgt, 1, random=True, second=second)
+                v_c = c_img.shape[1]
+                ext = absolute_to_relative_camera(torch.cat([c_ext, t_ext], dim=1).float(), index=rel_index).float()
+                sliced = {"context": {"image": c_img, "extrinsics": ext[:, :v_c], "intrinsics": c_int},
+                          "target": {"image": t_img, "extrinsics": ext[:, v_c:], "intrinsics": t_int}}
+                if "scene" in batch:
+                    sliced["scene"] = batch["scene"]
+                pipe.set_timesteps()
+                sampled, _ = pipe.sample(sliced, x_T=x_T, encode_noise=encode_noise, dtype=self.dtype)
+                targets = t_img.to(dev, torch.float32).contiguous()
+                roundtrip = pipe.last_stage_decode(pipe.first_stage_encode(targets, noise=roundtrip_noise))
+                sampled, roundtrip = sampled.contiguous(), roundtrip.contiguous()
+                psnr, ssim = image_metrics(targets, sampled)
+                psnr_rt, ssim_rt = image_metrics(roundtrip, sampled)
+            finally:
+                for k in ("num_inference_steps", "timesteps", "_dev"):
+                    sch.__dict__.pop(k, None)
+                sch.__dict__.update(keep)
+        return {"sampled": sampled, "targets": targets, "targets_roundtrip": roundtrip, "context": c_img.to(dev, torch.float32),
+                "psnr": psnr, "ssim": ssim, "psnr_roundtrip": psnr_rt, "ssim_roundtrip": ssim_rt, "batch": sliced}
 
     def _fresh(self, tp: TrainPlan):
         ev = tp.__dict__.pop("_repack_event", None)
