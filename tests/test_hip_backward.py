@@ -9,6 +9,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from test_hip_backward_edges import close_grad      # the relative L2 below AND max|got - ref| / rms(ref), bounds derived there
+
 GRAD_ENABLED = True       # tests/conftest.py::_grad_mode: torch references are differentiated here
 pytestmark = pytest.mark.gpu
 
@@ -73,14 +75,14 @@ def test_conv_data_and_weight_gradients(ops, case, dtype):
         dx = ops.pool2x2_sum(ops.conv2d(dyd, pw))                         # gradient at the upsampled size, then 2x2 sums
     else:
         dx = ops.conv2d(dyd, pw)
-    assert relerr(nchw(dx), gx) < TOL[dtype] * (2 if up else 1)
+    close_grad(nchw(dx), gx, dtype, "dgrad", l2=TOL[dtype] * (2 if up else 1))
     # weight gradient (fp32, PyTorch layout), then accumulated a second time
     grad = torch.zeros(co, ci, ks, ks, device="cuda") if ks > 1 else torch.zeros(co, ci, device="cuda")
     ops.conv_wgrad(nhwc(x, dtype), dyd, grad, ksize=ks, stride=stride, upsample=up)
     gwr = gw if ks > 1 else gw.reshape(co, ci)
-    assert relerr(grad, gwr) < TOL[dtype]
+    close_grad(grad, gwr, dtype, "wgrad", l2=TOL[dtype])
     ops.conv_wgrad(nhwc(x, dtype), dyd, grad, ksize=ks, stride=stride, upsample=up, accumulate=True)
-    assert relerr(grad, 2 * gwr) < TOL[dtype]
+    close_grad(grad, 2 * gwr, dtype, "wgrad", l2=TOL[dtype])
 
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
@@ -98,10 +100,11 @@ def test_skip_concat_conv_and_padded_conv_in_gradients(ops, dtype):
     wc = w.cuda().contiguous()
     da = ops.conv2d(dyd, ops.pack_weight_t(wc, dtype, 0, c0))
     db = ops.conv2d(dyd, ops.pack_weight_t(wc, dtype, c0, c1))
-    assert relerr(nchw(da), ga) < TOL[dtype] and relerr(nchw(db), gb) < TOL[dtype]
+    close_grad(nchw(da), ga, dtype, "dgrad", l2=TOL[dtype])
+    close_grad(nchw(db), gb, dtype, "dgrad", l2=TOL[dtype])
     grad = torch.zeros(co, c0 + c1, 3, 3, device="cuda")
     ops.conv_wgrad(nhwc(a, dtype), dyd, grad, ksize=3, x2=nhwc(b, dtype))
-    assert relerr(grad, gw) < TOL[dtype]
+    close_grad(grad, gw, dtype, "wgrad", l2=TOL[dtype])
     # conv_in: 11 real input channels in a 16-channel buffer
     x11 = rnd((n, 11, h, h), 8, dtype)
     w11 = rnd((64, 11, 3, 3), 9, torch.float32, 0.1)
@@ -113,7 +116,7 @@ def test_skip_concat_conv_and_padded_conv_in_gradients(ops, dtype):
     x16[..., :11] = nhwc(x11, dtype)
     grad = torch.zeros(64, 11, 3, 3, device="cuda")
     ops.conv_wgrad(x16, nhwc(dy, dtype), grad, ksize=3, c_in=11)
-    assert relerr(grad, gw) < TOL[dtype]
+    close_grad(grad, gw, dtype, "wgrad", l2=TOL[dtype])
     # conv_out: 4 output channels (gradient buffer padded to 8 columns)
     x = rnd((n, 64, h, h), 11, dtype)
     w4 = rnd((4, 64, 3, 3), 12, torch.float32, 0.05)
@@ -124,10 +127,10 @@ def test_skip_concat_conv_and_padded_conv_in_gradients(ops, dtype):
     dy8 = torch.zeros(n, h, h, 4 if dtype == torch.float32 else 8, dtype=dtype, device="cuda")      # padded to a 16-byte chunk
     dy8[..., :4] = nhwc(dy, dtype)
     dx = ops.conv2d(dy8, ops.pack_weight_t(w4.cuda().contiguous(), dtype))
-    assert relerr(nchw(dx), gx) < TOL[dtype]
+    close_grad(nchw(dx), gx, dtype, "dgrad", l2=TOL[dtype])
     grad = torch.zeros(4, 64, 3, 3, device="cuda")
     ops.conv_wgrad(nhwc(x, dtype), dy8, grad, ksize=3, n_out=4)
-    assert relerr(grad, gw) < TOL[dtype]
+    close_grad(grad, gw, dtype, "wgrad", l2=TOL[dtype])
 
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
@@ -141,17 +144,17 @@ def test_linear_gradients_column_slices_and_bias_sums(ops, dtype):
     gx, gw = torch.autograd.grad(y, (xd, wd), dy.double())
     dyd, xg = dy.to(dtype).cuda(), x.to(dtype).cuda()
     dx = ops.linear(dyd, ops.pack_weight_t(w.cuda().contiguous(), dtype))
-    assert relerr(dx.float().cpu(), gx) < TOL[dtype]
+    close_grad(dx, gx, dtype, "dgrad", l2=TOL[dtype])
     grad = torch.zeros(n3, c, device="cuda")
     for i in range(3):      # three 64-row slices, each from a column slice of dy
         ops.conv_wgrad(xg.view(rows, 1, 1, c), dyd[:, 64 * i:64 * (i + 1)], grad[64 * i:64 * (i + 1)], ksize=1)
-    assert relerr(grad, gw) < TOL[dtype]
+    close_grad(grad, gw, dtype, "wgrad", l2=TOL[dtype])
     tot = torch.full((n3,), 1.0, device="cuda")
     ops.colsum(dyd, tot, accumulate=True)
-    assert relerr(tot, dy.double().sum(0) + 1.0) < max(TOL[dtype], 1e-5)
+    close_grad(tot, dy.double().sum(0) + 1.0, dtype, "param", l2=max(TOL[dtype], 1e-5))
     per = torch.zeros(4, 256, device="cuda")                 # 4 images of 75 rows, destination row stride 256
     ops.colsum(dyd, per, rows_per_seg=75, per_seg=True, n=n3)
-    assert relerr(per[:, :n3], dy.double().view(4, 75, n3).sum(1)) < max(TOL[dtype], 1e-5)
+    close_grad(per[:, :n3], dy.double().view(4, 75, n3).sum(1), dtype, "param", l2=max(TOL[dtype], 1e-5))
 
 
 # ------------------------------------------------------------------------------------------------ norms
@@ -176,13 +179,14 @@ def test_groupnorm_backward(ops, dtype, silu):
         dg, db = torch.zeros(c, device="cuda"), torch.zeros(c, device="cuda")
         dx, dx2 = ops.groupnorm_bwd(xa, nhwc(dy, dtype), gamma.cuda(), beta.cuda(), stats, dg, db, groups, silu, x2=xb)
         tol = TOL[dtype] * 2
-        assert relerr(nchw(dx), grads[0]) < tol, (dual, "dx")
+        close_grad(nchw(dx), grads[0], dtype, "norm_dx", l2=tol, what=f"dual={dual} dx")
         if dual:
-            assert relerr(nchw(dx2), grads[1]) < tol
-        assert relerr(dg, grads[-2]) < tol and relerr(db, grads[-1]) < tol, (dual, "params")
+            close_grad(nchw(dx2), grads[1], dtype, "norm_dx", l2=tol, what="dx2")
+        close_grad(dg, grads[-2], dtype, "param", l2=tol, what=f"dual={dual} dgamma")
+        close_grad(db, grads[-1], dtype, "param", l2=tol, what=f"dual={dual} dbeta")
         # parameter gradients accumulate
         ops.groupnorm_bwd(xa, nhwc(dy, dtype), gamma.cuda(), beta.cuda(), stats, dg, db, groups, silu, x2=xb)
-        assert relerr(dg, 2 * grads[-2]) < tol
+        close_grad(dg, 2 * grads[-2], dtype, "param", l2=tol, what="2 x dgamma")
 
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
@@ -197,8 +201,9 @@ def test_layernorm_backward(ops, dtype, c):
     gx, gg, gb = torch.autograd.grad(y, (xd, gd, bd), dy.double())
     dg, db = torch.zeros(c, device="cuda"), torch.zeros(c, device="cuda")
     dx = ops.layernorm_bwd(x.to(dtype).cuda(), dy.to(dtype).cuda(), gamma.cuda(), dg, db)
-    assert relerr(dx.float().cpu(), gx) < TOL[dtype] * 2
-    assert relerr(dg, gg) < TOL[dtype] * 2 and relerr(db, gb) < TOL[dtype] * 2
+    close_grad(dx, gx, dtype, "norm_dx", l2=TOL[dtype] * 2)
+    close_grad(dg, gg, dtype, "param", l2=TOL[dtype] * 2)
+    close_grad(db, gb, dtype, "param", l2=TOL[dtype] * 2)
 
 
 # ------------------------------------------------------------------------------------------------ attention
@@ -239,7 +244,8 @@ def test_attention_backward(ops, case, dtype):
         assert (lse[:, :ql].double().cpu() - torch.logsumexp(s, -1) / math.log(2)).abs().max() < (1e-4 if dtype == torch.float32 else 2e-2)
     dq, dk, dv = ops.attention_bwd(qg, kg, vg, out, dout.to(dtype).cuda(), lse, heads, d, seg, max(q_lens), max(kv_lens))
     tol = 3e-5 if dtype == torch.float32 else TOL[dtype] * 3
-    assert relerr(dq.float().cpu(), gq) < tol and relerr(dk.float().cpu(), gk) < tol and relerr(dv.float().cpu(), gv) < tol
+    for got, want, nm in ((dq, gq, "dq"), (dk, gk, "dk"), (dv, gv, "dv")):
+        close_grad(got, want, dtype, "attn", l2=tol, what=nm)
 
 
 # ------------------------------------------------------------------------------------------------ elementwise, loss
@@ -251,16 +257,17 @@ def test_geglu_silu_resampling(ops, dtype):
     h = agd[:, :D] * F.gelu(agd[:, D:])
     (gag,) = torch.autograd.grad(h, agd, dh.double())
     agg = ag.to(dtype).cuda()
-    assert relerr(ops.geglu_fwd(agg).float().cpu(), h) < TOL[dtype] * 2
-    assert relerr(ops.geglu_bwd(agg, dh.to(dtype).cuda()).float().cpu(), gag) < TOL[dtype] * 2
+    close_grad(ops.geglu_fwd(agg), h, dtype, "eltwise", l2=TOL[dtype] * 2, what="geglu_fwd")
+    close_grad(ops.geglu_bwd(agg, dh.to(dtype).cuda()), gag, dtype, "eltwise", l2=TOL[dtype] * 2, what="geglu_bwd")
     x, dy = rnd((5, 1280), 32, dtype, 2.0), rnd((5, 1280), 33, dtype)
     xd = x.double().requires_grad_()
     (gx,) = torch.autograd.grad(F.silu(xd), xd, dy.double())
-    assert relerr(ops.silu_bwd(x.to(dtype).cuda(), dy.to(dtype).cuda()).float().cpu(), gx) < TOL[dtype] * 2
+    close_grad(ops.silu_bwd(x.to(dtype).cuda(), dy.to(dtype).cuda()), gx, dtype, "eltwise", l2=TOL[dtype] * 2, what="silu_bwd")
     # silu_bwd with the pre-activation kept in fp32 (the time-embedding path)
-    assert relerr(ops.train_eltwise(0, x.cuda(), dy.to(dtype).cuda(), torch.empty(5, 1280, dtype=dtype, device="cuda"), 1, 5 * 1280).float().cpu(), gx) < TOL[dtype] * 2
+    close_grad(ops.train_eltwise(0, x.cuda(), dy.to(dtype).cuda(), torch.empty(5, 1280, dtype=dtype, device="cuda"), 1, 5 * 1280), gx, dtype, "eltwise",
+               l2=TOL[dtype] * 2, what="silu_bwd fp32 x")
     du = rnd((2, 8, 8, 32), 34, dtype)
-    assert relerr(ops.pool2x2_sum(du.to(dtype).cuda()).float().cpu(), du.double().view(2, 4, 2, 4, 2, 32).sum((2, 4))) < TOL[dtype]
+    close_grad(ops.pool2x2_sum(du.to(dtype).cuda()), du.double().view(2, 4, 2, 4, 2, 32).sum((2, 4)), dtype, "eltwise", l2=TOL[dtype], what="pool2x2_sum")
     z = ops.zero_insert2x(du.to(dtype).cuda()).float().cpu()
     assert torch.equal(z[:, ::2, ::2], du) and float(z[:, 1::2].abs().max()) == 0 and float(z[:, :, 1::2].abs().max()) == 0
     a, b = rnd((100, 64), 35, dtype).to(dtype).cuda(), rnd((100, 64), 36, dtype).to(dtype).cuda()
