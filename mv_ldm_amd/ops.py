@@ -174,28 +174,48 @@ class PackBatch:
 
 
 # ------------------------------------------------------------------------------------------ igemm
+def conv_out_hw(h: int, w: int, ksize: int, stride: int, pad: int, upsample) -> tuple:
+    """output size of a forward conv; `upsample`: 0 / 1 (nearest-2x in front), or 2 + phase (one phase conv: the low-resolution size)"""
+    if int(upsample) >= 2:
+        return h, w
+    hs, ws = (2 * h, 2 * w) if upsample else (h, w)
+    if ksize == 3 and stride == 2 and pad == 0:       # VAE encoder: F.pad(0,1,0,1) then stride-2 conv
+        return (hs + 1 - 3) // 2 + 1, (ws + 1 - 3) // 2 + 1
+    return (hs + 2 * pad - ksize) // stride + 1, (ws + 2 * pad - ksize) // stride + 1
+
+
+def use_skinny(d, pw: PackedWeight) -> torch.Tensor:
+    """point igemm descriptor `d` at the fragment-order copy of `pw` (what tile 15, csrc/skinny.hip, reads); returns the copy"""
+    t = pw.skinny()
+    d.weight, d.k_order = ptr(t), 2
+    return t
+
+
 def igemm_desc(src0, src1, pw: PackedWeight, dst, *, n_img, h_in, w_in, h_out, w_out, stride=1, pad=None, upsample=False,
                bias=None, row_bias=None, residual=None, epilogue=L.EPI_NONE, out_scale=1.0, ws=None, splitk=0,
-               tile=0) -> L.IgemmDesc:
-    d = L.IgemmDesc()
+               tile=0, into=None) -> L.IgemmDesc:
+    """the one place an implicit-GEMM descriptor is filled: eager calls get a fresh one, a plan passes `into=op.u.igemm`.
+    `upsample`: 0 / 1, or 2 + phase (see upsample_phase_weights); `ws`: split-K workspace (None: one K pass)."""
+    d = L.IgemmDesc() if into is None else into
     c0 = src0.shape[-1]
     c1 = 0 if src1 is None else src1.shape[-1]
     assert c0 + c1 == pw.c_pad, f"weight packed for {pw.c_pad} channels, sources give {c0}+{c1}"
+    assert not pw.k_order or c0 % block_k(src0.dtype) == 0, "weight packed block-major but the source split is unaligned"
     d.src0, d.src1, d.weight = ptr(src0), ptr(src1), ptr(pw.data)
     d.bias, d.row_bias, d.residual, d.dst = ptr(bias), ptr(row_bias), ptr(residual), ptr(dst)
     d.c0, d.c1 = c0, c1
     d.n_img, d.h_in, d.w_in, d.h_out, d.w_out = n_img, h_in, w_in, h_out, w_out
-    d.ksize, d.stride, d.upsample = pw.ksize, stride, int(upsample)      # 0/1, or 2 + phase (see upsample_phase_weights)
+    d.ksize, d.stride, d.upsample = pw.ksize, stride, int(upsample)
     d.pad = (pw.ksize // 2) if pad is None else pad
     d.n_out, d.n_pad, d.k_pad = pw.n_out, pw.n_pad, pw.k_pad
     d.row_bias_ld = 0 if row_bias is None else row_bias.stride(0)
     d.epilogue, d.act_dtype, d.dst_dtype = epilogue, dt(src0), dt(dst)
     d.splitk, d.tile, d.out_scale = splitk, tile, out_scale
-    d.dst_ld = 0
+    n_dst = pw.n_out // 2 if epilogue == L.EPI_GEGLU else pw.n_out
+    d.dst_ld = 0 if dst.shape[-1] == n_dst else dst.shape[-1]      # rows of a wider buffer
     d.k_order = pw.k_order
-    assert not pw.k_order or c0 % block_k(src0.dtype) == 0, "weight packed block-major but the source split is unaligned"
     if (tile & 63) == 15:       # the skinny weight-streaming kernel reads the fragment-order copy of the pack
-        d.weight, d.k_order = ptr(pw.skinny()), 2
+        use_skinny(d, pw)
     if ws is not None:
         d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel() * ws.element_size()
     else:
@@ -212,11 +232,7 @@ def conv2d(x: torch.Tensor, pw: PackedWeight, bias=None, *, x2=None, stride=1, p
     assert x.is_cuda and x.is_contiguous() and (x2 is None or x2.is_contiguous())
     n, h, w, _ = x.shape
     pad = (pw.ksize // 2) if pad is None else pad
-    hs, ws_ = (2 * h, 2 * w) if upsample else (h, w)
-    if pw.ksize == 3 and stride == 2 and pad == 0:       # VAE encoder: F.pad(0,1,0,1) then stride-2 conv
-        ho, wo = (hs + 1 - 3) // 2 + 1, (ws_ + 1 - 3) // 2 + 1
-    else:
-        ho, wo = (hs + 2 * pad - pw.ksize) // stride + 1, (ws_ + 2 * pad - pw.ksize) // stride + 1
+    ho, wo = conv_out_hw(h, w, pw.ksize, stride, pad, upsample)
     n_dst = pw.n_out // 2 if epilogue == L.EPI_GEGLU else pw.n_out
     if out is None:
         out = torch.empty(n, ho, wo, n_dst, dtype=out_dtype or x.dtype, device=x.device)
@@ -432,6 +448,22 @@ def ddpm_cfg_step(eps_c, eps_u, x_t, noise, cfg_scale, coef, clip_range: float =
 
 
 # ------------------------------------------------------------------------------------------ training kernels
+def wgrad_desc(x, x2, dy, grad, ws, *, h_out, w_out, ksize, stride, pad, upsample, n_out, c_in=None, accumulate=False, form: int = 0,
+               into=None) -> L.WgradDesc:
+    """the one place a weight-gradient descriptor is filled (`into=op.u.wgrad` for a plan).  `ws`: uint8 slab workspace;
+    form: 0 = the library's rule, 1 = register-staged small tile, 2 = wide LDS-DMA tile (bits 8-9 of `accumulate`)"""
+    d = L.WgradDesc() if into is None else into
+    n, h, w, c0 = x.shape
+    c1 = 0 if x2 is None else x2.shape[-1]
+    d.src0, d.src1, d.dy, d.grad = ptr(x), ptr(x2), ptr(dy), ptr(grad)
+    d.workspace, d.workspace_bytes = ptr(ws), ws.numel()
+    d.c0, d.c1, d.c_in = c0, c1, (c0 + c1) if c_in is None else c_in
+    d.n_img, d.h_in, d.w_in, d.h_out, d.w_out = n, h, w, h_out, w_out
+    d.ksize, d.stride, d.pad, d.upsample = ksize, stride, pad, int(upsample)
+    d.n_out, d.dy_ld, d.act_dtype, d.accumulate = n_out, dy.stride(-2), dt(x), int(accumulate) | (int(form) << 8)
+    return d
+
+
 def conv_wgrad(x, dy, grad, *, ksize, stride=1, pad=None, upsample=False, x2=None, c_in=None, accumulate=False, n_out=None, form: int = 0) -> torch.Tensor:
     """x (x2): NHWC forward input(s); dy: NHWC / `[m, ld]` upstream gradient (columns [0, n_out)); grad: fp32 PyTorch-layout
     weight gradient `[n_out, c_in, k, k]` / `[n_out, c_in]`, written or accumulated in place."""
@@ -441,16 +473,10 @@ def conv_wgrad(x, dy, grad, *, ksize, stride=1, pad=None, upsample=False, x2=Non
     hs, ws_ = (2 * h, 2 * w) if upsample else (h, w)
     ho, wo = (hs + 2 * pad - ksize) // stride + 1, (ws_ + 2 * pad - ksize) // stride + 1
     n_out = grad.shape[0] if n_out is None else n_out
-    d = L.WgradDesc()
-    d.src0, d.src1, d.dy, d.grad = ptr(x), ptr(x2), ptr(dy), ptr(grad)
     need = n_out * ksize * ksize * (c0 + c1) * 4
     scratch = workspace(min(max(need * 8, 1 << 20), max(need, 512 << 20)), x.device, "wgrad")
-    d.workspace, d.workspace_bytes = scratch.data_ptr(), scratch.numel()
-    d.c0, d.c1, d.c_in = c0, c1, (c0 + c1) if c_in is None else c_in
-    d.n_img, d.h_in, d.w_in, d.h_out, d.w_out = n, h, w, ho, wo
-    d.ksize, d.stride, d.pad, d.upsample = ksize, stride, pad, int(upsample)
-    # form: 0 = the library's rule, 1 = register-staged small tile, 2 = wide LDS-DMA tile (bits 8-9 of `accumulate`)
-    d.n_out, d.dy_ld, d.act_dtype, d.accumulate = n_out, dy.stride(-2), dt(x), int(accumulate) | (int(form) << 8)
+    d = wgrad_desc(x, x2, dy, grad, scratch, h_out=ho, w_out=wo, ksize=ksize, stride=stride, pad=pad, upsample=upsample, n_out=n_out,
+                   c_in=c_in, accumulate=accumulate, form=form)
     L.check(L.load().mvldm_igemm_wgrad(C.byref(d), stream()))
     return grad
 
@@ -488,6 +514,20 @@ def layernorm_bwd(x, dy, gamma, dgamma, dbeta, eps=1e-5):
     return dx
 
 
+def attn_bwd_desc(q, k, v, out, dout, dq, dk, dv, lse, delta, seg, *, heads, head_dim, max_q_len, max_kv_len, scale=None,
+                  into=None) -> L.AttnBwdDesc:
+    """the one place an attention-backward descriptor is filled (`into=op.u.attention_bwd` for a plan).  q / k / v and their
+    gradients are 2-D views with unit column stride (column slices of a fused projection: only the row strides are used)."""
+    d = L.AttnBwdDesc() if into is None else into
+    d.q, d.k, d.v, d.out, d.dout, d.dq, d.dk, d.dv = (t.data_ptr() for t in (q, k, v, out, dout, dq, dk, dv))
+    d.lse, d.delta, d.seg = lse.data_ptr(), delta.data_ptr(), seg.data_ptr()
+    d.ld_q, d.ld_k, d.ld_v, d.ld_o, d.ld_do, d.ld_dq, d.ld_dk, d.ld_dv = (t.stride(0) for t in (q, k, v, out, dout, dq, dk, dv))
+    d.heads, d.head_dim, d.n_seg, d.max_q_len, d.max_kv_len = heads, head_dim, seg.shape[0], max_q_len, max_kv_len
+    d.total_q_rows, d.stat_ld, d.dtype = q.shape[0], lse.stride(0), dt(q)
+    d.scale = head_dim ** -0.5 if scale is None else scale
+    return d
+
+
 def attention_bwd(q, k, v, out, dout, lse, heads, head_dim, seg, max_q_len, max_kv_len, scale=None, dqkv=None):
     """returns (dq, dk, dv) `[tokens, heads*head_dim]` (views of `dqkv` `[tokens, 3C]` when given)"""
     C_ = heads * head_dim
@@ -496,13 +536,8 @@ def attention_bwd(q, k, v, out, dout, lse, heads, head_dim, seg, max_q_len, max_
     else:
         dq, dk, dv = dqkv[:, :C_], dqkv[:, C_:2 * C_], dqkv[:, 2 * C_:]
     delta = torch.empty_like(lse)
-    d = L.AttnBwdDesc()
-    d.q, d.k, d.v, d.out, d.dout, d.dq, d.dk, d.dv = (t.data_ptr() for t in (q, k, v, out, dout, dq, dk, dv))
-    d.lse, d.delta, d.seg = lse.data_ptr(), delta.data_ptr(), seg.data_ptr()
-    d.ld_q, d.ld_k, d.ld_v, d.ld_o, d.ld_do, d.ld_dq, d.ld_dk, d.ld_dv = (t.stride(0) for t in (q, k, v, out, dout, dq, dk, dv))
-    d.heads, d.head_dim, d.n_seg, d.max_q_len, d.max_kv_len = heads, head_dim, seg.shape[0], max_q_len, max_kv_len
-    d.total_q_rows, d.stat_ld, d.dtype = q.shape[0], lse.stride(0), dt(q)
-    d.scale = head_dim ** -0.5 if scale is None else scale
+    d = attn_bwd_desc(q, k, v, out, dout, dq, dk, dv, lse, delta, seg, heads=heads, head_dim=head_dim, max_q_len=max_q_len,
+                      max_kv_len=max_kv_len, scale=scale)
     L.check(L.load().mvldm_attention_bwd(C.byref(d), stream()))
     return dq, dk, dv
 

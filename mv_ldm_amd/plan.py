@@ -23,7 +23,7 @@ from typing import List, Optional
 import torch
 
 from . import _lib as L
-from .ops import PackedWeight, dt, ptr
+from .ops import PackedWeight, conv_out_hw, dt, igemm_desc, ptr, use_skinny
 
 
 def _PIN_TILE() -> int:
@@ -180,58 +180,46 @@ class Builder:
         """x (and x2): NHWC `[n, h, w, c]` contiguous; returns NHWC."""
         n, h, w, c0 = x.shape
         c1 = 0 if x2 is None else x2.shape[-1]
-        assert c0 + c1 == pw.c_pad, f"{name}: weight packed for {pw.c_pad} channels, got {c0}+{c1}"
         pad = (pw.ksize // 2) if pad is None else pad
-        hs, ws_ = (2 * h, 2 * w) if upsample else (h, w)
-        if pw.ksize == 3 and stride == 2 and pad == 0:
-            ho, wo = (hs + 1 - 3) // 2 + 1, (ws_ + 1 - 3) // 2 + 1
-        else:
-            ho, wo = (hs + 2 * pad - pw.ksize) // stride + 1, (ws_ + 2 * pad - pw.ksize) // stride + 1
+        ho, wo = conv_out_hw(h, w, pw.ksize, stride, pad, upsample)
         n_dst = pw.n_out // 2 if epilogue == L.EPI_GEGLU else pw.n_out
         if out is None:
             out = self.empty(n, ho, wo, n_dst, dtype=out_dtype or x.dtype)
         ws = self.splitk_ws() if splitk != 1 else None
-        op = L.Op()
-        op.kind = L.OP_IGEMM
-        d = op.u.igemm
-        d.src0, d.src1, d.weight = ptr(x), ptr(x2), ptr(pw.data)
-        d.bias, d.row_bias, d.residual, d.dst = ptr(bias), ptr(row_bias), ptr(residual), ptr(out)
-        d.c0, d.c1 = c0, c1
-        d.n_img, d.h_in, d.w_in, d.h_out, d.w_out = n, h, w, ho, wo
-        d.ksize, d.stride, d.pad, d.upsample = pw.ksize, stride, pad, int(upsample)
-        d.n_out, d.n_pad, d.k_pad = pw.n_out, pw.n_pad, pw.k_pad
-        d.row_bias_ld = 0 if row_bias is None else row_bias.stride(0)
-        d.epilogue, d.act_dtype, d.dst_dtype = epilogue, dt(x), dt(out)
         if tile == 0 and _PIN_TILE() and x.dtype != torch.float32 and pw.k_order == 1:
             tile, splitk = _PIN_TILE(), 1        # (test knob MVLDM_IGEMM_TILE: one tile, one K pass for every 16-bit block-major launch, see _PIN_TILE)
         m = n * ho * wo
-        can_sk = self.skinny and skinny_candidate(pw, m, c0, c1, upsample, x.dtype)
-        d.splitk, d.tile, d.out_scale = splitk, tile, out_scale
-        d.dst_ld = out.shape[-1] if out.shape[-1] != n_dst else 0
-        d.k_order = pw.k_order
-        can_sk = can_sk and x.is_cuda and L.load().mvldm_igemm_skinny_config(C.byref(d)) > 0      # (an image may be larger than the kernel's row tiles)
-        if tile == 0 and can_sk and skinny_rule(m, pw.n_pad):
-            tile = d.tile = 15                   # the rule: launches of a few hundred rows stream their weights (csrc/skinny.hip)
-        if (tile & 63) == 15:
-            d.weight, d.k_order = ptr(pw.skinny()), 2
-        elif can_sk and self.record and tile == 0:
-            self._skinny_pw[len(self.ops)] = pw  # a plan-time candidate (autotune_igemm)
-        assert not pw.k_order or c0 % (32 if x.dtype == torch.float32 else 64) == 0, f"{name}: block-major weight, unaligned source split"
-        if ws is not None:
-            d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
-        else:
-            d.workspace, d.workspace_bytes, d.splitk = None, 0, 1
         k_real = pw.ksize * pw.ksize * (c0 + c1)
         es = x.element_size()
         nbytes = (pw.n_out * k_real + n * h * w * (c0 + c1)) * es + m * n_dst * out.element_size() \
             + (m * n_dst * es if residual is not None else 0)
+        self._igemm(x, x2, pw, bias, row_bias, residual, out, ws, name, 2.0 * m * pw.n_out * k_real, nbytes, h_out=ho, w_out=wo,
+                    stride=stride, pad=pad, upsample=upsample, epilogue=epilogue, out_scale=out_scale, splitk=splitk, tile=tile)
+        return out
+
+    def _igemm(self, x, x2, pw, bias, row_bias, residual, out, ws, name, flops, nbytes, *, h_out, w_out, tile=0, **desc):
+        """emit one implicit-GEMM op.  The descriptor comes from `ops.igemm_desc`; what is added here is plan policy: tile 15 by
+        rule or as a plan-time candidate (see `skinny_rule`), and which sources the tuner may fill with timing data."""
+        n, h, w, c0 = x.shape
+        c1 = 0 if x2 is None else x2.shape[-1]
+        op = L.Op()
+        op.kind = L.OP_IGEMM
+        d = igemm_desc(x, x2, pw, out, n_img=n, h_in=h, w_in=w, h_out=h_out, w_out=w_out, bias=bias, row_bias=row_bias,
+                       residual=residual, ws=ws, tile=tile, into=op.u.igemm, **desc)
+        m = n * h_out * w_out
+        can_sk = tile == 0 and self.skinny and skinny_candidate(pw, m, c0, c1, d.upsample, x.dtype) \
+            and x.is_cuda and L.load().mvldm_igemm_skinny_config(C.byref(d)) > 0      # (an image may be larger than the kernel's row tiles)
+        if can_sk and skinny_rule(m, pw.n_pad):
+            tile = d.tile = 15                   # the rule: launches of a few hundred rows stream their weights (csrc/skinny.hip)
+            use_skinny(d, pw)
+        elif can_sk and self.record:
+            self._skinny_pw[len(self.ops)] = pw  # a plan-time candidate (autotune_igemm)
         if self.record:
             # (only temporaries of this builder's own pool may be filled with timing data: a caller's tensor is left alone)
             own = self.__dict__.get("_own_ptrs", ())
             self.__dict__.setdefault("_tune_srcs", {})[len(self.ops)] = tuple(t if (t is not None and t.data_ptr() in own) else None
                                                                               for t in (x, x2))
-        self._emit(op, name, 2.0 * m * pw.n_out * k_real, nbytes, (x, x2, pw.data, pw._skinny if (tile & 63) == 15 else None, bias, row_bias, residual, out))
-        return out
+        self._emit(op, name, flops, nbytes, (x, x2, pw.data, pw._skinny if (tile & 63) == 15 else None, bias, row_bias, residual, out))
 
     def small_launch(self, rows: int, n_out: int) -> bool:
         """should independent launches of this size run as parallel lanes?  OFF by default (MVLDM_PAR_ROWS=0): measured on MI355X /
@@ -263,36 +251,11 @@ class Builder:
         n, h, w, c0 = x.shape
         ws = self.splitk_ws()        # small batches: K = 4C is long and there are few output tiles -- let the library split K
         assert pw.ksize == 2 and pw.k_order == 1 and c0 == pw.c_pad
-        op = L.Op()
-        op.kind = L.OP_IGEMM
-        d = op.u.igemm
-        d.src0, d.src1, d.weight = ptr(x), None, ptr(pw.data)
-        d.bias, d.row_bias, d.residual, d.dst = ptr(bias), None, None, ptr(out)
-        d.c0, d.c1 = c0, 0
-        d.n_img, d.h_in, d.w_in, d.h_out, d.w_out = n, h, w, h, w
-        d.ksize, d.stride, d.pad, d.upsample = 2, 1, 0, 2 + phase
-        d.n_out, d.n_pad, d.k_pad = pw.n_out, pw.n_pad, pw.k_pad
-        d.row_bias_ld = 0
-        d.epilogue, d.act_dtype, d.dst_dtype = L.EPI_NONE, dt(x), dt(out)
         m = n * h * w
-        can_sk = self.skinny and skinny_candidate(pw, m, c0, 0, False, x.dtype)
-        d.splitk, d.tile, d.out_scale = splitk, tile, 1.0
-        d.dst_ld = 0
-        d.k_order = 1
-        can_sk = can_sk and x.is_cuda and L.load().mvldm_igemm_skinny_config(C.byref(d)) > 0
-        if tile == 0 and can_sk and skinny_rule(m, pw.n_pad):
-            tile = d.tile = 15
-        if (tile & 63) == 15:
-            d.weight, d.k_order = ptr(pw.skinny()), 2
-        elif can_sk and self.record and tile == 0:
-            self._skinny_pw[len(self.ops)] = pw
-        d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
         es = x.element_size()
-        nbytes = (pw.n_out * 4 * c0 + (m * c0 if phase == 0 else 0)) * es + m * pw.n_out * es
-        if self.record:
-            own = self.__dict__.get("_own_ptrs", ())
-            self.__dict__.setdefault("_tune_srcs", {})[len(self.ops)] = (x if x.data_ptr() in own else None, None)
-        self._emit(op, f"{name}.p{phase}", 2.0 * m * pw.n_out * 4 * c0, nbytes, (x, pw.data, pw._skinny if (tile & 63) == 15 else None, bias, out))
+        nbytes = (pw.n_out * 4 * c0 + (m * c0 if phase == 0 else 0)) * es + m * pw.n_out * es      # (the activation read is counted once)
+        self._igemm(x, None, pw, bias, None, None, out, ws, f"{name}.p{phase}", 2.0 * m * pw.n_out * 4 * c0, nbytes, h_out=h, w_out=w,
+                    stride=1, pad=0, upsample=2 + phase, splitk=splitk, tile=tile)
 
     def linear(self, x, pw: PackedWeight, bias=None, *, residual=None, epilogue=L.EPI_NONE, out_dtype=None, out=None,
                name="linear", row_bias=None):
@@ -566,7 +529,7 @@ _SMALL_TILES = tuple(int(t) for t in os.environ.get("MVLDM_TUNE_SMALL_TILES", "0
 
 
 # ---- igemm tile 15 (csrc/skinny.hip): the skinny-M weight-streaming kernel.  It reads the FRAGMENT-ORDER copy of the packed weight
-# (`PackedWeight.skinny()`, made on first use), so a choice of tile 15 swaps the descriptor's weight pointer and sets k_order = 2.
+# (`PackedWeight.skinny()`, made on first use), so a choice of tile 15 points the descriptor at that copy (`ops.use_skinny`).
 # Candidates: 16-bit block-major convs / Linears of at most MVLDM_SKINNY_ROWS output rows whose channel counts are multiples of 64.
 # With plan-time tuning on it is one more candidate, timed like the tiles in every configuration the library accepts; with tuning off
 # (MVLDM_AUTOTUNE=0) it is the RULE for the shape classes it won in tools/skinny_bench.py (profiles/r05_skinny_bench.json): launches of at
@@ -667,12 +630,13 @@ def autotune_igemm(ops, min_rows: int = 2048, iters: int = 4, srcs=None, skinny=
                 cands = cands + [(19, None), (13 | (1 << 13), None)]
             if sk_pw is not None:            # tile 15 in every configuration the library accepts for this problem (others return an error)
                 cands = cands + [(15 | (c << 8), 1) for c in _SKINNY_CFGS]
-                sk_ptr = sk_pw.skinny().data_ptr()
             results = []
             for tile, sk in cands:
                 trial.u.igemm.tile = tile
                 trial.u.igemm.splitk = d.splitk if sk is None else sk
-                trial.u.igemm.weight, trial.u.igemm.k_order = (sk_ptr, 2) if (tile & 63) == 15 else (d.weight, d.k_order)
+                trial.u.igemm.weight, trial.u.igemm.k_order = d.weight, d.k_order
+                if (tile & 63) == 15:
+                    use_skinny(trial.u.igemm, sk_pw)
                 if lib.mvldm_op_run(C.byref(trial), stream) != 0:      # candidate not applicable to this problem
                     continue
                 if cold:
@@ -715,7 +679,7 @@ def autotune_igemm(ops, min_rows: int = 2048, iters: int = 4, srcs=None, skinny=
                 if sk_pw is None:
                     tile, sk = 0, None
                 else:
-                    trial.u.igemm.weight, trial.u.igemm.k_order = sk_pw.skinny().data_ptr(), 2
+                    use_skinny(trial.u.igemm, sk_pw)
             if tile != 0 and lib.mvldm_op_run(C.byref(trial), stream) != 0:
                 tile, sk = 0, None
                 _TUNE_CACHE[key] = [0, None]
@@ -724,9 +688,8 @@ def autotune_igemm(ops, min_rows: int = 2048, iters: int = 4, srcs=None, skinny=
         if sk is not None:
             d.splitk = sk
         if (tile & 63) == 15:                # the fragment-order copy of the weight stays with the plan
-            t = sk_pw.skinny()
+            t = use_skinny(d, sk_pw)
             sk_pw._skinny_pinned = True      # the op holds a raw pointer: the copy stays with the pack whoever else shares it
-            d.weight, d.k_order = t.data_ptr(), 2
             if keep is not None:
                 keep.append(t)
         elif sk_pw is not None:

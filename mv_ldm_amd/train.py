@@ -263,19 +263,13 @@ class TrainBuilder(Builder):
 
     def _wgrad(self, x, x2, dy2d, n_out, grad, geom, c_in, name):
         """`grad` comes from `_pgrad` in the caller's argument list: `self._fw` is that range's store / accumulate decision"""
-        n, h, w, c0 = x.shape
+        assert not getattr(self, "_lane", 0), "weight gradients run on the main lane (they own the big slab workspace)"
         op = L.Op()
         op.kind = L.OP_WGRAD
-        d = op.u.wgrad
-        d.src0, d.src1, d.dy, d.grad = ptr(x), ptr(x2), ptr(dy2d), ptr(grad)
-        assert not getattr(self, "_lane", 0), "weight gradients run on the main lane (they own the big slab workspace)"
-        d.workspace, d.workspace_bytes = ptr(self._wws), self._wws.numel()
-        d.c0, d.c1, d.c_in = c0, 0 if x2 is None else x2.shape[-1], c_in
-        d.n_img, d.h_in, d.w_in, d.h_out, d.w_out = n, h, w, geom["ho"], geom["wo"]
-        d.ksize, d.stride, d.pad, d.upsample = geom["ksize"], geom["stride"], geom["pad"], int(geom["upsample"])
-        d.n_out, d.dy_ld, d.act_dtype, d.accumulate = n_out, dy2d.stride(0), dt(x), 0 if self._fw else 1
-        m = n * geom["ho"] * geom["wo"]
-        k = geom["ksize"] ** 2 * (c0 + d.c1)
+        d = ops.wgrad_desc(x, x2, dy2d, grad, self._wws, h_out=geom["ho"], w_out=geom["wo"], ksize=geom["ksize"], stride=geom["stride"],
+                           pad=geom["pad"], upsample=geom["upsample"], n_out=n_out, c_in=c_in, accumulate=not self._fw, into=op.u.wgrad)
+        m = d.n_img * geom["ho"] * geom["wo"]
+        k = geom["ksize"] ** 2 * (d.c0 + d.c1)
         self._emit(op, name, 2.0 * m * n_out * k, (m * (n_out + k / geom["ksize"] ** 2)) * x.element_size() + n_out * k * 4.0, (x, x2, dy2d, grad))
 
     def _as_act(self, g, name="cast"):
@@ -539,14 +533,9 @@ class TrainBuilder(Builder):
             dqkv = self.empty(M, 3 * Cw)
             op = L.Op()
             op.kind = L.OP_ATTENTION_BWD
-            d = op.u.attention_bwd
-            d.q, d.k, d.v, d.out, d.dout = ptr(qkv[:, :Cw]), ptr(qkv[:, Cw:2 * Cw]), ptr(qkv[:, 2 * Cw:]), ptr(out), ptr(do)
-            d.dq, d.dk, d.dv = ptr(dqkv[:, :Cw]), ptr(dqkv[:, Cw:2 * Cw]), ptr(dqkv[:, 2 * Cw:])
-            d.lse, d.delta, d.seg = ptr(lse), ptr(delta), ptr(seg)
-            d.ld_q = d.ld_k = d.ld_v = d.ld_dq = d.ld_dk = d.ld_dv = 3 * Cw
-            d.ld_o, d.ld_do = out.stride(0), do.stride(0)
-            d.heads, d.head_dim, d.n_seg, d.max_q_len, d.max_kv_len = heads, head_dim, seg.shape[0], max(lens), max(lens)
-            d.total_q_rows, d.stat_ld, d.dtype, d.scale = M, M, dt(qkv), head_dim ** -0.5
+            ops.attn_bwd_desc(qkv[:, :Cw], qkv[:, Cw:2 * Cw], qkv[:, 2 * Cw:], out, do, dqkv[:, :Cw], dqkv[:, Cw:2 * Cw], dqkv[:, 2 * Cw:],
+                              lse, delta, seg, heads=heads, head_dim=head_dim, max_q_len=max(lens), max_kv_len=max(lens),
+                              into=op.u.attention_bwd)
             pairs = sum(l * l for l in lens)
             self._emit(op, "bwd/" + name, 14.0 * pairs * Cw, 8.0 * M * Cw * qkv.element_size(), (qkv, out, do, dqkv, lse, delta, seg))
             self.add_grad(qkv, dqkv)
@@ -569,12 +558,7 @@ class TrainBuilder(Builder):
 
     def t_gelu(self, x, name="gelu"):
         """exact GELU as its own op (the inference path fuses it into the GEMM epilogue; training keeps the pre-activation)"""
-        y = self.empty(*x.shape)
-        op = L.Op()
-        op.kind = L.OP_ELTWISE
-        e = op.u.eltwise
-        e.x, e.y, e.n, e.op, e.src_dtype, e.dst_dtype = ptr(x), ptr(y), x.numel(), L.ELT_GELU, dt(x), dt(y)
-        self._emit(op, name, 0.0, 2.0 * x.numel() * x.element_size(), (x, y))
+        y = Builder.eltwise(self, x, L.ELT_GELU, name=name)
 
         def backward():
             dy = self.pop_grad(y)

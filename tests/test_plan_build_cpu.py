@@ -10,19 +10,22 @@ from mv_ldm_amd import _lib as L
 from mv_ldm_amd import modules, mvunet, ops, pipeline, plan, runtime, vae
 
 
+def fake_pack_weight(w, dtype, c_pad=None, geglu=False, c_split=None):
+    """`ops.pack_weight` without a device: the shapes of the pack, no data (tools/plan_dump.py records with it too)"""
+    n_out, c_in = w.shape[0], w.shape[1]
+    k = w.shape[2] if w.ndim == 4 else 1
+    e = ops.epc(dtype)
+    c_pad = (c_in + e - 1) // e * e if c_pad is None else c_pad
+    bk = 32 if dtype == torch.float32 else 64
+    k_pad = (k * k * c_pad + bk - 1) // bk * bk
+    n_pad = (n_out + 63) // 64 * 64
+    k_order = int(c_pad % bk == 0 and (c_split is None or c_split % bk == 0))
+    return ops.PackedWeight(torch.empty(0), n_out, n_pad, k_pad, c_pad, k, geglu, k_order)
+
+
 @pytest.fixture()
 def cpu_record(monkeypatch):
-    def fake_pack(w, dtype, c_pad=None, geglu=False, c_split=None):
-        n_out, c_in = w.shape[0], w.shape[1]
-        k = w.shape[2] if w.ndim == 4 else 1
-        e = ops.epc(dtype)
-        c_pad = (c_in + e - 1) // e * e if c_pad is None else c_pad
-        bk = 32 if dtype == torch.float32 else 64
-        k_pad = (k * k * c_pad + bk - 1) // bk * bk
-        n_pad = (n_out + 63) // 64 * 64
-        k_order = int(c_pad % bk == 0 and (c_split is None or c_split % bk == 0))
-        return ops.PackedWeight(torch.empty(0), n_out, n_pad, k_pad, c_pad, k, geglu, k_order)
-    monkeypatch.setattr(ops, "pack_weight", fake_pack)
+    monkeypatch.setattr(ops, "pack_weight", fake_pack_weight)
     for mod in (modules, mvunet, runtime, vae):
         monkeypatch.setattr(mod, "require_gpu", lambda t: None, raising=False)
     L.load()
@@ -263,3 +266,49 @@ def test_tail_drop_structure(cpu_record):
     assert len(att) == 1 and att[0].u.attention.max_q_len == 4 * 1024 and att[0].u.attention.n_seg == 4
     f_full, f_cut = sum(mm.flops for mm in full.meta), sum(mm.flops for mm in cut.meta)
     assert 0.985 < f_cut / f_full < 0.999
+
+
+def _fields(d):
+    return {name: getattr(d, name) for name, _ in L.IgemmDesc._fields_}
+
+
+@pytest.mark.parametrize("case", ["conv3x3", "two_source_1x1", "linear_residual_wide_out", "upsample_phase"])
+def test_builder_records_the_descriptor_an_eager_call_fills(cpu_record, case):
+    """one filler (`ops.igemm_desc`): for the same tensors a `Builder` records, field by field, the descriptor an eager call gets;
+    only what is the caller's policy may differ -- the split-K workspace (eager: sized per launch; Builder: the plan's own), the
+    split count that follows from having one, and the tile (Builder: MVLDM_IGEMM_TILE, the tile-15 rule)"""
+    policy = {"workspace", "workspace_bytes", "splitk", "tile"}
+    bf = torch.bfloat16
+    b = plan.Builder("cpu", bf, record=True, splitk_ws_bytes=1 << 20)
+    bias = torch.zeros(64)
+    if case == "conv3x3":
+        x = torch.zeros(2, 8, 8, 64, dtype=bf)
+        pw = ops.pack_weight(torch.empty(64, 64, 3, 3), bf)
+        out = b.conv(x, pw, bias, name=case)
+        eager = ops.igemm_desc(x, None, pw, out, n_img=2, h_in=8, w_in=8, h_out=8, w_out=8, bias=bias)
+    elif case == "two_source_1x1":
+        x, x2 = torch.zeros(2, 8, 8, 64, dtype=bf), torch.zeros(2, 8, 8, 64, dtype=bf)
+        pw = ops.pack_weight(torch.empty(64, 128, 1, 1), bf, c_split=64)
+        out = b.conv(x, pw, bias, x2=x2, name=case)
+        eager = ops.igemm_desc(x, x2, pw, out, n_img=2, h_in=8, w_in=8, h_out=8, w_out=8, bias=bias)
+    elif case == "linear_residual_wide_out":
+        x, res, wide = torch.zeros(48, 64, dtype=bf), torch.zeros(48, 64, dtype=bf), torch.zeros(48, 192, dtype=bf)
+        pw = ops.pack_weight(torch.empty(64, 64), bf)
+        b.linear(x, pw, bias, residual=res, out=wide, name=case)
+        eager = ops.igemm_desc(x.view(48, 1, 1, 64), None, pw, wide.view(48, 1, 1, 192), n_img=48, h_in=1, w_in=1, h_out=1, w_out=1,
+                               bias=bias, residual=res.view(48, 1, 1, 64))
+        assert eager.dst_ld == 192
+    else:
+        x = torch.zeros(2, 8, 8, 64, dtype=bf)
+        pw = ops.pack_weight(torch.empty(64, 64, 2, 2), bf)
+        out = b.conv_upsample_phases(x, [pw] * 4, bias, name=case)
+        assert out.shape == (2, 16, 16, 64) and [mm.name for mm in b.meta] == [f"{case}.p{i}" for i in range(4)]
+        eager = ops.igemm_desc(x, None, pw, out, n_img=2, h_in=8, w_in=8, h_out=8, w_out=8, stride=1, pad=0, upsample=2 + 3, bias=bias)
+    assert b.meta[-1].kind == L.OP_IGEMM
+    got, want = _fields(b.ops[-1].u.igemm), _fields(eager)
+    assert got["src0"] == x.data_ptr() and got["dst"] and got["bias"] == bias.data_ptr()      # (the comparison is not None against None)
+    differ = {k for k in want if got[k] != want[k]}
+    assert differ <= policy, {k: (got[k], want[k]) for k in differ - policy}
+    # the four really are the caller's: the plan brings its workspace and leaves the split to the library, the bare descriptor has neither
+    assert got["workspace"] and got["workspace_bytes"] == 1 << 20 and got["splitk"] == 0 and want["workspace"] is None and want["splitk"] == 1
+    assert policy <= set(want)
