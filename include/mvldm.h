@@ -29,7 +29,9 @@ extern "C" {
  * unchanged (additive).
  * 4 (round 5): + mvldm_pack_skinny and tile 15 / k_order 2 of mvldm_igemm_fwd (the skinny-M weight-streaming GEMM); additive over 3.
  * 5 (round 6): + tile 19 of mvldm_igemm_fwd (register-staged Linear), tile 13's bits 13 / 14, mvldm_build_flags; additive over 4.
- * 7: + mvldm_image_metrics, mvldm_image_metrics_workspace_bytes; additive over 6. */
+ * 7: + mvldm_image_metrics, mvldm_image_metrics_workspace_bytes; additive over 6.
+ *    + mvldm_lpips_prep / _relu / _tap / _fold, mvldm_lpips_workspace_bytes, mvldm_lpips_tap_slots (LPIPS around the implicit GEMM): new
+ *    symbols only, no struct, enum or op kind changes, so the number stays 7. */
 #define MVLDM_ABI_VERSION 7
 
 typedef void* mvldm_stream_t; /* hipStream_t */
@@ -473,6 +475,40 @@ int mvldm_attention_merge(const void* oa, const float* lse_a, const void* ob, co
 size_t mvldm_image_metrics_workspace_bytes(int n_img, int c, int h, int w);
 int mvldm_image_metrics(const float* pred, const float* gt, int n_img, int c, int h, int w, int use_sample_covariance, float* psnr,
                         float* ssim, double* workspace, size_t workspace_bytes, mvldm_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * LPIPS: the glue between the thirteen 3x3 convolutions of LPIPS(net="vgg")'s VGG-16 trunk (mvldm_igemm_fwd, with their bias) and
+ * the per-pixel distance.
+ *   replaces  compute_lpips (src/evaluation/metrics.py:43-54): lpips.LPIPS(net="vgg").forward(ground_truth, predicted,
+ *             normalize=True)[:, 0, 0, 0] -- the package's ScalingLayer, vgg16.features slices relu1_2 / 2_2 / 3_3 / 4_3 / 5_3,
+ *             normalize_tensor (x / (sqrt(sum_c x^2) + 1e-10)), the 1x1 `lin` layers and spatial_average, summed over the five taps.
+ * A pair batch is 2 n_img NHWC images in the compute dtype `dtype`: rows [0, n_img) the first input, rows [n_img, 2 n_img) the
+ * second.  All four run eagerly on `stream`, never synchronise or allocate, and refuse on the host before any launch (src/evaluation/metrics.py:43-54
+ * for each):
+ *   mvldm_lpips_prep   in0, in1: fp32 NCHW [n_img][3][h][w] -> dst NHWC [2 n_img][h][w][c_pad], x' = ((2x - 1) - shift_c) / scale_c
+ *                      with shift = (-.030, -.088, -.188), scale = (.458, .448, .450); the 2x - 1 only when normalize != 0; inputs not
+ *                      clipped; c_pad = 4 (f32) / 8 (16 bit), the pad channels zero.  Refused: h or w < 16 (four pool stages need one
+ *                      pixel left), a null pointer.
+ *   mvldm_lpips_relu   in-place ReLU of n elements (a multiple of the 16-byte chunk): after the convs that are no tap.
+ *   mvldm_lpips_tap    feat: the PRE-activation output [2 n_img][h][w][c] of a stage's last conv; weight: fp32 [c], the stage's lin
+ *                      layer.  Per pixel of pair i, with a = relu(feat[i]), b = relu(feat[n_img + i]), na = sqrt(sum_c a_c^2):
+ *                      d = sum_c weight_c (a_c / (na + 1e-10) - b_c / (nb + 1e-10))^2, summed in fp32 over channels and a wave's pixels,
+ *                      then in fp64: workgroup k of image i writes workspace[i * slots_per_image + slot0 + k], k <
+ *                      mvldm_lpips_tap_slots(h, w, c) (no atomics: the same bits on every run, for every n_img and position).
+ *                      pooled (may be null): the 2x2 max-pooled ReLU map [2 n_img][h / 2][w / 2][c]; a last odd row / column is not
+ *                      pooled and still counts in d.  Refused: c no multiple of 64 or > 512, a workspace that is too small, a null pointer.
+ *   mvldm_lpips_fold   out[i] (fp32) = sum over the taps l = 0..4 of (sum of tap l's partials of image i) / ((h >> l)(w >> l)), for
+ *                      the layout mvldm_lpips_workspace_bytes(n_img, h, w) describes: per image the slots of tap 0 (h x w, 64
+ *                      channels), tap 1 (h/2 x w/2, 128), tap 2 (256), tap 3 (512), tap 4 (512), in this order.
+ * mvldm_lpips_workspace_bytes is 0 for a refused shape (n_img < 1, h or w < 16), mvldm_lpips_tap_slots for a refused map or c. */
+size_t mvldm_lpips_workspace_bytes(int n_img, int h, int w);
+int mvldm_lpips_tap_slots(int h, int w, int c);
+int mvldm_lpips_prep(const float* in0, const float* in1, void* dst, int n_img, int h, int w, int c_pad, int dtype, int normalize,
+                     mvldm_stream_t stream);
+int mvldm_lpips_relu(void* x, size_t n, int dtype, mvldm_stream_t stream);
+int mvldm_lpips_tap(const void* feat, const float* weight, void* pooled, int n_img, int h, int w, int c, int dtype, double* workspace,
+                    size_t workspace_bytes, int slot0, int slots_per_image, mvldm_stream_t stream);
+int mvldm_lpips_fold(const double* workspace, size_t workspace_bytes, int n_img, int h, int w, float* out, mvldm_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Plans: a whole forward (UNet walk, VAE decoder, DDIM step) as a flat list of the ops above with

@@ -2,11 +2,14 @@
 `compute_ssim` :58-73) and of `metric_computer.test_step`, which walks the PNG tree `test_step` wrote.
 
 The reference pulls every image to the host and runs skimage one image at a time; here both scores of a whole batch come from
-one launch of `csrc/metrics.hip` (`ops.image_metrics`).  LPIPS / DISTS / FID need pretrained networks and are not provided.
+one launch of `csrc/metrics.hip` (`ops.image_metrics`).  LPIPS (`compute_lpips`, :43-54) runs on the device too -- its VGG-16 trunk
+through the implicit GEMM, the distance in `csrc/lpips.hip` (`mv_ldm_amd.lpips.LPIPS`) -- with the weight files the user brings: none
+ships with the package and none is fetched.  DISTS / FID need other networks and are not provided.
 
-    python -m mv_ldm_amd.metrics --pred DIR --gt DIR [--json OUT]
+    python -m mv_ldm_amd.metrics --pred DIR --gt DIR [--json OUT] [--lpips VGG.pth [--lpips-lin LIN.pth]]
 
 pairs `DIR/<scene>/color/<index>.png` of the two trees by scene and frame index and prints per-scene and overall means.
+`--lpips`: a full `lpips.LPIPS(net="vgg").state_dict()`, or torchvision's VGG-16 with the package's `vgg.pth` as `--lpips-lin`.
 """
 from __future__ import annotations
 
@@ -45,6 +48,27 @@ def compute_ssim(ground_truth: torch.Tensor, predicted: torch.Tensor, use_sample
     return image_metrics(ground_truth, predicted, use_sample_covariance)[1]
 
 
+def compute_lpips(ground_truth: torch.Tensor, predicted: torch.Tensor, model) -> torch.Tensor:
+    """src/evaluation/metrics.py:43-54: `model.forward(ground_truth, predicted, normalize=True)[:, 0, 0, 0]` with `model` an
+    `mv_ldm_amd.lpips.LPIPS` on the inputs' device; `[batch, 3, h, w]` -> `[batch]`, or `[b, v, 3, h, w]` -> `[b, v]`, fp32"""
+    if ground_truth.shape != predicted.shape:
+        raise ValueError(f"ground truth {tuple(ground_truth.shape)} against prediction {tuple(predicted.shape)}")
+    if ground_truth.dim() not in (4, 5):
+        raise ValueError(f"expected [batch, c, h, w] or [b, v, c, h, w], got {tuple(ground_truth.shape)}")
+    if not (ground_truth.is_contiguous() and predicted.is_contiguous()):
+        raise ValueError("compute_lpips: inputs must be contiguous (call .contiguous() first)")
+    lead = ground_truth.shape[:-3]
+    flat = lambda t: t.reshape(-1, *t.shape[-3:])
+    value = model(flat(ground_truth), flat(predicted), normalize=True)
+    return value[:, 0, 0, 0].reshape(lead)
+
+
+def load_lpips(weights, lin=None, device="cuda", dtype: torch.dtype = torch.float32):
+    """the `--lpips VGG.pth [--lpips-lin LIN.pth]` of the command lines: an `LPIPS` with the user's weights on `device`"""
+    from .lpips import LPIPS
+    return LPIPS(net="vgg", weights=weights, lin=lin, dtype=dtype).to(device)
+
+
 # ---- PNG trees ---------------------------------------------------------------------------------------------------
 def scan_tree(root) -> Dict[str, Dict[int, Path]]:
     """{scene: {frame index: path}} of `root/<scene>/color/<index>.png`; the index is the file stem as an integer (`000012.png`
@@ -79,16 +103,19 @@ def pair_trees(pred: Dict[str, Dict[int, object]], gt: Dict[str, Dict[int, objec
 
 
 def summarize(per_frame: Dict[str, Dict[int, List[float]]]) -> dict:
-    """{scene: {index: [psnr, ssim]}} -> the report: per-scene means, the overall mean over all frames"""
+    """{scene: {index: [psnr, ssim]}} -> the report: per-scene means, the overall mean over all frames.  Rows scored with an LPIPS
+    network are [psnr, ssim, lpips]: the report then carries "lpips" next to "psnr" and "ssim"."""
     mean = lambda v: sum(v) / len(v) if v else float("nan")
-    scenes = {s: {"psnr": mean([a for a, _ in f.values()]), "ssim": mean([b for _, b in f.values()]), "frames": len(f), "per_frame": f}
-              for s, f in per_frame.items()}
     every = [v for f in per_frame.values() for v in f.values()]
-    return {"scenes": scenes, "overall": {"psnr": mean([a for a, _ in every]), "ssim": mean([b for _, b in every]), "frames": len(every)}}
+    names = ("psnr", "ssim", "lpips") if every and all(len(v) == 3 for v in every) else ("psnr", "ssim")
+    means = lambda rows: {k: mean([v[j] for v in rows]) for j, k in enumerate(names)}
+    scenes = {s: {**means(list(f.values())), "frames": len(f), "per_frame": f} for s, f in per_frame.items()}
+    return {"scenes": scenes, "overall": {**means(every), "frames": len(every)}}
 
 
-def score_trees(pred_dir, gt_dir, device="cuda", batch: int = 64) -> dict:
-    """`metric_computer.test_step` over two PNG trees: every paired frame scored on the device, `batch` frames per launch"""
+def score_trees(pred_dir, gt_dir, device="cuda", batch: int = 64, lpips=None) -> dict:
+    """`metric_computer.test_step` over two PNG trees: every paired frame scored on the device, `batch` frames per launch.
+    `lpips`: an `LPIPS` network on `device`; the per-frame rows then grow from [psnr, ssim] to [psnr, ssim, lpips]"""
     from .image_io import load_image
     pairs, missing = pair_trees(scan_tree(pred_dir), scan_tree(gt_dir))
     per_frame: Dict[str, Dict[int, List[float]]] = {}
@@ -99,28 +126,34 @@ def score_trees(pred_dir, gt_dir, device="cuda", batch: int = 64) -> dict:
             p = torch.stack([load_image(a) for _, a, _ in chunk]).to(device)
             g = torch.stack([load_image(b) for _, _, b in chunk]).to(device)
             psnr, ssim = image_metrics(g, p)
-            for (i, _, _), a, b in zip(chunk, psnr.tolist(), ssim.tolist()):
-                per_frame[scene][i] = [a, b]
+            rows = [psnr.tolist(), ssim.tolist()] + ([] if lpips is None else [compute_lpips(g, p, lpips).tolist()])
+            for (i, _, _), *row in zip(chunk, *rows):
+                per_frame[scene][i] = row
     rep = summarize(per_frame)
     rep["missing"] = [list(m) for m in missing]
     return rep
 
 
 def main(argv=None):
-    ap = argparse.ArgumentParser(description="PSNR / SSIM of DIR/<scene>/color/<index>.png against a ground-truth tree of the same layout")
+    ap = argparse.ArgumentParser(description="PSNR / SSIM (/ LPIPS) of DIR/<scene>/color/<index>.png against a ground-truth tree of the same layout")
     ap.add_argument("--pred", required=True)
     ap.add_argument("--gt", required=True)
     ap.add_argument("--json", default=None, help="write the full report (per frame) here")
+    ap.add_argument("--lpips", default=None, help="LPIPS(net='vgg') weights: the package's full state dict, or torchvision's VGG-16 (then --lpips-lin too); adds lpips")
+    ap.add_argument("--lpips-lin", default=None, help="the lpips package's vgg.pth (lin layers), with a torchvision VGG-16 as --lpips")
     args = ap.parse_args(argv)
+    if args.lpips_lin and not args.lpips:
+        ap.error("--lpips-lin goes with --lpips")
     if not torch.cuda.is_available():
         raise SystemExit("metrics needs a GPU (the HIP path has no CPU fallback)")
-    rep = score_trees(args.pred, args.gt)
+    rep = score_trees(args.pred, args.gt, lpips=load_lpips(args.lpips, args.lpips_lin) if args.lpips else None)
     for kind, scene, index, side in rep["missing"]:
         print(f"skipped {kind} {scene}" + ("" if index is None else f"/{index}") + f": missing in --{side}")
+    extra = lambda r: f" lpips {r['lpips']:.6f}" if "lpips" in r else ""
     for s, r in rep["scenes"].items():
-        print(f"{s}: psnr {r['psnr']:.4f} ssim {r['ssim']:.6f} ({r['frames']} frames)")
+        print(f"{s}: psnr {r['psnr']:.4f} ssim {r['ssim']:.6f}{extra(r)} ({r['frames']} frames)")
     o = rep["overall"]
-    print(f"overall: psnr {o['psnr']:.4f} ssim {o['ssim']:.6f} ({o['frames']} frames)")
+    print(f"overall: psnr {o['psnr']:.4f} ssim {o['ssim']:.6f}{extra(o)} ({o['frames']} frames)")
     if args.json:
         Path(args.json).write_text(json.dumps(rep, indent=1))
     return 0

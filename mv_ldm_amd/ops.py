@@ -656,3 +656,53 @@ def image_metrics(pred: torch.Tensor, gt: torch.Tensor, use_sample_covariance: b
     L.check(L.load().mvldm_image_metrics(pred.data_ptr(), gt.data_ptr(), n, c, h, w, int(bool(use_sample_covariance)), psnr.data_ptr(),
                                          ssim.data_ptr(), ws.data_ptr(), ws.numel() * ws.element_size(), stream()))
     return psnr, ssim
+
+
+# ------------------------------------------------------------------------------------------ LPIPS glue (csrc/lpips.hip)
+LPIPS_CHANNELS = (64, 128, 256, 512, 512)      # the five taps of LPIPS(net="vgg"): relu1_2, 2_2, 3_3, 4_3, 5_3
+LPIPS_MIN_EDGE = 16                            # four 2x2 pools must leave one pixel
+
+
+def lpips_workspace_bytes(n_img: int, h: int, w: int) -> int:
+    """bytes of fp64 partials `lpips_tap` x 5 + `lpips_fold` need for `n_img` pairs of h x w images; 0 for a refused shape"""
+    return int(L.load().mvldm_lpips_workspace_bytes(n_img, h, w))
+
+
+def lpips_tap_slots(h: int, w: int, c: int) -> int:
+    """partials (workgroups) per image of one tap over an h x w map of c channels; 0 for a refused map"""
+    return int(L.load().mvldm_lpips_tap_slots(h, w, c))
+
+
+def lpips_prep(in0: torch.Tensor, in1: torch.Tensor, dtype: torch.dtype, normalize: bool) -> torch.Tensor:
+    """two fp32 NCHW `[n, 3, h, w]` -> NHWC `[2n, h, w, c_pad]` in `dtype` (rows [0, n): in0), through the package's ScalingLayer"""
+    n, _, h, w = in0.shape
+    dst = torch.empty(2 * n, h, w, epc(dtype), dtype=dtype, device=in0.device)
+    L.check(L.load().mvldm_lpips_prep(in0.data_ptr(), in1.data_ptr(), dst.data_ptr(), n, h, w, dst.shape[-1], dt(dtype), int(bool(normalize)), stream()))
+    return dst
+
+
+def lpips_relu(x: torch.Tensor) -> torch.Tensor:
+    """in-place ReLU of a contiguous conv output"""
+    assert x.is_cuda and x.is_contiguous()
+    L.check(L.load().mvldm_lpips_relu(x.data_ptr(), x.numel(), dt(x), stream()))
+    return x
+
+
+def lpips_tap(feat: torch.Tensor, weight: torch.Tensor, ws: torch.Tensor, slot0: int, slots: int, pool: bool = True) -> Optional[torch.Tensor]:
+    """feat: the pre-activation NHWC `[2n, h, w, c]` output of a stage's last conv; weight: fp32 `[c]`.  Writes the stage's distance
+    partials of the n pairs to slots [slot0, slot0 + lpips_tap_slots) of `ws` (uint8, `slots` fp64 per image) and returns the 2x2
+    max-pooled ReLU map `[2n, h // 2, w // 2, c]` (None when `pool` is False: the last tap)"""
+    assert feat.is_cuda and feat.is_contiguous() and feat.dim() == 4 and feat.shape[0] % 2 == 0
+    assert weight.dtype == torch.float32 and weight.is_contiguous() and weight.numel() == feat.shape[-1]
+    n2, h, w, c = feat.shape
+    pooled = torch.empty(n2, h // 2, w // 2, c, dtype=feat.dtype, device=feat.device) if pool else None
+    L.check(L.load().mvldm_lpips_tap(feat.data_ptr(), weight.data_ptr(), ptr(pooled), n2 // 2, h, w, c, dt(feat), ws.data_ptr(),
+                                     ws.numel() * ws.element_size(), slot0, slots, stream()))
+    return pooled
+
+
+def lpips_fold(ws: torch.Tensor, n_img: int, h: int, w: int, out: torch.Tensor) -> torch.Tensor:
+    """out fp32 `[n_img]` (any shape of n_img elements) = the five layer means of the partials in `ws`, summed"""
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() == n_img
+    L.check(L.load().mvldm_lpips_fold(ws.data_ptr(), ws.numel() * ws.element_size(), n_img, h, w, out.data_ptr(), stream()))
+    return out
