@@ -808,14 +808,25 @@ __global__ __launch_bounds__(256) void attn_merge_kernel(const T* __restrict__ o
         const size_t ra = (size_t)a_img[k] * tokens + t, rb = (size_t)b_img[k] * tokens + t, ro = (size_t)out_img[k] * tokens + t;
         const int head = c * EPC / d;
         const float la = lse_a[(size_t)head * lla + ra], lb = lse_b[(size_t)head * llb + rb];
-        const float mx = fmaxf(la, lb);
-        const float ea = __builtin_amdgcn_exp2f(la - mx), eb = __builtin_amdgcn_exp2f(lb - mx);
-        const float inv = 1.0f / (ea + eb);
-        const float wa = ea * inv, wb = eb * inv;
         const Chunk<T> va = load_chunk<T>(oa + ra * ld_a + c * EPC), vb = load_chunk<T>(ob + rb * ld_b + c * EPC);
         Chunk<T> o;
+        if constexpr (sizeof(T) == 4) {
+            // f32: weights and sum in fp64, rounded once.  Where the two sides cancel, fp32 weights carry 2^-24 of each TERM, many ulps
+            // of the result (measured: up to 78 x a bound of 2^-22 |result|); the 16-bit outputs round far coarser than that.
+            const double mx = fmax((double)la, (double)lb);
+            const double ea = exp2((double)la - mx), eb = exp2((double)lb - mx);
+            const double inv = 1.0 / (ea + eb);
+            const double wa = ea * inv, wb = eb * inv;
 #pragma unroll
-        for (int e = 0; e < EPC; ++e) o.set(e, va.get(e) * wa + vb.get(e) * wb);
+            for (int e = 0; e < EPC; ++e) o.set(e, (float)((double)va.get(e) * wa + (double)vb.get(e) * wb));
+        } else {
+            const float mx = fmaxf(la, lb);
+            const float ea = __builtin_amdgcn_exp2f(la - mx), eb = __builtin_amdgcn_exp2f(lb - mx);
+            const float inv = 1.0f / (ea + eb);
+            const float wa = ea * inv, wb = eb * inv;
+#pragma unroll
+            for (int e = 0; e < EPC; ++e) o.set(e, va.get(e) * wa + vb.get(e) * wb);
+        }
         store_chunk<T>(out + ro * ld_o + c * EPC, o);
     }
 }

@@ -226,15 +226,21 @@ def igemm_desc(src0, src1, pw: PackedWeight, dst, *, n_img, h_in, w_in, h_out, w
 
 
 def conv2d(x: torch.Tensor, pw: PackedWeight, bias=None, *, x2=None, stride=1, pad=None, upsample=False, row_bias=None,
-           residual=None, epilogue=L.EPI_NONE, out_dtype=None, out_scale=1.0, splitk=0, tile=0, out=None) -> torch.Tensor:
+           residual=None, epilogue=L.EPI_NONE, out_dtype=None, out_scale=1.0, splitk=0, tile=0, out=None, dst=None) -> torch.Tensor:
     """x: NHWC `[n, h, w, c]`; x2: optional second source concatenated along c.  Returns NHWC.  `out`: write into this tensor
-    (it may be the residual: x += f(x))."""
+    (it may be the residual: x += f(x)).  `dst`: rows of a WIDER buffer instead -- a contiguous `[n, ho, wo, dst_ld]` tensor with
+    dst_ld > n_dst whose columns [0, n_dst) are written (`[n, 2 ho, 2 wo, dst_ld]` for a phase conv, which scatters); returned as is."""
     assert x.is_cuda and x.is_contiguous() and (x2 is None or x2.is_contiguous())
     n, h, w, _ = x.shape
     pad = (pw.ksize // 2) if pad is None else pad
     ho, wo = conv_out_hw(h, w, pw.ksize, stride, pad, upsample)
     n_dst = pw.n_out // 2 if epilogue == L.EPI_GEGLU else pw.n_out
-    if out is None:
+    if dst is not None:
+        up = 2 if int(upsample) >= 2 else 1
+        assert out is None and dst.is_contiguous() and dst.dtype == (out_dtype or x.dtype) and dst.shape[-1] > n_dst
+        assert dst.numel() == n * up * ho * up * wo * dst.shape[-1]
+        out = dst
+    elif out is None:
         out = torch.empty(n, ho, wo, n_dst, dtype=out_dtype or x.dtype, device=x.device)
     else:
         assert out.is_contiguous() and out.numel() == n * ho * wo * n_dst and out.dtype == (out_dtype or x.dtype)
@@ -283,34 +289,42 @@ def conv2d_upsample_phases(x: torch.Tensor, pws, bias=None, tile=0, splitk=0) ->
 
 
 def linear(x: torch.Tensor, pw: PackedWeight, bias=None, *, residual=None, epilogue=L.EPI_NONE, out_dtype=None,
-           splitk=0, tile=0, out=None) -> torch.Tensor:
-    """x: `[rows, c]` token matrix."""
+           splitk=0, tile=0, out=None, dst=None) -> torch.Tensor:
+    """x: `[rows, c]` token matrix.  `dst`: a contiguous `[rows, dst_ld]` buffer wider than the output (see conv2d)."""
     rows, c = x.shape
     y = conv2d(x.view(rows, 1, 1, c), pw, bias, residual=None if residual is None else residual.view(rows, 1, 1, -1),
-               epilogue=epilogue, out_dtype=out_dtype, splitk=splitk, tile=tile, out=out)
+               epilogue=epilogue, out_dtype=out_dtype, splitk=splitk, tile=tile, out=out, dst=None if dst is None else dst.view(rows, 1, 1, -1))
     return y.view(rows, -1)
 
 
 # ------------------------------------------------------------------------------------------ norms
-def groupnorm(x: torch.Tensor, gamma, beta, groups: int, eps: float, silu: bool, x2=None, stats_out=None) -> torch.Tensor:
+def groupnorm(x: torch.Tensor, gamma, beta, groups: int, eps: float, silu: bool, x2=None, stats_out=None, out=None) -> torch.Tensor:
     """x NHWC `[n, h, w, c]` (or `[n, hw, c]`); x2: optional second source concatenated along c.
-    stats_out: optional fp32 `[n, groups, 2]` receiving (mean, rstd) for the backward pass."""
+    stats_out: optional fp32 `[n, groups, 2]` receiving (mean, rstd) for the backward pass.  `out`: write into this contiguous tensor."""
     assert x.is_cuda and x.is_contiguous() and (x2 is None or x2.is_contiguous())
     n, c0 = x.shape[0], x.shape[-1]
     c1 = 0 if x2 is None else x2.shape[-1]
     hw = math.prod(x.shape[1:-1])
-    y = torch.empty(*x.shape[:-1], c0 + c1, dtype=x.dtype, device=x.device)
+    if out is None:
+        y = torch.empty(*x.shape[:-1], c0 + c1, dtype=x.dtype, device=x.device)
+    else:
+        assert out.is_contiguous() and out.dtype == x.dtype and out.numel() == n * hw * (c0 + c1)
+        y = out.view(*x.shape[:-1], c0 + c1)
     ws = workspace(max(n, 1) * L.GN_MAX_CHUNKS * groups * 2 * 8, x.device, "gn")
     L.check(L.load().mvldm_groupnorm_fwd(x.data_ptr(), ptr(x2), y.data_ptr(), gamma.data_ptr(), beta.data_ptr(), n, hw, c0, c1,
                                          groups, eps, int(silu), dt(x), ws.data_ptr(), ptr(stats_out), stream()))
     return y
 
 
-def layernorm(x: torch.Tensor, gamma, beta, eps: float = 1e-5) -> torch.Tensor:
+def layernorm(x: torch.Tensor, gamma, beta, eps: float = 1e-5, out=None) -> torch.Tensor:
     assert x.is_cuda and x.is_contiguous()
     c = x.shape[-1]
     rows = x.numel() // c
-    y = torch.empty_like(x)
+    if out is None:
+        y = torch.empty_like(x)
+    else:
+        assert out.is_contiguous() and out.dtype == x.dtype and out.numel() == x.numel()
+        y = out.view(x.shape)
     L.check(L.load().mvldm_layernorm_fwd(x.data_ptr(), y.data_ptr(), gamma.data_ptr(), beta.data_ptr(), rows, c, eps,
                                          dt(x), stream()))
     return y
@@ -328,11 +342,14 @@ def make_segments(q_lens, kv_lens=None, device="cuda") -> torch.Tensor:
 
 
 def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, head_dim: int, seg: torch.Tensor,
-              max_q_len: int, scale: Optional[float] = None, lse: Optional[torch.Tensor] = None) -> torch.Tensor:
+              max_q_len: int, scale: Optional[float] = None, lse: Optional[torch.Tensor] = None, out=None) -> torch.Tensor:
     """q/k/v: 2-D row-major views `[tokens, >= heads*head_dim]` (may be column slices of one fused
-    projection: only the row stride is used).  Returns `[q_tokens, heads*head_dim]`."""
+    projection: only the row stride is used).  Returns `[q_tokens, heads*head_dim]`.  `out`: write into this 2-D view (unit column
+    stride, any row stride); `lse`: fp32 `[heads, >= q_tokens]` receiving the log2-domain log-sum-exp."""
     assert q.is_cuda and q.stride(1) == 1 and k.stride(1) == 1 and v.stride(1) == 1
-    out = torch.empty(q.shape[0], heads * head_dim, dtype=q.dtype, device=q.device)
+    if out is None:
+        out = torch.empty(q.shape[0], heads * head_dim, dtype=q.dtype, device=q.device)
+    assert out.stride(1) == 1 and out.dtype == q.dtype and out.shape[1] == heads * head_dim
     scale = head_dim ** -0.5 if scale is None else scale
     L.check(L.load().mvldm_attention_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), q.stride(0), k.stride(0),
                                          v.stride(0), out.stride(0), heads, head_dim, seg.data_ptr(), seg.shape[0],
@@ -340,7 +357,37 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, hea
     return out
 
 
+def attention_merge(oa, lse_a, ob, lse_b, a_img, b_img, out_img, tokens: int, heads: int, head_dim: int, out=None) -> torch.Tensor:
+    """combine two attention results of the same queries over disjoint key sets (`mvldm_attention_merge`).  oa / ob / out: 2-D views
+    `[rows, >= heads*head_dim]` with unit column stride; lse_a / lse_b: fp32 `[heads, lse_ld]` (log2 domain, from `attention(lse=)`);
+    a_img / b_img / out_img: int32 `[n_img]` image maps over images of `tokens` rows.  `out` may be oa or ob."""
+    assert oa.is_cuda and oa.dtype == ob.dtype and oa.stride(1) == 1 and ob.stride(1) == 1
+    assert all(t.dtype == torch.int32 and t.numel() == a_img.numel() for t in (a_img, b_img, out_img))
+    if out is None:
+        out = torch.empty(int(out_img.numel()) * tokens, heads * head_dim, dtype=oa.dtype, device=oa.device)
+    assert out.stride(1) == 1 and out.dtype == oa.dtype
+    L.check(L.load().mvldm_attention_merge(oa.data_ptr(), lse_a.data_ptr(), ob.data_ptr(), lse_b.data_ptr(), out.data_ptr(), a_img.data_ptr(),
+                                           b_img.data_ptr(), out_img.data_ptr(), a_img.numel(), tokens, heads, head_dim, oa.stride(0), ob.stride(0),
+                                           out.stride(0), lse_a.stride(0), lse_b.stride(0), dt(oa), stream()))
+    return out
+
+
 # ------------------------------------------------------------------------------------------ small ops
+def gather_rows(src: torch.Tensor, dst: torch.Tensor, src_index=None, dst_index=None, n_rows: Optional[int] = None) -> torch.Tensor:
+    """dst row (dst_index[k] or k) = src row (src_index[k] or k), k < n_rows (`mvldm_gather_rows`).  src / dst: contiguous 2-D
+    tensors of equal row size (a multiple of 16 bytes); the index vectors are int32 device tensors.  src may be dst when no
+    destination row is also a source row."""
+    assert src.is_cuda and src.is_contiguous() and dst.is_contiguous() and src.dim() == 2 and dst.dim() == 2
+    row_bytes = src.shape[1] * src.element_size()
+    assert row_bytes == dst.shape[1] * dst.element_size()
+    for t in (src_index, dst_index):
+        assert t is None or (t.dtype == torch.int32 and t.is_cuda and t.is_contiguous())
+    if n_rows is None:
+        n_rows = src_index.numel() if src_index is not None else dst_index.numel() if dst_index is not None else min(src.shape[0], dst.shape[0])
+    L.check(L.load().mvldm_gather_rows(src.data_ptr(), dst.data_ptr(), ptr(src_index), ptr(dst_index), n_rows, row_bytes, stream()))
+    return dst
+
+
 def timestep_embed(timesteps: torch.Tensor, freqs: torch.Tensor, dim: int, flip_sin_to_cos: bool,
                    dtype=torch.float32) -> torch.Tensor:
     assert timesteps.dtype == torch.int64 and timesteps.is_cuda
