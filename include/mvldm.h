@@ -31,7 +31,9 @@ extern "C" {
  * 5 (round 6): + tile 19 of mvldm_igemm_fwd (register-staged Linear), tile 13's bits 13 / 14, mvldm_build_flags; additive over 4.
  * 7: + mvldm_image_metrics, mvldm_image_metrics_workspace_bytes; additive over 6.
  *    + mvldm_lpips_prep / _relu / _tap / _fold, mvldm_lpips_workspace_bytes, mvldm_lpips_tap_slots (LPIPS around the implicit GEMM): new
- *    symbols only, no struct, enum or op kind changes, so the number stays 7. */
+ *    symbols only, no struct, enum or op kind changes, so the number stays 7.
+ *    + mvldm_dists_prep / _stats / _l2pool / _fold, mvldm_dists_workspace_bytes, mvldm_dists_stat_slots (DISTS around the implicit GEMM):
+ *    new symbols only again, the number stays 7. */
 #define MVLDM_ABI_VERSION 7
 
 typedef void* mvldm_stream_t; /* hipStream_t */
@@ -509,6 +511,50 @@ int mvldm_lpips_relu(void* x, size_t n, int dtype, mvldm_stream_t stream);
 int mvldm_lpips_tap(const void* feat, const float* weight, void* pooled, int n_img, int h, int w, int c, int dtype, double* workspace,
                     size_t workspace_bytes, int slot0, int slots_per_image, mvldm_stream_t stream);
 int mvldm_lpips_fold(const double* workspace, size_t workspace_bytes, int n_img, int h, int w, float* out, mvldm_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * DISTS: the glue between the thirteen 3x3 convolutions of DISTS' VGG-16 trunk (mvldm_igemm_fwd, with their bias; the ReLU after the
+ * convs that are no tap is mvldm_lpips_relu) and the structure / texture statistics.
+ *   replaces  compute_dists (src/evaluation/metrics.py:27-40): DISTS_pytorch.DISTS().forward(ground_truth, predicted) -- the trunk
+ *             input (x - mean) / std, vgg16.features cut after relu1_2 / 2_2 / 3_3 / 4_3 / 5_3 with an L2pooling in place of every
+ *             max-pool, and per channel of the six taps (the raw image, then the five stages; 3 + 64 + 128 + 256 + 512 + 512 = 1475
+ *             channels) S1 = (2 mx my + c1) / (mx^2 + my^2 + c1), S2 = (2 cov + c2) / (vx + vy + c2), c1 = c2 = 1e-6, means over the
+ *             map's pixels; score = 1 - sum_c (alpha_c S1_c + beta_c S2_c) / (sum alpha + sum beta).
+ * A pair batch is 2 n_img NHWC images in the compute dtype `dtype`: rows [0, n_img) the first input, rows [n_img, 2 n_img) the
+ * second.  All four run eagerly on `stream`, never synchronise or allocate, and refuse on the host before any launch
+ * (src/evaluation/metrics.py:27-40 for each):
+ *   mvldm_dists_prep    in0, in1: fp32 NCHW [n_img][3][h][w] in [0, 1] (not clipped) -> dst NHWC [2 n_img][h][w][c_pad],
+ *                       x' = (x - mean_c) / std_c with mean = (.485, .456, .406), std = (.229, .224, .225); c_pad = 4 (f32) / 8 (16 bit),
+ *                       the pad channels zero.  Refused: h or w < 1, a null or unaligned pointer.
+ *   mvldm_dists_stats   feat: the PRE-activation output [2 n_img][h][w][c] of a stage's last conv (feat_b null), ReLU applied on load; or,
+ *                       with c = 3 and dtype MVLDM_F32, feat and feat_b the two RAW fp32 NCHW inputs [n_img][3][h][w] (tap 0: never a
+ *                       rounded copy).  Per pair i and channel, with a = relu(feat[i]), b = relu(feat[n_img + i]): the five sums over the
+ *                       pixels  sum a, sum b, sum a^2, sum b^2, sum a b,  accumulated in fp64 from the first product on.  Workgroup k
+ *                       (k < mvldm_dists_stat_slots(h, w, c), a band of 512 pixels at c = 64, 256 above, 4096 at c = 3) writes its
+ *                       partial of sum s, channel ch to workspace[i * doubles_per_pair + offset + (k * 5 + s) * c + ch]
+ *                       (no atomics: the same bits on every run, for every n_img and position).  Refused: c not 3 or a multiple of 64
+ *                       in 64 ... 512, [offset, offset + slots * 5 * c) outside doubles_per_pair, a workspace below
+ *                       n_img * doubles_per_pair * 8 bytes, a null or unaligned pointer, h or w < 1.
+ *   mvldm_dists_l2pool  feat as above (c a multiple of 64) -> out [2 n_img][ceil(h / 2)][ceil(w / 2)][c] =
+ *                       sqrt(sum_{i,j < 3} g_ij relu(feat)[2y - 1 + i][2x - 1 + j]^2 + 1e-12), g = outer((1, 2, 1), (1, 2, 1)) / 16
+ *                       (hanning(5)[1:-1], normalised), zeros outside the map; fp32 arithmetic, rounded once to `dtype` at the store.
+ *   mvldm_dists_fold    out[i] (fp32) = sum_c (alpha_c (mx - my)^2 / (mx^2 + my^2 + c1) + beta_c (vx + vy - 2 cov) / (vx + vy + c2))
+ *                       / (sum alpha + sum beta), which equals the score above and is exactly 0 for identical inputs; fp64, each
+ *                       channel's partials summed in slot order, the channels in a fixed tree.  alpha, beta: fp32 [1475] in tap order.
+ *                       The layout is the one mvldm_dists_workspace_bytes(n_img, h, w) describes: per pair, tap after tap, the
+ *                       slots * 5 * c doubles of tap 0 (h x w, 3 channels), tap 1 (h x w, 64), tap 2 (ceil(h/2) x ceil(w/2), 128),
+ *                       tap 3 (256), tap 4 (512), tap 5 (512), each map half the one before, rounded up.
+ * mvldm_dists_workspace_bytes is 0 for a refused shape (n_img, h or w < 1, or too large), mvldm_dists_stat_slots for a refused map or c.
+ * There is no minimum edge: a 1 x 1 image is valid (every variance is 0, every S2 is c2 / c2 = 1).
+ * Parity with the DISTS_pytorch package and its published weights is unpinned: the arithmetic above is a restatement. */
+size_t mvldm_dists_workspace_bytes(int n_img, int h, int w);
+int mvldm_dists_stat_slots(int h, int w, int c);
+int mvldm_dists_prep(const float* in0, const float* in1, void* dst, int n_img, int h, int w, int c_pad, int dtype, mvldm_stream_t stream);
+int mvldm_dists_stats(const void* feat, const void* feat_b, int n_img, int h, int w, int c, int dtype, double* workspace,
+                      size_t workspace_bytes, int offset, int doubles_per_pair, mvldm_stream_t stream);
+int mvldm_dists_l2pool(const void* feat, void* out, int n_img, int h, int w, int c, int dtype, mvldm_stream_t stream);
+int mvldm_dists_fold(const double* workspace, size_t workspace_bytes, int n_img, int h, int w, const float* alpha, const float* beta,
+                     float* out, mvldm_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Plans: a whole forward (UNet walk, VAE decoder, DDIM step) as a flat list of the ops above with

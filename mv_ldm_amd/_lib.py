@@ -233,6 +233,12 @@ SIGNATURES = {
     "mvldm_lpips_relu": (C.c_int, [vp, sz, C.c_int, vp]),
     "mvldm_lpips_tap": (C.c_int, [vp, vp, vp] + [C.c_int] * 5 + [vp, sz, C.c_int, C.c_int, vp]),
     "mvldm_lpips_fold": (C.c_int, [vp, sz, C.c_int, C.c_int, C.c_int, vp, vp]),
+    "mvldm_dists_workspace_bytes": (sz, [C.c_int] * 3),
+    "mvldm_dists_stat_slots": (C.c_int, [C.c_int] * 3),
+    "mvldm_dists_prep": (C.c_int, [vp, vp, vp] + [C.c_int] * 5 + [vp]),
+    "mvldm_dists_stats": (C.c_int, [vp, vp] + [C.c_int] * 5 + [vp, sz, C.c_int, C.c_int, vp]),
+    "mvldm_dists_l2pool": (C.c_int, [vp, vp] + [C.c_int] * 5 + [vp]),
+    "mvldm_dists_fold": (C.c_int, [vp, sz, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]),
     "mvldm_nchw_to_nhwc": (C.c_int, [vp, vp] + [C.c_int] * 6 + [f32, f32, vp, vp]),
     "mvldm_ray_channels": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "mvldm_ray_encode": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp] + [C.c_int] * 4 + [vp]),

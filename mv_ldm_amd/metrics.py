@@ -4,19 +4,22 @@
 The reference pulls every image to the host and runs skimage one image at a time; here both scores of a whole batch come from
 one launch of `csrc/metrics.hip` (`ops.image_metrics`).  LPIPS (`compute_lpips`, :43-54) runs on the device too -- its VGG-16 trunk
 through the implicit GEMM, the distance in `csrc/lpips.hip` (`mv_ldm_amd.lpips.LPIPS`) -- with the weight files the user brings: none
-ships with the package and none is fetched.  DISTS / FID need other networks and are not provided.
+ships with the package and none is fetched.  DISTS (`compute_dists`, :27-40) runs the same trunk with L2 pooling and per-channel
+statistics (`csrc/dists.hip`, `mv_ldm_amd.dists.DISTS`), again with the user's files.  FID needs another network and is not provided.
 
     python -m mv_ldm_amd.metrics --pred DIR --gt DIR [--json OUT] [--lpips VGG.pth [--lpips-lin LIN.pth]]
+                                 [--dists VGG_OR_FULL.pth [--dists-weights WEIGHTS.pt]]
 
 pairs `DIR/<scene>/color/<index>.png` of the two trees by scene and frame index and prints per-scene and overall means.
 `--lpips`: a full `lpips.LPIPS(net="vgg").state_dict()`, or torchvision's VGG-16 with the package's `vgg.pth` as `--lpips-lin`.
+`--dists`: a full `DISTS_pytorch.DISTS().state_dict()`, or torchvision's VGG-16 with the package's `weights.pt` as `--dists-weights`.
 """
 from __future__ import annotations
 
 import argparse
 import json
 from pathlib import Path
-from typing import Dict, List, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
@@ -69,6 +72,31 @@ def load_lpips(weights, lin=None, device="cuda", dtype: torch.dtype = torch.floa
     return LPIPS(net="vgg", weights=weights, lin=lin, dtype=dtype).to(device)
 
 
+def compute_dists(ground_truth: torch.Tensor, predicted: torch.Tensor, model) -> torch.Tensor:
+    """src/evaluation/metrics.py:27-40: `model.forward(ground_truth, predicted)` with `model` an `mv_ldm_amd.dists.DISTS` on the
+    inputs' device; `[batch, 3, h, w]` -> `[batch]`, or `[b, v, 3, h, w]` -> `[b, v]`, fp32"""
+    if ground_truth.shape != predicted.shape:
+        raise ValueError(f"ground truth {tuple(ground_truth.shape)} against prediction {tuple(predicted.shape)}")
+    if ground_truth.dim() not in (4, 5):
+        raise ValueError(f"expected [batch, c, h, w] or [b, v, c, h, w], got {tuple(ground_truth.shape)}")
+    if not (ground_truth.is_contiguous() and predicted.is_contiguous()):
+        raise ValueError("compute_dists: inputs must be contiguous (call .contiguous() first)")
+    lead = ground_truth.shape[:-3]
+    flat = lambda t: t.reshape(-1, *t.shape[-3:])
+    return model(flat(ground_truth), flat(predicted)).reshape(lead)
+
+
+def load_dists(weights, alpha_beta=None, device="cuda", dtype: torch.dtype = torch.float32):
+    """the `--dists VGG_OR_FULL.pth [--dists-weights WEIGHTS.pt]` of the command lines: a `DISTS` with the user's weights on `device`"""
+    from .dists import DISTS
+    return DISTS(weights=weights, alpha_beta=alpha_beta, dtype=dtype).to(device)
+
+
+def metric_names(lpips=None, dists=None) -> Tuple[str, ...]:
+    """the columns of a per-frame row scored with these networks: psnr, ssim, then lpips, then dists"""
+    return ("psnr", "ssim") + (() if lpips is None else ("lpips",)) + (() if dists is None else ("dists",))
+
+
 # ---- PNG trees ---------------------------------------------------------------------------------------------------
 def scan_tree(root) -> Dict[str, Dict[int, Path]]:
     """{scene: {frame index: path}} of `root/<scene>/color/<index>.png`; the index is the file stem as an integer (`000012.png`
@@ -102,20 +130,25 @@ def pair_trees(pred: Dict[str, Dict[int, object]], gt: Dict[str, Dict[int, objec
     return pairs, missing
 
 
-def summarize(per_frame: Dict[str, Dict[int, List[float]]]) -> dict:
+def summarize(per_frame: Dict[str, Dict[int, List[float]]], names: Optional[Sequence[str]] = None) -> dict:
     """{scene: {index: [psnr, ssim]}} -> the report: per-scene means, the overall mean over all frames.  Rows scored with an LPIPS
-    network are [psnr, ssim, lpips]: the report then carries "lpips" next to "psnr" and "ssim"."""
+    network are [psnr, ssim, lpips]: the report then carries "lpips" next to "psnr" and "ssim".  `names`: the rows' columns, said
+    outright (a run with a DISTS network passes them); without it they are inferred from the row length as above."""
     mean = lambda v: sum(v) / len(v) if v else float("nan")
     every = [v for f in per_frame.values() for v in f.values()]
-    names = ("psnr", "ssim", "lpips") if every and all(len(v) == 3 for v in every) else ("psnr", "ssim")
+    if names is None:
+        names = ("psnr", "ssim", "lpips") if every and all(len(v) == 3 for v in every) else ("psnr", "ssim")
+    elif any(len(v) != len(names) for v in every):
+        raise ValueError(f"summarize: rows of other lengths than the {len(names)} columns {list(names)}")
     means = lambda rows: {k: mean([v[j] for v in rows]) for j, k in enumerate(names)}
     scenes = {s: {**means(list(f.values())), "frames": len(f), "per_frame": f} for s, f in per_frame.items()}
     return {"scenes": scenes, "overall": {**means(every), "frames": len(every)}}
 
 
-def score_trees(pred_dir, gt_dir, device="cuda", batch: int = 64, lpips=None) -> dict:
+def score_trees(pred_dir, gt_dir, device="cuda", batch: int = 64, lpips=None, dists=None) -> dict:
     """`metric_computer.test_step` over two PNG trees: every paired frame scored on the device, `batch` frames per launch.
-    `lpips`: an `LPIPS` network on `device`; the per-frame rows then grow from [psnr, ssim] to [psnr, ssim, lpips]"""
+    `lpips`: an `LPIPS` network on `device`; the per-frame rows then grow from [psnr, ssim] to [psnr, ssim, lpips].  `dists`: a `DISTS`
+    network on `device` appends a dists column after that, and the report names its columns under "columns"."""
     from .image_io import load_image
     pairs, missing = pair_trees(scan_tree(pred_dir), scan_tree(gt_dir))
     per_frame: Dict[str, Dict[int, List[float]]] = {}
@@ -126,30 +159,40 @@ def score_trees(pred_dir, gt_dir, device="cuda", batch: int = 64, lpips=None) ->
             p = torch.stack([load_image(a) for _, a, _ in chunk]).to(device)
             g = torch.stack([load_image(b) for _, _, b in chunk]).to(device)
             psnr, ssim = image_metrics(g, p)
-            rows = [psnr.tolist(), ssim.tolist()] + ([] if lpips is None else [compute_lpips(g, p, lpips).tolist()])
+            rows = [psnr.tolist(), ssim.tolist()] + ([] if lpips is None else [compute_lpips(g, p, lpips).tolist()]) \
+                + ([] if dists is None else [compute_dists(g, p, dists).tolist()])
             for (i, _, _), *row in zip(chunk, *rows):
                 per_frame[scene][i] = row
-    rep = summarize(per_frame)
+    if dists is None:
+        rep = summarize(per_frame)
+    else:
+        rep = summarize(per_frame, names=metric_names(lpips, dists))
+        rep["columns"] = list(metric_names(lpips, dists))
     rep["missing"] = [list(m) for m in missing]
     return rep
 
 
 def main(argv=None):
-    ap = argparse.ArgumentParser(description="PSNR / SSIM (/ LPIPS) of DIR/<scene>/color/<index>.png against a ground-truth tree of the same layout")
+    ap = argparse.ArgumentParser(description="PSNR / SSIM (/ LPIPS / DISTS) of DIR/<scene>/color/<index>.png against a ground-truth tree of the same layout")
     ap.add_argument("--pred", required=True)
     ap.add_argument("--gt", required=True)
     ap.add_argument("--json", default=None, help="write the full report (per frame) here")
     ap.add_argument("--lpips", default=None, help="LPIPS(net='vgg') weights: the package's full state dict, or torchvision's VGG-16 (then --lpips-lin too); adds lpips")
     ap.add_argument("--lpips-lin", default=None, help="the lpips package's vgg.pth (lin layers), with a torchvision VGG-16 as --lpips")
+    ap.add_argument("--dists", default=None, help="DISTS weights: the package's full state dict, or torchvision's VGG-16 (then --dists-weights too); adds dists")
+    ap.add_argument("--dists-weights", default=None, help="the DISTS_pytorch package's weights.pt (alpha, beta), with a torchvision VGG-16 as --dists")
     args = ap.parse_args(argv)
     if args.lpips_lin and not args.lpips:
         ap.error("--lpips-lin goes with --lpips")
+    if args.dists_weights and not args.dists:
+        ap.error("--dists-weights goes with --dists")
     if not torch.cuda.is_available():
         raise SystemExit("metrics needs a GPU (the HIP path has no CPU fallback)")
-    rep = score_trees(args.pred, args.gt, lpips=load_lpips(args.lpips, args.lpips_lin) if args.lpips else None)
+    rep = score_trees(args.pred, args.gt, lpips=load_lpips(args.lpips, args.lpips_lin) if args.lpips else None,
+                      dists=load_dists(args.dists, args.dists_weights) if args.dists else None)
     for kind, scene, index, side in rep["missing"]:
         print(f"skipped {kind} {scene}" + ("" if index is None else f"/{index}") + f": missing in --{side}")
-    extra = lambda r: f" lpips {r['lpips']:.6f}" if "lpips" in r else ""
+    extra = lambda r: (f" lpips {r['lpips']:.6f}" if "lpips" in r else "") + (f" dists {r['dists']:.6f}" if "dists" in r else "")
     for s, r in rep["scenes"].items():
         print(f"{s}: psnr {r['psnr']:.4f} ssim {r['ssim']:.6f}{extra(r)} ({r['frames']} frames)")
     o = rep["overall"]

@@ -753,3 +753,72 @@ def lpips_fold(ws: torch.Tensor, n_img: int, h: int, w: int, out: torch.Tensor) 
     assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() == n_img
     L.check(L.load().mvldm_lpips_fold(ws.data_ptr(), ws.numel() * ws.element_size(), n_img, h, w, out.data_ptr(), stream()))
     return out
+
+
+# ------------------------------------------------------------------------------------------ DISTS glue (csrc/dists.hip)
+DISTS_CHANNELS = (3, 64, 128, 256, 512, 512)   # the six taps of DISTS: the raw image, relu1_2, 2_2, 3_3, 4_3, 5_3 (1475 channels)
+DISTS_SUMS = 5                                 # sum a, sum b, sum a^2, sum b^2, sum a b
+
+
+def dists_workspace_bytes(n_img: int, h: int, w: int) -> int:
+    """bytes of fp64 partials `dists_stats` x 6 + `dists_fold` need for `n_img` pairs of h x w images; 0 for a refused shape"""
+    return int(L.load().mvldm_dists_workspace_bytes(n_img, h, w))
+
+
+def dists_stat_slots(h: int, w: int, c: int) -> int:
+    """partials (workgroups) per pair of one tap over an h x w map of c channels; 0 for a refused map"""
+    return int(L.load().mvldm_dists_stat_slots(h, w, c))
+
+
+def dists_layout(h: int, w: int):
+    """([(h_k, w_k, c_k, offset_k)] of the six taps, doubles per pair): the workspace layout `dists_fold` reads"""
+    taps, off, hk, wk = [], 0, h, w
+    for k, c in enumerate(DISTS_CHANNELS):
+        if k >= 2:
+            hk, wk = (hk + 1) // 2, (wk + 1) // 2
+        taps.append((hk, wk, c, off))
+        off += dists_stat_slots(hk, wk, c) * DISTS_SUMS * c
+    return taps, off
+
+
+def dists_prep(in0: torch.Tensor, in1: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
+    """two fp32 NCHW `[n, 3, h, w]` in [0, 1] -> NHWC `[2n, h, w, c_pad]` in `dtype` (rows [0, n): in0), (x - mean) / std"""
+    n, _, h, w = in0.shape
+    dst = torch.empty(2 * n, h, w, epc(dtype), dtype=dtype, device=in0.device)
+    L.check(L.load().mvldm_dists_prep(in0.data_ptr(), in1.data_ptr(), dst.data_ptr(), n, h, w, dst.shape[-1], dt(dtype), stream()))
+    return dst
+
+
+def dists_stats(feat: torch.Tensor, ws: torch.Tensor, offset: int, stride: int, feat_b: Optional[torch.Tensor] = None) -> None:
+    """feat: the pre-activation NHWC `[2n, h, w, c]` output of a stage's last conv -- or, with `feat_b`, the two raw fp32 NCHW
+    `[n, 3, h, w]` inputs (tap 0).  Writes the five fp64 sums per (pair, workgroup, channel) to doubles [offset, offset +
+    dists_stat_slots * 5 * c) of each pair's `stride` doubles in `ws` (uint8)"""
+    assert feat.is_cuda and feat.is_contiguous() and feat.dim() == 4
+    if feat_b is None:
+        assert feat.shape[0] % 2 == 0
+        n2, h, w, c = feat.shape
+        n = n2 // 2
+    else:
+        assert feat_b.is_contiguous() and feat_b.shape == feat.shape and feat.dtype == feat_b.dtype == torch.float32
+        n, c, h, w = feat.shape
+    L.check(L.load().mvldm_dists_stats(feat.data_ptr(), ptr(feat_b), n, h, w, c, dt(feat), ws.data_ptr(), ws.numel() * ws.element_size(),
+                                       offset, stride, stream()))
+
+
+def dists_l2pool(feat: torch.Tensor) -> torch.Tensor:
+    """the pre-activation NHWC `[2n, h, w, c]` -> `[2n, ceil(h / 2), ceil(w / 2), c]`: sqrt(3x3 Hann-weighted mean of relu(feat)^2 + 1e-12), stride 2"""
+    assert feat.is_cuda and feat.is_contiguous() and feat.dim() == 4 and feat.shape[0] % 2 == 0
+    n2, h, w, c = feat.shape
+    out = torch.empty(n2, (h + 1) // 2, (w + 1) // 2, c, dtype=feat.dtype, device=feat.device)
+    L.check(L.load().mvldm_dists_l2pool(feat.data_ptr(), out.data_ptr(), n2 // 2, h, w, c, dt(feat), stream()))
+    return out
+
+
+def dists_fold(ws: torch.Tensor, n_img: int, h: int, w: int, alpha: torch.Tensor, beta: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """out fp32 `[n_img]` = the DISTS score of each pair from the partials in `ws`; alpha, beta: fp32, 1475 elements each, in tap order"""
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() == n_img
+    for t in (alpha, beta):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == sum(DISTS_CHANNELS)
+    L.check(L.load().mvldm_dists_fold(ws.data_ptr(), ws.numel() * ws.element_size(), n_img, h, w, alpha.data_ptr(), beta.data_ptr(),
+                                      out.data_ptr(), stream()))
+    return out

@@ -1796,14 +1796,15 @@ class MVLDMTrainer:
 
     # ---- validation: sample held-out scenes with the current weights and score them ------------------------------------
     def validation_step(self, batch, num_inference_steps: Optional[int] = None, x_T=None, encode_noise=None, *, second: Optional[int] = None,
-                        roundtrip_noise=None, use_ema: bool = False, sampler_cfg=None, lpips=None) -> dict:
+                        roundtrip_noise=None, use_ema: bool = False, sampler_cfg=None, lpips=None, dists=None) -> dict:
         """`DiffusionWrapper.validation_step` (diffusion_wrapper.py:492-544) without the logger: keep ONE context view
         (`sample_indices(batch, 1, random=True)`, :505-506; the others join the targets), convert to poses relative to it (:509-511),
         sample the targets with the weights of the last optimizer step (:513-514) and VAE-round-trip the target images (:519-520).
         Returns {"sampled", "targets", "targets_roundtrip" [b, v_t, 3, H, W], "context" [b, 1, 3, H, W], "psnr" / "ssim" [b, v_t] of the
         sampled views against the raw targets, "psnr_roundtrip" / "ssim_roundtrip" against the round trip (the ceiling the VAE
         allows), "batch": the sliced batch `sample()` saw}; all on the device, scored by `metrics.image_metrics`.  `lpips`: an
-        `mv_ldm_amd.lpips.LPIPS` on the trainer's device adds "lpips" and "lpips_roundtrip" [b, v_t] (`metrics.compute_lpips`).
+        `mv_ldm_amd.lpips.LPIPS` on the trainer's device adds "lpips" and "lpips_roundtrip" [b, v_t] (`metrics.compute_lpips`); `dists`: an
+        `mv_ldm_amd.dists.DISTS` there adds "dists" and "dists_roundtrip" [b, v_t] (`metrics.compute_dists`).
 
         `x_T` / `encode_noise`: the explicit noise of `MVLDMPipeline.sample`; `second`: which context view is kept (the torch.randint
         of `sample_indices`); `roundtrip_noise`: the posterior draw of the target round trip.  What is not given is drawn inside a
@@ -1816,7 +1817,7 @@ class MVLDMTrainer:
         every VAE call waits for a window being encoded ahead on the side stream.  The training plans, a prefetched window, the
         gradient and moment buffers, the scheduler's timestep grid and the compute dtype are as they were on return.  Only at an optimizer-step boundary (RuntimeError inside an accumulation window).
         Under a multi-rank trainer this is a COLLECTIVE (it enters `sync_masters()`): every rank calls it, with its own scenes."""
-        from .metrics import compute_lpips, image_metrics
+        from .metrics import compute_dists, compute_lpips, image_metrics
         from .pipeline import MVLDMPipeline, SamplerCfg, absolute_to_relative_camera
         from .runtime import compute_dtype
         if use_ema:
@@ -1862,6 +1863,8 @@ class MVLDMTrainer:
                 psnr, ssim = image_metrics(targets, sampled)
                 psnr_rt, ssim_rt = image_metrics(roundtrip, sampled)
                 extra = {} if lpips is None else {"lpips": compute_lpips(targets, sampled, lpips), "lpips_roundtrip": compute_lpips(roundtrip, sampled, lpips)}
+                if dists is not None:
+                    extra.update({"dists": compute_dists(targets, sampled, dists), "dists_roundtrip": compute_dists(roundtrip, sampled, dists)})
             finally:
                 for k in ("num_inference_steps", "timesteps", "_dev"):
                     sch.__dict__.pop(k, None)
