@@ -33,7 +33,9 @@ extern "C" {
  *    + mvldm_lpips_prep / _relu / _tap / _fold, mvldm_lpips_workspace_bytes, mvldm_lpips_tap_slots (LPIPS around the implicit GEMM): new
  *    symbols only, no struct, enum or op kind changes, so the number stays 7.
  *    + mvldm_dists_prep / _stats / _l2pool / _fold, mvldm_dists_workspace_bytes, mvldm_dists_stat_slots (DISTS around the implicit GEMM):
- *    new symbols only again, the number stays 7. */
+ *    new symbols only again, the number stays 7.
+ *    + mvldm_fid_prep / _pool / _accumulate / _compute, mvldm_fid_workspace_bytes, mvldm_fid_pool_slots (FID, feature = 64, around the
+ *    implicit GEMM): new symbols only, the number stays 7. */
 #define MVLDM_ABI_VERSION 7
 
 typedef void* mvldm_stream_t; /* hipStream_t */
@@ -555,6 +557,53 @@ int mvldm_dists_stats(const void* feat, const void* feat_b, int n_img, int h, in
 int mvldm_dists_l2pool(const void* feat, void* out, int n_img, int h, int w, int c, int dtype, mvldm_stream_t stream);
 int mvldm_dists_fold(const double* workspace, size_t workspace_bytes, int n_img, int h, int w, const float* alpha, const float* beta,
                      float* out, mvldm_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * FID (feature = 64): the glue between the three 3x3 convolutions of the Inception-v3 stem (mvldm_igemm_fwd, BatchNorm folded into
+ * weight and bias; the ReLU after the first two is mvldm_lpips_relu) and the Frechet distance of two sets of 64 features.
+ *   replaces  torchmetrics' FrechetInceptionDistance(feature=64, normalize=True) as src/evaluation/metric_computer.py:22,65-68 uses it:
+ *             update(imgs, real) -- (imgs * 255).byte(), torch-fidelity's TensorFlow-1 bilinear resize to 299 x 299, (x - 128) / 128,
+ *             Conv2d_1a_3x3 / 2a / 2b with BatchNorm(eps 1e-3) and ReLU, MaxPool(3, 2), the mean over the map, .double(), sum f and
+ *             sum f^T f per side -- and compute(): mu = sum / n, Sigma = (sum f^T f - n mu^T mu) / (n - 1),
+ *             fid = |mu1 - mu2|^2 + tr Sigma1 + tr Sigma2 - 2 sum_i Re sqrt(eig_i(Sigma1 Sigma2)).
+ * All four run eagerly on `stream`, never synchronise or allocate, use no atomics (the same bits on every run) and refuse on the host
+ * before any launch:
+ *   mvldm_fid_prep        src: NCHW [n_img][3][h][w], fp32 in [0, 1] (src_u8 = 0: quantised as trunc(min(max(x * 255, 0), 255)), the
+ *                         product in fp32 -- the package's .byte() wraps outside [0, 1], this clamps) or uint8 (src_u8 = 1) -> dst NHWC
+ *                         [n_img][oh][ow][c_pad] in `dtype`, c_pad = 4 (f32) / 8 (16 bit), the pad channels zero.  Output (oy, ox) reads
+ *                         the source at y = float(oy) * (float(h) / float(oh)) (fp32, no half-pixel centres), y0 = trunc(y),
+ *                         y1 = min(y0 + 1, h - 1), dy = y - y0, likewise x; v0 = a00 + (a01 - a00) dx, v1 = a10 + (a11 - a10) dx,
+ *                         v = v0 + (v1 - v0) dy, all fp32, not contracted; stores (v - 128) / 128.  Refused: an edge below 1, a c_pad
+ *                         the implicit GEMM would refuse, a null or unaligned pointer.
+ *   mvldm_fid_pool        feat: the PRE-activation NHWC [n_img][h][w][c], c a multiple of 64 up to 512.  ReLU, max-pool 3x3 / stride 2 /
+ *                         no padding / floor (oh = (h - 3) / 2 + 1), and the sum of the pooled map per channel, fp64 from the first
+ *                         add; the pooled map is never written.  Workgroup k (k < mvldm_fid_pool_slots(h, w, c): a band of
+ *                         ceil(512 / ow) output rows) writes its partial of channel ch to workspace[(i * slots + k) * c + ch].
+ *                         Refused: h or w < 3, another c, a workspace below n_img * slots * c * 8 bytes, a null or unaligned pointer.
+ *   mvldm_fid_accumulate  workspace: the partials above, followed by room for n_img * c doubles (mvldm_fid_workspace_bytes covers both).
+ *                         f[i][ch] = (the partials of image i in band order) / (oh * ow), written behind the partials and, if
+ *                         `features` is not null, to features[n_img][c]; then state[0] += n_img, state[1 + a] += sum_i f[i][a],
+ *                         state[1 + c + a c + b] += sum_i f[i][a] f[i][b], each sum over the images in order and added to the state
+ *                         once.  `state`: 1 + c + c c doubles on the device, zero before the first call; null: the features only.
+ *   mvldm_fid_compute     c must be 64.  One workgroup; mu, Sigma and everything after in fp64, the matrices in LDS.  Sigma1 = V D V^T by
+ *                         cyclic Jacobi (round-robin ordering: 32 disjoint rotations a round, 63 rounds a sweep; converged when
+ *                         off(A) <= 1e-22 |A|_F, at most 30 sweeps), then the eigenvalues lambda of D^1/2 V^T Sigma2 V D^1/2 (the spectrum of
+ *                         Sigma1^1/2 Sigma2 Sigma1^1/2, real and symmetric) the same way; score (fp32) = |mu1 - mu2|^2 + (tr Sigma1 +
+ *                         tr Sigma2) - 2 sum_i sqrt(max(lambda_i, 0)).  info (8 doubles): sweeps and final off(A) / |A|_F of the first
+ *                         solve, of the second, the number of solves that stopped at the sweep cap, the score in fp64, sum sqrt, and
+ *                         the other three terms.  A solve that stops at the cap, or a state of fewer than 2 samples, stores NaN as
+ *                         the score.  Identical states score about -1e-8 times the scale, not 0.
+ * mvldm_fid_workspace_bytes and mvldm_fid_pool_slots are 0 for a refused shape.
+ * Parity with torchmetrics / torch-fidelity and their published weights is unpinned: the arithmetic above is a restatement. */
+size_t mvldm_fid_workspace_bytes(int n_img, int h, int w, int c);
+int mvldm_fid_pool_slots(int h, int w, int c);
+int mvldm_fid_prep(const void* src, int src_u8, void* dst, int n_img, int h, int w, int oh, int ow, int c_pad, int dtype,
+                   mvldm_stream_t stream);
+int mvldm_fid_pool(const void* feat, int n_img, int h, int w, int c, int dtype, double* workspace, size_t workspace_bytes,
+                   mvldm_stream_t stream);
+int mvldm_fid_accumulate(double* workspace, size_t workspace_bytes, int n_img, int h, int w, int c, double* features, double* state,
+                         mvldm_stream_t stream);
+int mvldm_fid_compute(const double* state1, const double* state2, int c, float* score, double* info, mvldm_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Plans: a whole forward (UNet walk, VAE decoder, DDIM step) as a flat list of the ops above with

@@ -239,6 +239,12 @@ SIGNATURES = {
     "mvldm_dists_stats": (C.c_int, [vp, vp] + [C.c_int] * 5 + [vp, sz, C.c_int, C.c_int, vp]),
     "mvldm_dists_l2pool": (C.c_int, [vp, vp] + [C.c_int] * 5 + [vp]),
     "mvldm_dists_fold": (C.c_int, [vp, sz, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]),
+    "mvldm_fid_workspace_bytes": (sz, [C.c_int] * 4),
+    "mvldm_fid_pool_slots": (C.c_int, [C.c_int] * 3),
+    "mvldm_fid_prep": (C.c_int, [vp, C.c_int, vp] + [C.c_int] * 7 + [vp]),
+    "mvldm_fid_pool": (C.c_int, [vp] + [C.c_int] * 5 + [vp, sz, vp]),
+    "mvldm_fid_accumulate": (C.c_int, [vp, sz] + [C.c_int] * 4 + [vp, vp, vp]),
+    "mvldm_fid_compute": (C.c_int, [vp, vp, C.c_int, vp, vp, vp]),
     "mvldm_nchw_to_nhwc": (C.c_int, [vp, vp] + [C.c_int] * 6 + [f32, f32, vp, vp]),
     "mvldm_ray_channels": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "mvldm_ray_encode": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp] + [C.c_int] * 4 + [vp]),

@@ -5,14 +5,17 @@ The reference pulls every image to the host and runs skimage one image at a time
 one launch of `csrc/metrics.hip` (`ops.image_metrics`).  LPIPS (`compute_lpips`, :43-54) runs on the device too -- its VGG-16 trunk
 through the implicit GEMM, the distance in `csrc/lpips.hip` (`mv_ldm_amd.lpips.LPIPS`) -- with the weight files the user brings: none
 ships with the package and none is fetched.  DISTS (`compute_dists`, :27-40) runs the same trunk with L2 pooling and per-channel
-statistics (`csrc/dists.hip`, `mv_ldm_amd.dists.DISTS`), again with the user's files.  FID needs another network and is not provided.
+statistics (`csrc/dists.hip`, `mv_ldm_amd.dists.DISTS`), again with the user's files.  FID (`metric_computer.py:22,65-68`:
+`FrechetInceptionDistance(feature=64, normalize=True)`, one value per scene) runs the three convolutions of the Inception-v3 stem through
+the same kernels and the Frechet distance in `csrc/fid.hip` (`mv_ldm_amd.fid.FrechetInceptionDistance`), with the user's Inception file.
 
     python -m mv_ldm_amd.metrics --pred DIR --gt DIR [--json OUT] [--lpips VGG.pth [--lpips-lin LIN.pth]]
-                                 [--dists VGG_OR_FULL.pth [--dists-weights WEIGHTS.pt]]
+                                 [--dists VGG_OR_FULL.pth [--dists-weights WEIGHTS.pt]] [--fid INCEPTION.pth]
 
 pairs `DIR/<scene>/color/<index>.png` of the two trees by scene and frame index and prints per-scene and overall means.
 `--lpips`: a full `lpips.LPIPS(net="vgg").state_dict()`, or torchvision's VGG-16 with the package's `vgg.pth` as `--lpips-lin`.
 `--dists`: a full `DISTS_pytorch.DISTS().state_dict()`, or torchvision's VGG-16 with the package's `weights.pt` as `--dists-weights`.
+`--fid`: torch-fidelity's `pt_inception` state dict, or a torchmetrics FID state dict; adds one `fid` per scene (scenes of 2 frames or more).
 """
 from __future__ import annotations
 
@@ -92,6 +95,37 @@ def load_dists(weights, alpha_beta=None, device="cuda", dtype: torch.dtype = tor
     return DISTS(weights=weights, alpha_beta=alpha_beta, dtype=dtype).to(device)
 
 
+def compute_fid(ground_truth: torch.Tensor, predicted: torch.Tensor, model) -> torch.Tensor:
+    """src/evaluation/metric_computer.py:65-68: `update(ground_truth, real=True)`, `update(predicted, real=False)`, `compute()`,
+    `reset()` with `model` an `mv_ldm_amd.fid.FrechetInceptionDistance` on the inputs' device: one score per SET of views.
+    `[v, 3, h, w]` -> 0-d, `[b, v, 3, h, w]` -> `[b]`, fp32.  Whatever the model had accumulated before is dropped."""
+    if ground_truth.shape != predicted.shape:
+        raise ValueError(f"ground truth {tuple(ground_truth.shape)} against prediction {tuple(predicted.shape)}")
+    if ground_truth.dim() not in (4, 5):
+        raise ValueError(f"expected [v, c, h, w] or [b, v, c, h, w], got {tuple(ground_truth.shape)}")
+    if not (ground_truth.is_contiguous() and predicted.is_contiguous()):
+        raise ValueError("compute_fid: inputs must be contiguous (call .contiguous() first)")
+
+    def one(g, p):
+        model.reset()
+        model.update(g, real=True)
+        model.update(p, real=False)
+        value = model.compute()
+        model.reset()
+        return value
+
+    if ground_truth.dim() == 4:
+        return one(ground_truth, predicted)
+    return torch.stack([one(ground_truth[i], predicted[i]) for i in range(ground_truth.shape[0])]) if ground_truth.shape[0] \
+        else torch.empty(0, dtype=torch.float32, device=ground_truth.device)
+
+
+def load_fid(weights, device="cuda", dtype: torch.dtype = torch.float32):
+    """the `--fid INCEPTION.pth` of the command lines: a `FrechetInceptionDistance(feature=64, normalize=True)` with the user's weights on `device`"""
+    from .fid import FrechetInceptionDistance
+    return FrechetInceptionDistance(feature=64, normalize=True, weights=weights, dtype=dtype).to(device)
+
+
 def metric_names(lpips=None, dists=None) -> Tuple[str, ...]:
     """the columns of a per-frame row scored with these networks: psnr, ssim, then lpips, then dists"""
     return ("psnr", "ssim") + (() if lpips is None else ("lpips",)) + (() if dists is None else ("dists",))
@@ -145,15 +179,21 @@ def summarize(per_frame: Dict[str, Dict[int, List[float]]], names: Optional[Sequ
     return {"scenes": scenes, "overall": {**means(every), "frames": len(every)}}
 
 
-def score_trees(pred_dir, gt_dir, device="cuda", batch: int = 64, lpips=None, dists=None) -> dict:
+def score_trees(pred_dir, gt_dir, device="cuda", batch: int = 64, lpips=None, dists=None, fid=None) -> dict:
     """`metric_computer.test_step` over two PNG trees: every paired frame scored on the device, `batch` frames per launch.
     `lpips`: an `LPIPS` network on `device`; the per-frame rows then grow from [psnr, ssim] to [psnr, ssim, lpips].  `dists`: a `DISTS`
-    network on `device` appends a dists column after that, and the report names its columns under "columns"."""
+    network on `device` appends a dists column after that, and the report names its columns under "columns".  `fid`: a
+    `FrechetInceptionDistance` on `device`; FID is one value per scene, so the per-frame rows do not change: every scene entry gains
+    "fid" (None for a scene of fewer than 2 paired frames) and "overall" the mean over the scored scenes, as the reference's running
+    table averages its per-scene values."""
     from .image_io import load_image
     pairs, missing = pair_trees(scan_tree(pred_dir), scan_tree(gt_dir))
     per_frame: Dict[str, Dict[int, List[float]]] = {}
+    scene_fid: Dict[str, Optional[torch.Tensor]] = {}
     for scene, items in pairs.items():
         per_frame[scene] = {}
+        if fid is not None:
+            fid.reset()
         for i0 in range(0, len(items), batch):
             chunk = items[i0:i0 + batch]
             p = torch.stack([load_image(a) for _, a, _ in chunk]).to(device)
@@ -163,17 +203,28 @@ def score_trees(pred_dir, gt_dir, device="cuda", batch: int = 64, lpips=None, di
                 + ([] if dists is None else [compute_dists(g, p, dists).tolist()])
             for (i, _, _), *row in zip(chunk, *rows):
                 per_frame[scene][i] = row
+            if fid is not None and len(items) >= 2:
+                fid.update(g, real=True)
+                fid.update(p, real=False)
+        if fid is not None:
+            scene_fid[scene] = fid.compute() if len(items) >= 2 else None
+            fid.reset()
     if dists is None:
         rep = summarize(per_frame)
     else:
         rep = summarize(per_frame, names=metric_names(lpips, dists))
         rep["columns"] = list(metric_names(lpips, dists))
+    if fid is not None:
+        for scene, value in scene_fid.items():
+            rep["scenes"][scene]["fid"] = None if value is None else float(value)
+        scored = [v["fid"] for v in rep["scenes"].values() if v["fid"] is not None]
+        rep["overall"]["fid"] = sum(scored) / len(scored) if scored else None
     rep["missing"] = [list(m) for m in missing]
     return rep
 
 
 def main(argv=None):
-    ap = argparse.ArgumentParser(description="PSNR / SSIM (/ LPIPS / DISTS) of DIR/<scene>/color/<index>.png against a ground-truth tree of the same layout")
+    ap = argparse.ArgumentParser(description="PSNR / SSIM (/ LPIPS / DISTS / FID) of DIR/<scene>/color/<index>.png against a ground-truth tree of the same layout")
     ap.add_argument("--pred", required=True)
     ap.add_argument("--gt", required=True)
     ap.add_argument("--json", default=None, help="write the full report (per frame) here")
@@ -181,6 +232,8 @@ def main(argv=None):
     ap.add_argument("--lpips-lin", default=None, help="the lpips package's vgg.pth (lin layers), with a torchvision VGG-16 as --lpips")
     ap.add_argument("--dists", default=None, help="DISTS weights: the package's full state dict, or torchvision's VGG-16 (then --dists-weights too); adds dists")
     ap.add_argument("--dists-weights", default=None, help="the DISTS_pytorch package's weights.pt (alpha, beta), with a torchvision VGG-16 as --dists")
+    ap.add_argument("--fid", default=None, help="Inception-v3 weights (torch-fidelity's pt_inception state dict or a torchmetrics FID state dict); "
+                                                "adds fid (feature=64), one value per scene")
     args = ap.parse_args(argv)
     if args.lpips_lin and not args.lpips:
         ap.error("--lpips-lin goes with --lpips")
@@ -189,10 +242,11 @@ def main(argv=None):
     if not torch.cuda.is_available():
         raise SystemExit("metrics needs a GPU (the HIP path has no CPU fallback)")
     rep = score_trees(args.pred, args.gt, lpips=load_lpips(args.lpips, args.lpips_lin) if args.lpips else None,
-                      dists=load_dists(args.dists, args.dists_weights) if args.dists else None)
+                      dists=load_dists(args.dists, args.dists_weights) if args.dists else None, fid=load_fid(args.fid) if args.fid else None)
     for kind, scene, index, side in rep["missing"]:
         print(f"skipped {kind} {scene}" + ("" if index is None else f"/{index}") + f": missing in --{side}")
-    extra = lambda r: (f" lpips {r['lpips']:.6f}" if "lpips" in r else "") + (f" dists {r['dists']:.6f}" if "dists" in r else "")
+    extra = lambda r: (f" lpips {r['lpips']:.6f}" if "lpips" in r else "") + (f" dists {r['dists']:.6f}" if "dists" in r else "") \
+        + ("" if "fid" not in r else " fid -" if r["fid"] is None else f" fid {r['fid']:.6f}")
     for s, r in rep["scenes"].items():
         print(f"{s}: psnr {r['psnr']:.4f} ssim {r['ssim']:.6f}{extra(r)} ({r['frames']} frames)")
     o = rep["overall"]

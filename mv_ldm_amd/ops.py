@@ -822,3 +822,60 @@ def dists_fold(ws: torch.Tensor, n_img: int, h: int, w: int, alpha: torch.Tensor
     L.check(L.load().mvldm_dists_fold(ws.data_ptr(), ws.numel() * ws.element_size(), n_img, h, w, alpha.data_ptr(), beta.data_ptr(),
                                       out.data_ptr(), stream()))
     return out
+
+
+# ------------------------------------------------------------------------------------------ FID glue (csrc/fid.hip)
+FID_FEATURES = 64                              # feature=64: Inception-v3 after its first max-pool
+FID_STATE = 1 + FID_FEATURES + FID_FEATURES * FID_FEATURES      # doubles of one side's running state: count, sum f, sum f^T f
+FID_INFO = 8                                   # doubles of `fid_compute`'s record
+
+
+def fid_workspace_bytes(n_img: int, h: int, w: int, c: int = FID_FEATURES) -> int:
+    """bytes of fp64 `fid_pool` + `fid_accumulate` need for `n_img` pre-pool maps of h x w x c: the partials, then the features; 0 for
+    a refused shape"""
+    return int(L.load().mvldm_fid_workspace_bytes(n_img, h, w, c))
+
+
+def fid_pool_slots(h: int, w: int, c: int) -> int:
+    """partials (workgroups) per image of the pool over an h x w map of c channels; 0 for a refused map"""
+    return int(L.load().mvldm_fid_pool_slots(h, w, c))
+
+
+def fid_prep(imgs: torch.Tensor, dtype: torch.dtype, oh: int = 299, ow: int = 299) -> torch.Tensor:
+    """fp32 in [0, 1] or uint8 NCHW `[n, 3, h, w]` -> NHWC `[n, oh, ow, c_pad]` in `dtype`: the package's byte quantisation, the
+    TensorFlow-1 bilinear resize, (x - 128) / 128"""
+    assert imgs.is_cuda and imgs.is_contiguous() and imgs.dim() == 4 and imgs.shape[1] == 3 and imgs.dtype in (torch.float32, torch.uint8)
+    n, _, h, w = imgs.shape
+    dst = torch.empty(n, oh, ow, epc(dtype), dtype=dtype, device=imgs.device)
+    L.check(L.load().mvldm_fid_prep(imgs.data_ptr(), int(imgs.dtype == torch.uint8), dst.data_ptr(), n, h, w, oh, ow, dst.shape[-1], dt(dtype), stream()))
+    return dst
+
+
+def fid_pool(feat: torch.Tensor, ws: torch.Tensor) -> None:
+    """feat: the pre-activation NHWC `[n, h, w, c]`.  ReLU, max-pool 3x3 / 2, and the fp64 sum of the pooled map per channel: doubles
+    `[n, fid_pool_slots, c]` at the start of `ws` (uint8)"""
+    assert feat.is_cuda and feat.is_contiguous() and feat.dim() == 4
+    n, h, w, c = feat.shape
+    L.check(L.load().mvldm_fid_pool(feat.data_ptr(), n, h, w, c, dt(feat), ws.data_ptr(), ws.numel() * ws.element_size(), stream()))
+
+
+def fid_accumulate(ws: torch.Tensor, n_img: int, h: int, w: int, c: int, state: Optional[torch.Tensor],
+                   features: Optional[torch.Tensor] = None) -> None:
+    """folds `fid_pool`'s partials in `ws` to the fp64 features `[n_img, c]` (written to `features` if given) and adds them to `state`
+    (fp64, 1 + c + c c: count, sum f, sum f^T f; None: the features only)"""
+    for t, numel in ((state, 1 + c + c * c), (features, n_img * c)):
+        assert t is None or (t.dtype == torch.float64 and t.is_contiguous() and t.numel() == numel)
+    L.check(L.load().mvldm_fid_accumulate(ws.data_ptr(), ws.numel() * ws.element_size(), n_img, h, w, c, ptr(features), ptr(state), stream()))
+
+
+def fid_compute(state1: torch.Tensor, state2: torch.Tensor, out: torch.Tensor, info: torch.Tensor) -> torch.Tensor:
+    """out (fp32, one element) = the Frechet distance of two states of 64 features; info (fp64 `[FID_INFO]`): sweeps and final relative
+    off-diagonal norm of the first solve, of the second, solves that stopped at the sweep cap (then `out` is NaN), the score in fp64,
+    sum sqrt(lambda), |mu1 - mu2|^2 + tr Sigma1 + tr Sigma2"""
+    for t in (state1, state2):
+        assert t.dtype == torch.float64 and t.is_contiguous()
+    c = int(round((-1 + (1 + 4 * (state1.numel() - 1)) ** 0.5) / 2))
+    assert state1.numel() == state2.numel() == 1 + c + c * c
+    assert out.dtype == torch.float32 and out.numel() == 1 and info.dtype == torch.float64 and info.is_contiguous() and info.numel() == FID_INFO
+    L.check(L.load().mvldm_fid_compute(state1.data_ptr(), state2.data_ptr(), c, out.data_ptr(), info.data_ptr(), stream()))
+    return out

@@ -1796,7 +1796,7 @@ class MVLDMTrainer:
 
     # ---- validation: sample held-out scenes with the current weights and score them ------------------------------------
     def validation_step(self, batch, num_inference_steps: Optional[int] = None, x_T=None, encode_noise=None, *, second: Optional[int] = None,
-                        roundtrip_noise=None, use_ema: bool = False, sampler_cfg=None, lpips=None, dists=None) -> dict:
+                        roundtrip_noise=None, use_ema: bool = False, sampler_cfg=None, lpips=None, dists=None, fid=None) -> dict:
         """`DiffusionWrapper.validation_step` (diffusion_wrapper.py:492-544) without the logger: keep ONE context view
         (`sample_indices(batch, 1, random=True)`, :505-506; the others join the targets), convert to poses relative to it (:509-511),
         sample the targets with the weights of the last optimizer step (:513-514) and VAE-round-trip the target images (:519-520).
@@ -1804,7 +1804,8 @@ class MVLDMTrainer:
         sampled views against the raw targets, "psnr_roundtrip" / "ssim_roundtrip" against the round trip (the ceiling the VAE
         allows), "batch": the sliced batch `sample()` saw}; all on the device, scored by `metrics.image_metrics`.  `lpips`: an
         `mv_ldm_amd.lpips.LPIPS` on the trainer's device adds "lpips" and "lpips_roundtrip" [b, v_t] (`metrics.compute_lpips`); `dists`: an
-        `mv_ldm_amd.dists.DISTS` there adds "dists" and "dists_roundtrip" [b, v_t] (`metrics.compute_dists`).
+        `mv_ldm_amd.dists.DISTS` there adds "dists" and "dists_roundtrip" [b, v_t] (`metrics.compute_dists`); `fid`: an
+        `mv_ldm_amd.fid.FrechetInceptionDistance` there adds "fid" and "fid_roundtrip" [b], one value per scene (`metrics.compute_fid`).
 
         `x_T` / `encode_noise`: the explicit noise of `MVLDMPipeline.sample`; `second`: which context view is kept (the torch.randint
         of `sample_indices`); `roundtrip_noise`: the posterior draw of the target round trip.  What is not given is drawn inside a
@@ -1817,7 +1818,7 @@ class MVLDMTrainer:
         every VAE call waits for a window being encoded ahead on the side stream.  The training plans, a prefetched window, the
         gradient and moment buffers, the scheduler's timestep grid and the compute dtype are as they were on return.  Only at an optimizer-step boundary (RuntimeError inside an accumulation window).
         Under a multi-rank trainer this is a COLLECTIVE (it enters `sync_masters()`): every rank calls it, with its own scenes."""
-        from .metrics import compute_dists, compute_lpips, image_metrics
+        from .metrics import compute_dists, compute_fid, compute_lpips, image_metrics
         from .pipeline import MVLDMPipeline, SamplerCfg, absolute_to_relative_camera
         from .runtime import compute_dtype
         if use_ema:
@@ -1865,6 +1866,8 @@ class MVLDMTrainer:
                 extra = {} if lpips is None else {"lpips": compute_lpips(targets, sampled, lpips), "lpips_roundtrip": compute_lpips(roundtrip, sampled, lpips)}
                 if dists is not None:
                     extra.update({"dists": compute_dists(targets, sampled, dists), "dists_roundtrip": compute_dists(roundtrip, sampled, dists)})
+                if fid is not None:
+                    extra.update({"fid": compute_fid(targets, sampled, fid), "fid_roundtrip": compute_fid(roundtrip, sampled, fid)})
             finally:
                 for k in ("num_inference_steps", "timesteps", "_dev"):
                     sch.__dict__.pop(k, None)
