@@ -35,7 +35,10 @@ extern "C" {
  *    + mvldm_dists_prep / _stats / _l2pool / _fold, mvldm_dists_workspace_bytes, mvldm_dists_stat_slots (DISTS around the implicit GEMM):
  *    new symbols only again, the number stays 7.
  *    + mvldm_fid_prep / _pool / _accumulate / _compute, mvldm_fid_workspace_bytes, mvldm_fid_pool_slots (FID, feature = 64, around the
- *    implicit GEMM): new symbols only, the number stays 7. */
+ *    implicit GEMM): new symbols only, the number stays 7.
+ *    + mvldm_inception_prep / _unfold / _maxpool / _avgpool / _concat / _features, mvldm_inception_workspace_bytes, mvldm_frechet_accumulate /
+ *    _compute, mvldm_frechet_workspace_bytes (Clean-FID: the whole Inception-v3 and a Frechet distance up to 2048 features): new symbols
+ *    only, the number stays 7. */
 #define MVLDM_ABI_VERSION 7
 
 typedef void* mvldm_stream_t; /* hipStream_t */
@@ -604,6 +607,69 @@ int mvldm_fid_pool(const void* feat, int n_img, int h, int w, int c, int dtype, 
 int mvldm_fid_accumulate(double* workspace, size_t workspace_bytes, int n_img, int h, int w, int c, double* features, double* state,
                          mvldm_stream_t stream);
 int mvldm_fid_compute(const double* state1, const double* state2, int c, float* score, double* info, mvldm_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Clean-FID: what `cleanfid.fid.compute_fid(dir, "gt_images")` (src/scripts/compute_fid.py:44-47; mode "clean", model inception_v3)
+ * needs around the 94 convolutions of Inception-v3 (mvldm_igemm_fwd, BatchNorm folded into weight and bias), and the Frechet distance of
+ * two sets of up to 2048 features.  Everything runs eagerly on `stream`, never synchronises or allocates, uses no atomics (the same bits
+ * on every run) and refuses on the host before any launch: a null or unaligned pointer, an unknown dtype, channels that are no whole
+ * 16-byte chunks, an operand past the 32-bit offset range of the convolutions, a workspace that is too small.
+ *   mvldm_inception_prep      replaces cleanfid's resize_single_channel (compute_fid.py:46 -> cleanfid/resize.py, mode "clean"):
+ *                             src NCHW [n_img][3][h][w], uint8 (src_u8 = 1) or fp32 in [0, 1] (src_u8 = 0: multiplied by 255 in fp32 and NOT
+ *                             quantised) -> dst NHWC [n_img][oh][ow][c_pad] in `dtype`, c_pad = 4 (f32) / 8 (16 bit), pad channels zero.
+ *                             PIL's Image.resize(BICUBIC) on a float32 plane: antialiased and separable, horizontally first, a pass whose
+ *                             size stays is skipped.  Per axis scale = in / out, filterscale = max(scale, 1), support = 2 filterscale;
+ *                             output i: center = (i + 0.5) scale, xmin = max(0, int(center - support + 0.5)), xmax = min(in,
+ *                             int(center + support + 0.5)), k_j = cubic((j + xmin - center + 0.5) (1 / filterscale)) with a = -0.5,
+ *                             divided by their sum; the sum over the taps in double, in tap order, rounded to float32 at the end of each
+ *                             pass.  Then clip to [0, 255] and (v - 128) / 128 in fp32.  workspace: [n_img][3][h][ow] float32, the
+ *                             horizontal pass's output (mvldm_inception_workspace_bytes(n_img, h, ow)).
+ *   mvldm_inception_unfold    src NHWC [n_img][h][w][c] -> dst [n_img][h][w][kh kw c]: the kh x kw window around each pixel (stride 1,
+ *                             padding kh / 2, kw / 2), tap-major then channel, zero outside the map.  The 1 x 7, 7 x 1, 1 x 3, 3 x 1 and
+ *                             5 x 5 convolutions of torchvision's InceptionA / C / D / E blocks are then 1 x 1 convolutions whose weight is
+ *                             permuted to [n_out][kh][kw][c_in].  kh, kw odd, up to 7.
+ *   mvldm_inception_maxpool   F.max_pool2d(x, 3, stride, pad), stride 1 or 2, pad 0 or 1 (as -inf), the output size floored;
+ *   mvldm_inception_avgpool   F.avg_pool2d(x, 3, 1, 1, count_include_pad=False): the sum of the taps inside the map in fp64, divided by their
+ *                             number, rounded once;
+ *   mvldm_inception_concat    dst = src (relu = 1: max(src, 0)), src a contiguous [rows][c].  All three write channels [dst_c_off,
+ *                             dst_c_off + c) of rows of dst_ld channels: torch.cat(branches, 1) without a pass of its own.
+ *   mvldm_inception_features  feat NHWC [n_img][h][w][c] (after its ReLU) -> features[n_img][c] fp64: adaptive_avg_pool2d(x, 1), the pixels
+ *                             in order, fp64 from the first add.
+ *   mvldm_frechet_accumulate  state[0] += n, state[1 + a] += sum_i f[i][a], state[1 + d + a d + b] += sum_i f[i][a] f[i][b], the rows in
+ *                             order and added to the state once; d a multiple of 64 up to 2048 (np.mean / np.cov of cleanfid's
+ *                             get_folder_features output, kept as sums).
+ *   mvldm_frechet_compute     cleanfid.fid.frechet_distance: mu = sum / n, Sigma = (sum f^T f - n mu^T mu) / (n - 1); Sigma1 = V D V^T, then
+ *                             the eigenvalues lambda of D^1/2 V^T Sigma2 V D^1/2 (the spectrum of Sigma1^1/2 Sigma2 Sigma1^1/2; the package
+ *                             takes Re sqrtm(Sigma1 Sigma2)); score (fp32) = |mu1 - mu2|^2 + (tr Sigma1 + tr Sigma2) - 2 sum_i
+ *                             sqrt(max(lambda_i, 0)), all in fp64 with the matrices in the workspace (mvldm_frechet_workspace_bytes(d):
+ *                             16 + 4 d + 4 d d doubles).  Both eigen-solves are one-sided Jacobi (Hestenes) on the columns of G = A V:
+ *                             round-robin ordering, d / 2 disjoint column pairs a round, one launch a round with one workgroup a pair;
+ *                             the rotation of a pair comes from its three dot products and is applied when |g_p . g_q| >
+ *                             tol |g_p| |g_q|, tol = sqrt(d) 2^-52 (and |g_p| |g_q| > tol^2 |A|_F^2: two columns of round-off
+ *                             are left alone).  30 sweeps are enqueued; a sweep in which no pair passed tol sets a
+ *                             flag in the workspace that makes the launches behind it return at once -- the host reads nothing.  The
+ *                             first solve's eigenvalues are v_i . g_i, the second's |g_i|.  info (8 doubles): sweeps and the last
+ *                             sweep's largest |g_p . g_q| / (|g_p| |g_q|) of the first solve, of the second, the solves that were still
+ *                             rotating in sweep 30 (then the score is NaN, as for a state of fewer than 2 samples), the score in fp64,
+ *                             sum sqrt, and the other three terms.
+ * The two *_workspace_bytes are 0 for a refused shape.  Parity with clean-fid, PIL and the published weights: the resize is pinned against
+ * PIL's own output (tests/golden/cleanfid_resize.npz), the rest is a restatement ("parity unpinned"). */
+size_t mvldm_inception_workspace_bytes(int n_img, int h, int ow);
+int mvldm_inception_prep(const void* src, int src_u8, void* dst, int n_img, int h, int w, int oh, int ow, int c_pad, int dtype,
+                         void* workspace, size_t workspace_bytes, mvldm_stream_t stream);
+int mvldm_inception_unfold(const void* src, void* dst, int n_img, int h, int w, int c, int kh, int kw, int pad_h, int pad_w, int dtype,
+                           mvldm_stream_t stream);
+int mvldm_inception_maxpool(const void* src, void* dst, int n_img, int h, int w, int c, int stride, int pad, int dst_ld, int dst_c_off,
+                            int dtype, mvldm_stream_t stream);
+int mvldm_inception_avgpool(const void* src, void* dst, int n_img, int h, int w, int c, int dst_ld, int dst_c_off, int dtype,
+                            mvldm_stream_t stream);
+int mvldm_inception_concat(const void* src, void* dst, size_t rows, int c, int dst_ld, int dst_c_off, int relu, int dtype,
+                           mvldm_stream_t stream);
+int mvldm_inception_features(const void* feat, int n_img, int h, int w, int c, int dtype, double* features, mvldm_stream_t stream);
+int mvldm_frechet_accumulate(const double* features, int n, int d, double* state, mvldm_stream_t stream);
+size_t mvldm_frechet_workspace_bytes(int d);
+int mvldm_frechet_compute(const double* state1, const double* state2, int d, double* workspace, size_t workspace_bytes, float* score,
+                          double* info, mvldm_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Plans: a whole forward (UNet walk, VAE decoder, DDIM step) as a flat list of the ops above with

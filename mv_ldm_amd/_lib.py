@@ -245,6 +245,16 @@ SIGNATURES = {
     "mvldm_fid_pool": (C.c_int, [vp] + [C.c_int] * 5 + [vp, sz, vp]),
     "mvldm_fid_accumulate": (C.c_int, [vp, sz] + [C.c_int] * 4 + [vp, vp, vp]),
     "mvldm_fid_compute": (C.c_int, [vp, vp, C.c_int, vp, vp, vp]),
+    "mvldm_inception_workspace_bytes": (sz, [C.c_int] * 3),
+    "mvldm_inception_prep": (C.c_int, [vp, C.c_int, vp] + [C.c_int] * 7 + [vp, sz, vp]),
+    "mvldm_inception_unfold": (C.c_int, [vp, vp] + [C.c_int] * 9 + [vp]),
+    "mvldm_inception_maxpool": (C.c_int, [vp, vp] + [C.c_int] * 9 + [vp]),
+    "mvldm_inception_avgpool": (C.c_int, [vp, vp] + [C.c_int] * 7 + [vp]),
+    "mvldm_inception_concat": (C.c_int, [vp, vp, sz] + [C.c_int] * 5 + [vp]),
+    "mvldm_inception_features": (C.c_int, [vp] + [C.c_int] * 5 + [vp, vp]),
+    "mvldm_frechet_accumulate": (C.c_int, [vp, C.c_int, C.c_int, vp, vp]),
+    "mvldm_frechet_workspace_bytes": (sz, [C.c_int]),
+    "mvldm_frechet_compute": (C.c_int, [vp, vp, C.c_int, vp, sz, vp, vp, vp]),
     "mvldm_nchw_to_nhwc": (C.c_int, [vp, vp] + [C.c_int] * 6 + [f32, f32, vp, vp]),
     "mvldm_ray_channels": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "mvldm_ray_encode": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp] + [C.c_int] * 4 + [vp]),

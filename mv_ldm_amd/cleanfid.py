@@ -1,0 +1,506 @@
+"""Clean-FID on the device: the counterpart of `cleanfid.fid.compute_fid(dir, "gt_images")` as src/scripts/compute_fid.py:44-47 calls it
+(`mode="clean"`, `model_name="inception_v3"`): the `fidclean_*` column of the reference's evaluation.
+
+    python -m mv_ldm_amd.cleanfid DIR1 DIR2 --weights INCEPTION.pth [--json OUT]
+
+Every `*.png` under a folder (recursively, sorted) goes through the package's "clean" resize -- PIL's antialiased bicubic on float32
+planes, no re-quantisation --, `(x - 128) / 128`, the FID variant of Inception-v3 up to its 2048-wide pool, and the fp64 statistics; the
+score is the Frechet distance of the two sets.  The resize, the pools, the unfold that turns the 1 x 7 / 7 x 1 / 1 x 3 / 3 x 1 / 5 x 5
+convolutions into 1 x 1 ones, the running statistics and the 2048-wide eigen-solves are `csrc/inception.hip`; the 94 convolutions run
+through the implicit GEMM (`ops.conv2d`) with BatchNorm folded into weight and bias.  No PyTorch math and no PIL on this path.
+
+No pretrained file ships with this package and none is fetched: `load_weights` takes the user's file (torch-fidelity / pytorch-fid
+`pt_inception` key names).  The resize is pinned against PIL's own output (tests/golden/cleanfid_resize.npz); everything behind it is a
+restatement of the package's arithmetic ("parity unpinned").  `sum sqrt(eig(Sigma1 Sigma2))` is computed in its symmetric
+form, as `csrc/fid.hip` does; the package takes `scipy.linalg.sqrtm` and its real part.
+
+Float images: the package's input is uint8.  A float image in [0, 1] is multiplied by 255 in fp32 and NOT quantised; the command line
+always passes the decoded bytes.  KID (`compute_kid`) is not built: it needs only the `[n, 2048]` features `InceptionPool3.features`
+returns.
+"""
+from __future__ import annotations
+
+import json
+import math
+import sys
+import warnings
+from pathlib import Path
+from typing import Optional
+
+import torch
+from torch import nn
+
+from . import ops
+from .fid import BN_EPS, _BN
+from .lpips import _read
+
+SIZE = 299                      # the extractor's input edge
+FEATURES = 2048
+MAPS = ("stem", "Mixed_5d", "Mixed_6a", "Mixed_6e", "Mixed_7a", "Mixed_7c")      # what `features(return_maps=...)` can hand back
+_IGNORED = ("AuxLogits.", "fc.")
+
+
+def _layers():
+    """[(name, c_in, c_out, (kh, kw), stride, (pad_h, pad_w))] of the 94 BasicConv2d of the FID Inception-v3, in forward order"""
+    out = []
+
+    def add(name, c_in, c_out, k=(1, 1), stride=1, pad=(0, 0)):
+        out.append((name, c_in, c_out, k, stride, pad))
+
+    add("Conv2d_1a_3x3", 3, 32, (3, 3), 2)
+    add("Conv2d_2a_3x3", 32, 32, (3, 3))
+    add("Conv2d_2b_3x3", 32, 64, (3, 3), 1, (1, 1))
+    add("Conv2d_3b_1x1", 64, 80)
+    add("Conv2d_4a_3x3", 80, 192, (3, 3))
+    for name, c_in, pf in (("Mixed_5b", 192, 32), ("Mixed_5c", 256, 64), ("Mixed_5d", 288, 64)):
+        add(f"{name}.branch1x1", c_in, 64)
+        add(f"{name}.branch5x5_1", c_in, 48)
+        add(f"{name}.branch5x5_2", 48, 64, (5, 5), 1, (2, 2))
+        add(f"{name}.branch3x3dbl_1", c_in, 64)
+        add(f"{name}.branch3x3dbl_2", 64, 96, (3, 3), 1, (1, 1))
+        add(f"{name}.branch3x3dbl_3", 96, 96, (3, 3), 1, (1, 1))
+        add(f"{name}.branch_pool", c_in, pf)
+    add("Mixed_6a.branch3x3", 288, 384, (3, 3), 2)
+    add("Mixed_6a.branch3x3dbl_1", 288, 64)
+    add("Mixed_6a.branch3x3dbl_2", 64, 96, (3, 3), 1, (1, 1))
+    add("Mixed_6a.branch3x3dbl_3", 96, 96, (3, 3), 2)
+    for name, c7 in (("Mixed_6b", 128), ("Mixed_6c", 160), ("Mixed_6d", 160), ("Mixed_6e", 192)):
+        add(f"{name}.branch1x1", 768, 192)
+        add(f"{name}.branch7x7_1", 768, c7)
+        add(f"{name}.branch7x7_2", c7, c7, (1, 7), 1, (0, 3))
+        add(f"{name}.branch7x7_3", c7, 192, (7, 1), 1, (3, 0))
+        add(f"{name}.branch7x7dbl_1", 768, c7)
+        add(f"{name}.branch7x7dbl_2", c7, c7, (7, 1), 1, (3, 0))
+        add(f"{name}.branch7x7dbl_3", c7, c7, (1, 7), 1, (0, 3))
+        add(f"{name}.branch7x7dbl_4", c7, c7, (7, 1), 1, (3, 0))
+        add(f"{name}.branch7x7dbl_5", c7, 192, (1, 7), 1, (0, 3))
+        add(f"{name}.branch_pool", 768, 192)
+    add("Mixed_7a.branch3x3_1", 768, 192)
+    add("Mixed_7a.branch3x3_2", 192, 320, (3, 3), 2)
+    add("Mixed_7a.branch7x7x3_1", 768, 192)
+    add("Mixed_7a.branch7x7x3_2", 192, 192, (1, 7), 1, (0, 3))
+    add("Mixed_7a.branch7x7x3_3", 192, 192, (7, 1), 1, (3, 0))
+    add("Mixed_7a.branch7x7x3_4", 192, 192, (3, 3), 2)
+    for name, c_in in (("Mixed_7b", 1280), ("Mixed_7c", 2048)):
+        add(f"{name}.branch1x1", c_in, 320)
+        add(f"{name}.branch3x3_1", c_in, 384)
+        add(f"{name}.branch3x3_2a", 384, 384, (1, 3), 1, (0, 1))
+        add(f"{name}.branch3x3_2b", 384, 384, (3, 1), 1, (1, 0))
+        add(f"{name}.branch3x3dbl_1", c_in, 448)
+        add(f"{name}.branch3x3dbl_2", 448, 384, (3, 3), 1, (1, 1))
+        add(f"{name}.branch3x3dbl_3a", 384, 384, (1, 3), 1, (0, 1))
+        add(f"{name}.branch3x3dbl_3b", 384, 384, (3, 1), 1, (1, 0))
+        add(f"{name}.branch_pool", c_in, 192)
+    return out
+
+
+LAYERS = _layers()
+# elements per image of the largest operand of a launch: the 5 x 5 window of a 35 x 35 x 48 map, unfolded
+_LARGEST = 35 * 35 * 25 * 48
+
+
+class _Conv(nn.Module):
+    """parameter holder with nn.Conv2d's names; the kernel may be oblong"""
+
+    def __init__(self, c_out: int, c_in: int, kh: int, kw: int):
+        super().__init__()
+        self.weight = nn.Parameter(torch.empty(c_out, c_in, kh, kw), requires_grad=False)
+
+
+class _BasicConv(nn.Module):
+    def __init__(self, c_in: int, c_out: int, k):
+        super().__init__()
+        self.conv = _Conv(c_out, c_in, *k)
+        self.bn = _BN(c_out)
+
+
+def pack_conv(w: torch.Tensor, dtype: torch.dtype) -> ops.PackedWeight:
+    """fp32 `[n_out, c_in, kh, kw]` on the device -> the packed weight `conv` reads: a 1 x 1 or 3 x 3 kernel as the implicit GEMM takes
+    it, any other as the 1 x 1 weight `[n_out, kh kw c_in]` over the unfolded map (tap-major, then channel)"""
+    kh, kw = w.shape[2:]
+    if kh == kw and kh in (1, 3):
+        return ops.pack_weight(w, dtype)
+    return ops.pack_weight(w.permute(0, 2, 3, 1).reshape(w.shape[0], -1).contiguous(), dtype)
+
+
+def conv(x: torch.Tensor, pw: ops.PackedWeight, bias, k, stride: int = 1, pad=(0, 0)) -> torch.Tensor:
+    """the pre-activation convolution of NHWC `x`: 1 x 1 and 3 x 3 straight through `ops.conv2d`, every other kernel (stride 1, padding
+    that keeps the size) as `ops.inception_unfold` and a 1 x 1 convolution"""
+    kh, kw = k
+    if kh == kw and kh in (1, 3):
+        return ops.conv2d(x, pw, bias, stride=stride, pad=pad[0])
+    assert stride == 1 and tuple(pad) == (kh // 2, kw // 2)
+    return ops.conv2d(ops.inception_unfold(x, kh, kw), pw, bias, pad=0)
+
+
+class InceptionPool3(nn.Module):
+    """The FID Inception-v3 up to its 2048-wide pool; fp32 parameters under torch-fidelity's `pt_inception` key names
+    (`Mixed_6b.branch7x7_2.conv.weight`, `.bn.{weight,bias,running_mean,running_var}`).  `dtype`: the compute dtype of the activations and
+    packed weights (float32 by default: a metric; float16 / bfloat16 are allowed)."""
+
+    def __init__(self, weights=None, dtype: torch.dtype = torch.float32, allow_random_init: bool = False):
+        super().__init__()
+        if dtype not in (torch.float32, torch.float16, torch.bfloat16):
+            raise TypeError(f"InceptionPool3: compute dtype {dtype}")
+        self.compute_dtype = dtype
+        for name, c_in, c_out, k, _, _ in LAYERS:
+            parent = self
+            *path, leaf = name.split(".")
+            for p in path:
+                if not hasattr(parent, p):
+                    setattr(parent, p, nn.Module())
+                parent = getattr(parent, p)
+            setattr(parent, leaf, _BasicConv(c_in, c_out, k))
+        self._packs: dict = {}
+        self.reset_parameters()
+        if weights is not None:
+            self.load_weights(weights)
+        elif not allow_random_init:
+            warnings.warn("InceptionPool3(): no weight file given -- the module keeps RANDOM initial weights and its scores mean nothing "
+                          "(pass weights=... / call load_weights, or allow_random_init=True to silence)", stacklevel=2)
+
+    def reset_parameters(self, seed: Optional[int] = None):
+        """Kaiming-normal convs, BatchNorm close to the identity"""
+        g = None if seed is None else torch.Generator().manual_seed(seed)
+        with torch.no_grad():
+            for name, *_ in LAYERS:
+                m = self.get_submodule(name)
+                w = m.conv.weight
+                m.conv.weight.copy_(torch.randn(w.shape, generator=g) * math.sqrt(2.0 / (w.shape[1] * w.shape[2] * w.shape[3])))
+                m.bn.weight.copy_(0.5 + torch.rand(m.bn.weight.shape, generator=g))
+                m.bn.bias.copy_(0.1 * torch.randn(m.bn.bias.shape, generator=g))
+                m.bn.running_mean.copy_(0.1 * torch.randn(m.bn.running_mean.shape, generator=g))
+                m.bn.running_var.copy_(0.5 + torch.rand(m.bn.running_var.shape, generator=g))
+        self._packs.clear()
+
+    # ---- weights ---------------------------------------------------------------------------------------------------------------
+    def load_weights(self, weights) -> "InceptionPool3":
+        """`weights`: a state dict or the path of one (read with `torch.load(weights_only=True)`): torch-fidelity's `pt_inception` or the
+        same keys under `inception.`.  Ignored: `num_batches_tracked`, `fc.*`, `AuxLogits.*`.  Anything else, or a missing key, raises a
+        KeyError that names it; a wrong shape or a non-positive `running_var + 1e-3` a ValueError.  A refused file changes nothing."""
+        sd = _read(weights)
+        if any(k.startswith("inception.") for k in sd):
+            sd = {(k[len("inception."):] if k.startswith("inception.") else k): v for k, v in sd.items()}
+        want = dict(self.state_dict())
+        ignored = lambda k: k.endswith("num_batches_tracked") or k.startswith(_IGNORED)
+        missing = sorted(k for k in want if k not in sd)
+        unexpected = sorted(k for k in sd if k not in want and not ignored(k))
+        if missing or unexpected:
+            raise KeyError(f"InceptionPool3.load_weights: missing keys {missing}, unexpected keys {unexpected}")
+        for k, ref in want.items():
+            if tuple(sd[k].shape) != tuple(ref.shape):
+                raise ValueError(f"InceptionPool3.load_weights: {k} has shape {tuple(sd[k].shape)}, expected {tuple(ref.shape)}")
+            if k.endswith("running_var") and not bool((sd[k].detach().double() + BN_EPS > 0).all()):
+                raise ValueError(f"InceptionPool3.load_weights: {k} + {BN_EPS} is not positive everywhere; BatchNorm divides by its root")
+        with torch.no_grad():
+            for k, ref in want.items():
+                ref.copy_(sd[k].detach().to(torch.float32))
+        self._packs.clear()
+        return self
+
+    def _apply(self, fn, *args, **kw):
+        self._packs.clear()                     # .to(device) / .float(): the packs follow the parameters
+        return super()._apply(fn, *args, **kw)
+
+    def _packed(self, dtype: torch.dtype) -> dict:
+        """name -> (packed weight, fp32 bias) with BatchNorm folded in, in fp64 on the host"""
+        mods = [self.get_submodule(name) for name, *_ in LAYERS]
+        dev = mods[0].conv.weight.device
+        key = (dtype, str(dev))
+        version = tuple(t._version for m in mods for t in (m.conv.weight, m.bn.weight, m.bn.bias, m.bn.running_mean, m.bn.running_var))
+        hit = self._packs.get(key)
+        if hit is None or hit[0] != version:
+            packs = {}
+            for (name, *_), m in zip(LAYERS, mods):
+                var = m.bn.running_var.detach().double().cpu() + BN_EPS
+                if not bool((var > 0).all()):
+                    raise ValueError(f"InceptionPool3: {name}.bn.running_var + {BN_EPS} is not positive everywhere")
+                g = m.bn.weight.detach().double().cpu() / var.sqrt()
+                w = m.conv.weight.detach().double().cpu() * g.view(-1, 1, 1, 1)
+                b = m.bn.bias.detach().double().cpu() - m.bn.running_mean.detach().double().cpu() * g
+                packs[name] = (pack_conv(w.float().to(dev), dtype), b.float().to(dev))
+            hit = (version, packs)
+            self._packs[key] = hit
+        return hit[1]
+
+    # ---- the network -----------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def chunk_images(dtype: torch.dtype, h: int = SIZE, w: int = SIZE) -> int:
+        """images per launch: the largest operand (the unfolded 5 x 5 window of a 35 x 35 x 48 map, or the resize's intermediate
+        `[n, 3, h, 299]` float32) stays below 2 GiB"""
+        per_image = max(_LARGEST * (4 if dtype == torch.float32 else 2), 3 * h * SIZE * 4, 3 * h * w * 4)
+        return max(1, ((1 << 31) - 1) // per_image)
+
+    def workspace_bytes(self, n: int, h: int = SIZE, w: int = SIZE, dtype: Optional[torch.dtype] = None) -> int:
+        """bytes `features` / `CleanFID.update` need as `ws=` for n images of h x w: the resize's intermediate, then the features"""
+        m = min(n, self.chunk_images(self.compute_dtype if dtype is None else dtype, h, w))
+        return ops._roundup(ops.inception_workspace_bytes(m, h, SIZE), 16) + m * FEATURES * 8
+
+    def _check(self, imgs: torch.Tensor) -> torch.Tensor:
+        if not imgs.is_cuda:
+            raise RuntimeError("mv_ldm_amd modules run only on a HIP device (no CPU fallback): move the module and its inputs to 'cuda'")
+        if imgs.dim() != 4 or imgs.shape[1] != 3:
+            raise ValueError(f"InceptionPool3: imgs must be [n, 3, h, w], got {tuple(imgs.shape)}")
+        if imgs.dtype not in (torch.uint8, torch.float32, torch.float16, torch.bfloat16):
+            raise TypeError(f"InceptionPool3: imgs is {imgs.dtype}; uint8 images, or float images in [0, 1], are scored")
+        if not imgs.is_contiguous():
+            raise ValueError(f"InceptionPool3: imgs must be contiguous NCHW (got strides {imgs.stride()}); call .contiguous() first")
+        if self.Conv2d_1a_3x3.conv.weight.device != imgs.device:
+            raise RuntimeError(f"InceptionPool3: the module is on {self.Conv2d_1a_3x3.conv.weight.device}, the images on {imgs.device} "
+                               "(no CPU fallback: module.to('cuda'))")
+        if imgs.shape[2] < 1 or imgs.shape[3] < 1:
+            raise ValueError(f"InceptionPool3: imgs {tuple(imgs.shape)} has an empty edge")
+        return imgs if imgs.dtype in (torch.float32, torch.uint8) else ops.convert(imgs, torch.float32)
+
+    def _forward(self, x: torch.Tensor, packs: dict, keep: dict, wanted) -> torch.Tensor:
+        """the prepared NHWC input -> the post-ReLU 8 x 8 x 2048 map; every stored map is post-ReLU"""
+        spec = {name: (k, stride, pad) for name, _, _, k, stride, pad in LAYERS}
+
+        def cv(name, x, dst=None, off=0):
+            k, stride, pad = spec[name]
+            y = conv(x, packs[name][0], packs[name][1], k, stride, pad)
+            if dst is None:
+                return ops.lpips_relu(y)
+            return ops.inception_concat(y, dst, off, relu=True)
+
+        def new(x, h, w, c):
+            return torch.empty(x.shape[0], h, w, c, dtype=x.dtype, device=x.device)
+
+        def tap(name, x):
+            if name in wanted:
+                keep[name] = x
+            return x
+
+        x = cv("Conv2d_1a_3x3", x)
+        x = cv("Conv2d_2a_3x3", x)
+        x = cv("Conv2d_2b_3x3", x)
+        x = ops.inception_maxpool(x, 2, 0)
+        x = cv("Conv2d_3b_1x1", x)
+        x = cv("Conv2d_4a_3x3", x)
+        x = tap("stem", ops.inception_maxpool(x, 2, 0))
+        for name, pf in (("Mixed_5b", 32), ("Mixed_5c", 64), ("Mixed_5d", 64)):
+            out = new(x, x.shape[1], x.shape[2], 224 + pf)
+            cv(f"{name}.branch1x1", x, out, 0)
+            cv(f"{name}.branch5x5_2", cv(f"{name}.branch5x5_1", x), out, 64)
+            cv(f"{name}.branch3x3dbl_3", cv(f"{name}.branch3x3dbl_2", cv(f"{name}.branch3x3dbl_1", x)), out, 128)
+            cv(f"{name}.branch_pool", ops.inception_avgpool(x), out, 224)
+            x = tap(name, out)
+        h, w = (x.shape[1] - 3) // 2 + 1, (x.shape[2] - 3) // 2 + 1
+        out = new(x, h, w, 768)
+        cv("Mixed_6a.branch3x3", x, out, 0)
+        cv("Mixed_6a.branch3x3dbl_3", cv("Mixed_6a.branch3x3dbl_2", cv("Mixed_6a.branch3x3dbl_1", x)), out, 384)
+        ops.inception_maxpool(x, 2, 0, out, 480)
+        x = tap("Mixed_6a", out)
+        for name in ("Mixed_6b", "Mixed_6c", "Mixed_6d", "Mixed_6e"):
+            out = new(x, x.shape[1], x.shape[2], 768)
+            cv(f"{name}.branch1x1", x, out, 0)
+            cv(f"{name}.branch7x7_3", cv(f"{name}.branch7x7_2", cv(f"{name}.branch7x7_1", x)), out, 192)
+            y = cv(f"{name}.branch7x7dbl_1", x)
+            for j in (2, 3, 4):
+                y = cv(f"{name}.branch7x7dbl_{j}", y)
+            cv(f"{name}.branch7x7dbl_5", y, out, 384)
+            cv(f"{name}.branch_pool", ops.inception_avgpool(x), out, 576)
+            x = tap(name, out)
+        h, w = (x.shape[1] - 3) // 2 + 1, (x.shape[2] - 3) // 2 + 1
+        out = new(x, h, w, 1280)
+        cv("Mixed_7a.branch3x3_2", cv("Mixed_7a.branch3x3_1", x), out, 0)
+        y = cv("Mixed_7a.branch7x7x3_1", x)
+        y = cv("Mixed_7a.branch7x7x3_3", cv("Mixed_7a.branch7x7x3_2", y))
+        cv("Mixed_7a.branch7x7x3_4", y, out, 320)
+        ops.inception_maxpool(x, 2, 0, out, 512)
+        x = tap("Mixed_7a", out)
+        for name in ("Mixed_7b", "Mixed_7c"):
+            out = new(x, x.shape[1], x.shape[2], 2048)
+            cv(f"{name}.branch1x1", x, out, 0)
+            y = cv(f"{name}.branch3x3_1", x)
+            cv(f"{name}.branch3x3_2a", y, out, 320)
+            cv(f"{name}.branch3x3_2b", y, out, 704)
+            y = cv(f"{name}.branch3x3dbl_2", cv(f"{name}.branch3x3dbl_1", x))
+            cv(f"{name}.branch3x3dbl_3a", y, out, 1088)
+            cv(f"{name}.branch3x3dbl_3b", y, out, 1472)
+            pooled = ops.inception_avgpool(x) if name == "Mixed_7b" else ops.inception_maxpool(x, 1, 1)
+            cv(f"{name}.branch_pool", pooled, out, 1856)
+            x = tap(name, out)
+        return x
+
+    def _run(self, imgs: torch.Tensor, out: Optional[torch.Tensor], state: Optional[torch.Tensor], dtype, ws, wanted=()):
+        imgs = self._check(imgs)
+        bad = [m for m in wanted if m not in MAPS]
+        if bad:
+            raise ValueError(f"InceptionPool3: return_maps {bad}; known: {MAPS}")
+        dtype = self.compute_dtype if dtype is None else dtype
+        n, _, h, w = imgs.shape
+        maps = {m: [] for m in wanted}
+        if n == 0:
+            return maps
+        step = min(n, self.chunk_images(dtype, h, w))
+        need = self.workspace_bytes(step, h, w, dtype)
+        if ws is None:
+            ws = ops.workspace(need, imgs.device, "cleanfid")
+        if ws.numel() * ws.element_size() < need:
+            raise ValueError(f"InceptionPool3: workspace of {ws.numel() * ws.element_size()} bytes, need {need}")
+        prep_bytes = ops._roundup(ops.inception_workspace_bytes(step, h, SIZE), 16)
+        ws = ws.view(torch.uint8).view(-1)
+        packs = self._packed(dtype)
+        for i0 in range(0, n, step):
+            m = min(step, n - i0)
+            x = ops.inception_prep(imgs[i0:i0 + m], dtype, SIZE, SIZE, ws[:prep_bytes])
+            keep: dict = {}
+            x = self._forward(x, packs, keep, wanted)
+            f = ws[prep_bytes:prep_bytes + m * FEATURES * 8].view(torch.float64).view(m, FEATURES) if out is None else out[i0:i0 + m]
+            ops.inception_features(x, f)
+            if state is not None:
+                ops.frechet_accumulate(f, state)
+            for k, v in keep.items():
+                maps[k].append(v)
+        return maps
+
+    @torch.no_grad()
+    def features(self, imgs: torch.Tensor, *, dtype: Optional[torch.dtype] = None, out: Optional[torch.Tensor] = None,
+                 ws: Optional[torch.Tensor] = None, return_maps=()):
+        """uint8 `[n, 3, h, w]`, or float in [0, 1] -> the fp64 `[n, 2048]` features on the device.  `return_maps`: names out of `MAPS`;
+        then `(features, {name: post-ReLU NHWC map})` is returned."""
+        n = imgs.shape[0]
+        out = torch.empty(n, FEATURES, dtype=torch.float64, device=imgs.device) if out is None else out
+        assert out.dtype == torch.float64 and out.is_contiguous() and tuple(out.shape) == (n, FEATURES)
+        maps = self._run(imgs, out, None, dtype, ws, tuple(return_maps))
+        if not return_maps:
+            return out
+        return out, {k: (v[0] if len(v) == 1 else torch.cat(v)) for k, v in maps.items()}
+
+    def forward(self, *args, **kw):
+        raise NotImplementedError("InceptionPool3: call features(imgs)")
+
+
+class CleanFID(nn.Module):
+    """`update(imgs, real)`, `compute()`, `reset()` around an `InceptionPool3`.  The two running states (count, sum f, sum f^T f; fp64,
+    1 + 2048 + 2048^2 doubles each) live on the device; the sample counts are kept on the host too, so `compute()` can refuse without
+    a synchronisation."""
+
+    def __init__(self, model: InceptionPool3):
+        super().__init__()
+        self.model = model
+        dev = model.Conv2d_1a_3x3.conv.weight.device
+        size = ops.frechet_state_size(FEATURES)
+        self.register_buffer("real_state", torch.zeros(size, dtype=torch.float64, device=dev), persistent=False)
+        self.register_buffer("fake_state", torch.zeros(size, dtype=torch.float64, device=dev), persistent=False)
+        self.register_buffer("info", torch.zeros(ops.FID_INFO, dtype=torch.float64, device=dev), persistent=False)
+        self._n = {True: 0, False: 0}
+
+    def _apply(self, fn, *args, **kw):
+        out = super()._apply(fn, *args, **kw)
+        for name in ("real_state", "fake_state", "info"):      # the statistics stay fp64 whatever the module is cast to
+            if self._buffers[name].dtype != torch.float64:
+                self._buffers[name] = self._buffers[name].double()
+        return out
+
+    @torch.no_grad()
+    def update(self, imgs: torch.Tensor, real: bool, *, dtype: Optional[torch.dtype] = None, ws: Optional[torch.Tensor] = None) -> None:
+        """adds `[n, 3, h, w]` images to the real or the fake side.  `ws` (uint8, at least `model.workspace_bytes(n, h, w)`) lets a captured
+        graph own its buffer."""
+        if imgs.is_cuda and self.real_state.device != imgs.device:
+            raise RuntimeError(f"CleanFID: the states are on {self.real_state.device}, the images on {imgs.device} (no CPU fallback: module.to('cuda'))")
+        self.model._run(imgs, None, self.real_state if real else self.fake_state, dtype, ws)
+        self._n[bool(real)] += int(imgs.shape[0])
+
+    @torch.no_grad()
+    def compute(self, *, out: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """the 0-d fp32 score on the device.  Raises below 2 samples on a side (host counters: no synchronisation).  `self.info` then
+        holds the solves' record (`ops.frechet_compute`)."""
+        if self._n[True] < 2 or self._n[False] < 2:
+            raise RuntimeError("More than one sample is required for both the real and fake distributed to compute FID")
+        out = torch.empty((), dtype=torch.float32, device=self.real_state.device) if out is None else out
+        ops.frechet_compute(self.real_state, self.fake_state, out, self.info, ws)
+        return out.view(())
+
+    def reset(self) -> None:
+        """both sides empty again (stream-ordered fills of the two states)"""
+        self.real_state.zero_()
+        self.fake_state.zero_()
+        self._n = {True: 0, False: 0}
+
+    def forward(self, *args, **kw):
+        raise NotImplementedError("CleanFID: call update(imgs, real) / compute() / reset()")
+
+
+# ---- folders ------------------------------------------------------------------------------------------------------------------------
+def list_images(folder) -> list:
+    """every `*.png` under `folder`, recursively, in sorted order (the package's `sorted(glob(..., recursive=True))`)"""
+    folder = Path(folder)
+    if not folder.is_dir():
+        raise FileNotFoundError(f"cleanfid: {folder} is not a folder")
+    return sorted(p for p in folder.rglob("*.png") if p.is_file())
+
+
+def iter_batches(folder, batch: int = 32):
+    """uint8 `[m, 3, h, w]` host tensors of the folder's images: sorted order, split by image size (sizes in order of first appearance),
+    at most `batch` images each"""
+    from .image_io import load_image
+    groups: dict = {}
+    for p in list_images(folder):
+        img = (load_image(p) * 255).round().to(torch.uint8)       # k / 255 back to the decoded byte k, exactly
+        groups.setdefault(tuple(img.shape[1:]), []).append(img)
+    for imgs in groups.values():
+        for i in range(0, len(imgs), batch):
+            yield torch.stack(imgs[i:i + batch]).contiguous()
+
+
+def score_folders(dir1, dir2, metric: CleanFID, batch: int = 32, dtype: Optional[torch.dtype] = None) -> dict:
+    """{"fidclean", "n1", "n2", "solve": {...}} of two folders, which need not pair up: a distance of two distributions"""
+    dev = metric.real_state.device
+    metric.reset()
+    counts = []
+    for folder, real in ((dir1, False), (dir2, True)):
+        n = 0
+        for imgs in iter_batches(folder, batch):
+            metric.update(imgs.to(dev), real=real, dtype=dtype)
+            n += imgs.shape[0]
+        if n == 0:
+            raise ValueError(f"cleanfid: no *.png under {folder}")
+        counts.append(n)
+    score = float(metric.compute())
+    info = metric.info.tolist()
+    metric.reset()
+    return {"fidclean": score, "n1": counts[0], "n2": counts[1],
+            "solve": {"sweeps": [int(info[0]), int(info[2])], "residual": [info[1], info[3]], "capped": int(info[4]), "fid_fp64": info[5],
+                      "sum_sqrt": info[6], "scale": info[7]}}
+
+
+def _not_empty(*folders) -> None:
+    """refuse before any weight is read or any launch is made"""
+    for folder in folders:
+        if not list_images(folder):
+            raise ValueError(f"cleanfid: no *.png under {folder}")
+
+
+def compute_fid(dir1, dir2, weights, device="cuda", batch: int = 32, dtype: torch.dtype = torch.float32) -> float:
+    """`cleanfid.fid.compute_fid(dir1, dir2)` with the Inception-v3 weights of `weights` (a path or a state dict)"""
+    _not_empty(dir1, dir2)
+    model = weights if isinstance(weights, InceptionPool3) else InceptionPool3(weights=weights, dtype=dtype).to(device)
+    return score_folders(dir1, dir2, CleanFID(model), batch, dtype)["fidclean"]
+
+
+def main(argv=None) -> int:
+    import argparse
+    ap = argparse.ArgumentParser(prog="python -m mv_ldm_amd.cleanfid", description="clean-fid's compute_fid of two PNG folders on the device")
+    ap.add_argument("dir1")
+    ap.add_argument("dir2")
+    ap.add_argument("--weights", required=True, help="pt_inception state dict (torch-fidelity / pytorch-fid key names)")
+    ap.add_argument("--json", default=None, help="write the record here too")
+    ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--dtype", default="float32", choices=("float32", "float16", "bfloat16"))
+    a = ap.parse_args(argv)
+    dtype = getattr(torch, a.dtype)
+    _not_empty(a.dir1, a.dir2)
+    model = InceptionPool3(weights=a.weights, dtype=dtype).to("cuda")
+    rec = score_folders(a.dir1, a.dir2, CleanFID(model), a.batch, dtype)
+    s = rec["solve"]
+    print(f"fidclean {rec['fidclean']:.6f}  ({rec['n1']} vs {rec['n2']} images; solves: {s['sweeps'][0]} + {s['sweeps'][1]} sweeps, "
+          f"residual {s['residual'][0]:.1e}, {s['residual'][1]:.1e}, capped {s['capped']})")
+    if a.json:
+        Path(a.json).write_text(json.dumps(rec, indent=1))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

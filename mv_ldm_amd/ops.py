@@ -879,3 +879,113 @@ def fid_compute(state1: torch.Tensor, state2: torch.Tensor, out: torch.Tensor, i
     assert out.dtype == torch.float32 and out.numel() == 1 and info.dtype == torch.float64 and info.is_contiguous() and info.numel() == FID_INFO
     L.check(L.load().mvldm_fid_compute(state1.data_ptr(), state2.data_ptr(), c, out.data_ptr(), info.data_ptr(), stream()))
     return out
+
+
+# ------------------------------------------------------------------------------------------ Clean-FID glue (csrc/inception.hip)
+FRECHET_MAX_D = 2048                           # the widest feature vector `frechet_compute` takes (Inception-v3's pool3)
+
+
+def frechet_state_size(d: int) -> int:
+    """doubles of one side's running state at width d: count, sum f, sum f^T f"""
+    return 1 + d + d * d
+
+
+def inception_workspace_bytes(n_img: int, h: int, ow: int) -> int:
+    """bytes `inception_prep` needs for n_img images of height h resized to width ow: the horizontal pass's float32 output"""
+    return int(L.load().mvldm_inception_workspace_bytes(n_img, h, ow))
+
+
+def inception_prep(imgs: torch.Tensor, dtype: torch.dtype, oh: int = 299, ow: int = 299, ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """uint8 or fp32-in-[0, 1] NCHW `[n, 3, h, w]` -> NHWC `[n, oh, ow, c_pad]` in `dtype`: PIL's bicubic on float32 planes as clean-fid's
+    "clean" mode calls it, clip to [0, 255], (x - 128) / 128.  A float image is multiplied by 255 and not quantised."""
+    assert imgs.is_cuda and imgs.is_contiguous() and imgs.dim() == 4 and imgs.shape[1] == 3 and imgs.dtype in (torch.float32, torch.uint8)
+    n, _, h, w = imgs.shape
+    dst = torch.empty(n, oh, ow, epc(dtype), dtype=dtype, device=imgs.device)
+    if ws is None:
+        ws = workspace(inception_workspace_bytes(n, h, ow), imgs.device, "cleanfid")
+    L.check(L.load().mvldm_inception_prep(imgs.data_ptr(), int(imgs.dtype == torch.uint8), dst.data_ptr(), n, h, w, oh, ow, dst.shape[-1], dt(dtype),
+                                          ws.data_ptr(), ws.numel() * ws.element_size(), stream()))
+    return dst
+
+
+def inception_unfold(x: torch.Tensor, kh: int, kw: int) -> torch.Tensor:
+    """NHWC `[n, h, w, c]` -> `[n, h, w, kh kw c]`: the kh x kw window around each pixel (padding kh // 2, kw // 2), tap-major then
+    channel, zero outside the map"""
+    assert x.is_cuda and x.is_contiguous() and x.dim() == 4
+    n, h, w, c = x.shape
+    out = torch.empty(n, h, w, kh * kw * c, dtype=x.dtype, device=x.device)
+    L.check(L.load().mvldm_inception_unfold(x.data_ptr(), out.data_ptr(), n, h, w, c, kh, kw, kh // 2, kw // 2, dt(x), stream()))
+    return out
+
+
+def _slice_of(dst: Optional[torch.Tensor], c_off: int, n: int, oh: int, ow: int, c: int, like: torch.Tensor):
+    if dst is None:
+        assert c_off == 0
+        return torch.empty(n, oh, ow, c, dtype=like.dtype, device=like.device)
+    assert dst.is_cuda and dst.is_contiguous() and dst.dtype == like.dtype and tuple(dst.shape[:3]) == (n, oh, ow) and c_off + c <= dst.shape[-1]
+    return dst
+
+
+def inception_maxpool(x: torch.Tensor, stride: int, pad: int, dst: Optional[torch.Tensor] = None, c_off: int = 0) -> torch.Tensor:
+    """3 x 3 max-pool of NHWC `[n, h, w, c]` (padding as -inf, floored size) into channels [c_off, c_off + c) of `dst` (a new map if None)"""
+    assert x.is_cuda and x.is_contiguous() and x.dim() == 4
+    n, h, w, c = x.shape
+    out = _slice_of(dst, c_off, n, (h + 2 * pad - 3) // stride + 1, (w + 2 * pad - 3) // stride + 1, c, x)
+    L.check(L.load().mvldm_inception_maxpool(x.data_ptr(), out.data_ptr(), n, h, w, c, stride, pad, out.shape[-1], c_off, dt(x), stream()))
+    return out
+
+
+def inception_avgpool(x: torch.Tensor, dst: Optional[torch.Tensor] = None, c_off: int = 0) -> torch.Tensor:
+    """3 x 3 / stride 1 / padding 1 average of NHWC `[n, h, w, c]`, divided by the taps inside the map, into a channel slice of `dst`"""
+    assert x.is_cuda and x.is_contiguous() and x.dim() == 4
+    n, h, w, c = x.shape
+    out = _slice_of(dst, c_off, n, h, w, c, x)
+    L.check(L.load().mvldm_inception_avgpool(x.data_ptr(), out.data_ptr(), n, h, w, c, out.shape[-1], c_off, dt(x), stream()))
+    return out
+
+
+def inception_concat(x: torch.Tensor, dst: torch.Tensor, c_off: int, relu: bool = False) -> torch.Tensor:
+    """the contiguous NHWC `x` (ReLU applied if asked) into channels [c_off, c_off + c) of the wider NHWC `dst`"""
+    assert x.is_cuda and x.is_contiguous() and dst.is_contiguous() and dst.dtype == x.dtype and dst.shape[:-1] == x.shape[:-1]
+    c = x.shape[-1]
+    assert c_off + c <= dst.shape[-1]
+    L.check(L.load().mvldm_inception_concat(x.data_ptr(), dst.data_ptr(), x.numel() // c, c, dst.shape[-1], c_off, int(bool(relu)), dt(x), stream()))
+    return dst
+
+
+def inception_features(x: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """NHWC `[n, h, w, c]` -> out fp64 `[n, c]`: the mean over the map, fp64 from the first add"""
+    assert x.is_cuda and x.is_contiguous() and x.dim() == 4
+    n, h, w, c = x.shape
+    assert out.dtype == torch.float64 and out.is_contiguous() and out.numel() == n * c
+    L.check(L.load().mvldm_inception_features(x.data_ptr(), n, h, w, c, dt(x), out.data_ptr(), stream()))
+    return out
+
+
+def frechet_accumulate(features: torch.Tensor, state: torch.Tensor) -> None:
+    """state (fp64, 1 + d + d d: count, sum f, sum f^T f) += the rows of `features` (fp64 `[n, d]`), in order"""
+    assert features.dtype == torch.float64 and features.is_contiguous() and features.dim() == 2
+    n, d = features.shape
+    assert state.dtype == torch.float64 and state.is_contiguous() and state.numel() == frechet_state_size(d)
+    L.check(L.load().mvldm_frechet_accumulate(features.data_ptr(), n, d, state.data_ptr(), stream()))
+
+
+def frechet_workspace_bytes(d: int) -> int:
+    """bytes `frechet_compute` needs at width d (four d x d fp64 matrices and a little more); 0 for a refused width"""
+    return int(L.load().mvldm_frechet_workspace_bytes(d))
+
+
+def frechet_compute(state1: torch.Tensor, state2: torch.Tensor, out: torch.Tensor, info: torch.Tensor, ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out (fp32, one element) = the Frechet distance of two states of d features, d a multiple of 64 up to 2048; info (fp64 `[FID_INFO]`):
+    sweeps and last residual of the first solve, of the second, solves still rotating at the sweep cap (then `out` is NaN), the score in
+    fp64, sum sqrt(lambda), |mu1 - mu2|^2 + tr Sigma1 + tr Sigma2"""
+    for t in (state1, state2):
+        assert t.dtype == torch.float64 and t.is_contiguous()
+    d = int(round((-1 + (1 + 4 * (state1.numel() - 1)) ** 0.5) / 2))
+    assert state1.numel() == state2.numel() == frechet_state_size(d)
+    assert out.dtype == torch.float32 and out.numel() == 1 and info.dtype == torch.float64 and info.is_contiguous() and info.numel() == FID_INFO
+    if ws is None:
+        ws = workspace(frechet_workspace_bytes(d), state1.device, "frechet")
+    L.check(L.load().mvldm_frechet_compute(state1.data_ptr(), state2.data_ptr(), d, ws.data_ptr(), ws.numel() * ws.element_size(), out.data_ptr(),
+                                           info.data_ptr(), stream()))
+    return out
