@@ -38,7 +38,9 @@ extern "C" {
  *    implicit GEMM): new symbols only, the number stays 7.
  *    + mvldm_inception_prep / _unfold / _maxpool / _avgpool / _concat / _features, mvldm_inception_workspace_bytes, mvldm_frechet_accumulate /
  *    _compute, mvldm_frechet_workspace_bytes (Clean-FID: the whole Inception-v3 and a Frechet distance up to 2048 features): new symbols
- *    only, the number stays 7. */
+ *    only, the number stays 7.
+ *    + mvldm_kid_compute, mvldm_kid_workspace_bytes (Clean-KID: the subset Gram sums on the fp64 matrix cores): new symbols only, the number
+ *    stays 7. */
 #define MVLDM_ABI_VERSION 7
 
 typedef void* mvldm_stream_t; /* hipStream_t */
@@ -670,6 +672,32 @@ int mvldm_frechet_accumulate(const double* features, int n, int d, double* state
 size_t mvldm_frechet_workspace_bytes(int d);
 int mvldm_frechet_compute(const double* state1, const double* state2, int d, double* workspace, size_t workspace_bytes, float* score,
                           double* info, mvldm_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Clean-KID: `cleanfid.fid.compute_kid(dir, "gt_images")` (src/scripts/compute_fid.py:44-47) behind the features, i.e. the package's
+ * kernel_distance(feats1, feats2, num_subsets, max_subset_size) with the subsets as an explicit input:
+ *   x_s = rows idx2[s][0 .. m) of f2 [n2][d], y_s = rows idx1[s][0 .. m) of f1 [n1][d]   (the package draws the x side first)
+ *   A_s = sum_{i != j} (x_i . x_j / d + 1)^3 + sum_{i != j} (y_i . y_j / d + 1)^3,  B_s = sum_{i, j} (x_i . y_j / d + 1)^3
+ *   per_subset[s] = A_s / (m - 1) - 2 B_s / m,  kid = sum_s per_subset[s] / num_subsets / m
+ * all in fp64 (the package's features and products are float32).  No m x m matrix is ever stored: a workgroup owns one 64 x 64 tile of
+ * one Gram of one subset, gathers the rows through LDS in 128-byte pieces, multiplies on v_mfma_f64_16x16x4_f64, cubes, masks (rows and
+ * columns at or beyond m, the diagonal of the two symmetric Grams) and reduces the tile in a fixed tree to one double of the workspace;
+ * the symmetric Grams run only the tile pairs a <= b and count a < b twice.  A second launch adds a subset's tiles in index order, a
+ * third the subsets in order: no floating-point atomics, the same bits on every call; nothing allocates or synchronises.
+ *   mvldm_kid_workspace_bytes  num_subsets (T (T + 1) + T T + 2) doubles, T = ceil(m / 64); 0 for m < 2 or num_subsets < 1.
+ *   mvldm_kid_compute          score (fp32) = (float)info[0]; per_subset [num_subsets] may be NULL (the values then stay in the
+ *                              workspace); info (4 doubles): kid in fp64, the mean over s of scale_s / m with scale_s = |A_s| / (m - 1) +
+ *                              2 |B_s| / m (what an error of the sums is measured against), m, the number of subsets with an index
+ *                              outside [0, n).  Such an index is clamped before it is used as an address -- no read leaves f1[0 .. n1 d)
+ *                              or f2[0 .. n2 d) --, its subset's value is NaN and so is the score; the other subsets are unaffected.
+ *                              MVLDM_ERR_ARG: m < 2, m > min(n1, n2), num_subsets < 1, a short workspace, a null or unaligned pointer
+ *                              (f1, f2: 16 bytes).  MVLDM_ERR_UNSUPPORTED: d no multiple of 64 or above 2048 (the widths
+ *                              mvldm_frechet_* takes).
+ * Parity with the clean-fid package is unpinned (it is not installed): the arithmetic above is a restatement. */
+size_t mvldm_kid_workspace_bytes(int m, int num_subsets);
+int mvldm_kid_compute(const double* f1, int n1, const double* f2, int n2, int d, const int32_t* idx1, const int32_t* idx2, int num_subsets,
+                      int m, double* workspace, size_t workspace_bytes, float* score, double* per_subset /* [num_subsets], may be NULL */,
+                      double* info /* [4] */, mvldm_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Plans: a whole forward (UNet walk, VAE decoder, DDIM step) as a flat list of the ops above with

@@ -255,6 +255,8 @@ SIGNATURES = {
     "mvldm_frechet_accumulate": (C.c_int, [vp, C.c_int, C.c_int, vp, vp]),
     "mvldm_frechet_workspace_bytes": (sz, [C.c_int]),
     "mvldm_frechet_compute": (C.c_int, [vp, vp, C.c_int, vp, sz, vp, vp, vp]),
+    "mvldm_kid_workspace_bytes": (sz, [C.c_int, C.c_int]),
+    "mvldm_kid_compute": (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, sz, vp, vp, vp, vp]),
     "mvldm_nchw_to_nhwc": (C.c_int, [vp, vp] + [C.c_int] * 6 + [f32, f32, vp, vp]),
     "mvldm_ray_channels": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "mvldm_ray_encode": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp] + [C.c_int] * 4 + [vp]),

@@ -1,7 +1,8 @@
-"""Clean-FID on the device: the counterpart of `cleanfid.fid.compute_fid(dir, "gt_images")` as src/scripts/compute_fid.py:44-47 calls it
-(`mode="clean"`, `model_name="inception_v3"`): the `fidclean_*` column of the reference's evaluation.
+"""Clean-FID and Clean-KID on the device: the counterparts of `cleanfid.fid.compute_fid(dir, "gt_images")` and
+`cleanfid.fid.compute_kid(dir, "gt_images")` as src/scripts/compute_fid.py:44-47 calls them (`mode="clean"`, `model_name="inception_v3"`):
+the `fidclean_*` and `kidclean_*` columns of the reference's evaluation.
 
-    python -m mv_ldm_amd.cleanfid DIR1 DIR2 --weights INCEPTION.pth [--json OUT]
+    python -m mv_ldm_amd.cleanfid DIR1 DIR2 --weights INCEPTION.pth [--json OUT] [--kid [--kid-seed N] [--kid-subsets S] [--kid-subset-size M]]
 
 Every `*.png` under a folder (recursively, sorted) goes through the package's "clean" resize -- PIL's antialiased bicubic on float32
 planes, no re-quantisation --, `(x - 128) / 128`, the FID variant of Inception-v3 up to its 2048-wide pool, and the fp64 statistics; the
@@ -15,8 +16,15 @@ restatement of the package's arithmetic ("parity unpinned").  `su
 form, as `csrc/fid.hip` does; the package takes `scipy.linalg.sqrtm` and its real part.
 
 Float images: the package's input is uint8.  A float image in [0, 1] is multiplied by 255 in fp32 and NOT quantised; the command line
-always passes the decoded bytes.  KID (`compute_kid`) is not built: it needs only the `[n, 2048]` features `InceptionPool3.features`
-returns.
+always passes the decoded bytes.
+
+KID is the package's `kernel_distance(feats1, feats2, num_subsets=100, max_subset_size=1000)` on the same features: per subset m =
+min(n1, n2, max_subset_size) rows a side, the cubic kernel `(x . y / d + 1)^3`, the unbiased estimate, averaged (`csrc/kid.hip`: the Gram
+tiles on the fp64 matrix cores, never an m x m matrix in memory).  Two differences to the package, both on purpose: its features are
+float32 and its products run in float32, here the features are the fp64 ones and everything is fp64; and it draws the subsets from
+numpy's global legacy stream, which the reference never seeds (it seeds torch only), so its own `kidclean` changes from run to run --
+here the subsets are an explicit input (`kid_subsets`, in the package's draw order: `np.random.seed(s)` before a `seed=None` call selects
+the subsets the package would draw), as noise is everywhere else at this boundary.
 """
 from __future__ import annotations
 
@@ -27,6 +35,7 @@ import warnings
 from pathlib import Path
 from typing import Optional
 
+import numpy as np
 import torch
 from torch import nn
 
@@ -377,9 +386,11 @@ class CleanFID(nn.Module):
     1 + 2048 + 2048^2 doubles each) live on the device; the sample counts are kept on the host too, so `compute()` can refuse without
     a synchronisation."""
 
-    def __init__(self, model: InceptionPool3):
+    def __init__(self, model: InceptionPool3, keep_features: bool = False):
         super().__init__()
         self.model = model
+        self.keep_features = bool(keep_features)
+        self._feats = {True: [], False: []}
         dev = model.Conv2d_1a_3x3.conv.weight.device
         size = ops.frechet_state_size(FEATURES)
         self.register_buffer("real_state", torch.zeros(size, dtype=torch.float64, device=dev), persistent=False)
@@ -400,7 +411,13 @@ class CleanFID(nn.Module):
         graph own its buffer."""
         if imgs.is_cuda and self.real_state.device != imgs.device:
             raise RuntimeError(f"CleanFID: the states are on {self.real_state.device}, the images on {imgs.device} (no CPU fallback: module.to('cuda'))")
-        self.model._run(imgs, None, self.real_state if real else self.fake_state, dtype, ws)
+        state = self.real_state if real else self.fake_state
+        if self.keep_features and imgs.dim() == 4 and imgs.shape[0] > 0:
+            f = torch.empty(imgs.shape[0], FEATURES, dtype=torch.float64, device=imgs.device)
+            self.model._run(imgs, f, state, dtype, ws)
+            self._feats[bool(real)].append(f)
+        else:
+            self.model._run(imgs, None, state, dtype, ws)
         self._n[bool(real)] += int(imgs.shape[0])
 
     @torch.no_grad()
@@ -413,14 +430,88 @@ class CleanFID(nn.Module):
         ops.frechet_compute(self.real_state, self.fake_state, out, self.info, ws)
         return out.view(())
 
+    def features(self, real: bool) -> torch.Tensor:
+        """the kept fp64 `[n, 2048]` features of one side, in the order of the `update` calls (`keep_features=True` only)"""
+        if not self.keep_features:
+            raise RuntimeError("CleanFID: the features are folded into the moments and dropped; construct with keep_features=True")
+        kept = self._feats[bool(real)]
+        if not kept:
+            return torch.empty(0, FEATURES, dtype=torch.float64, device=self.real_state.device)
+        return kept[0] if len(kept) == 1 else torch.cat(kept)
+
+    @torch.no_grad()
+    def compute_kid(self, num_subsets: int = 100, max_subset_size: int = 1000, seed=None, **buffers) -> torch.Tensor:
+        """the 0-d fp32 KID of the kept features, fake = `feats1`, real = `feats2` (`score_folders`' dir1 / dir2).  `buffers`: what
+        `kernel_distance` takes (`subsets=`, `out=`, `info=`, `per_subset=`, `ws=`)."""
+        if not self.keep_features:
+            raise RuntimeError("CleanFID.compute_kid: KID needs the features themselves; construct with keep_features=True")
+        return kernel_distance(self.features(False), self.features(True), num_subsets, max_subset_size, seed, **buffers)
+
     def reset(self) -> None:
-        """both sides empty again (stream-ordered fills of the two states)"""
+        """both sides empty again (stream-ordered fills of the two states); the kept features are dropped"""
         self.real_state.zero_()
         self.fake_state.zero_()
         self._n = {True: 0, False: 0}
+        self._feats = {True: [], False: []}
 
     def forward(self, *args, **kw):
         raise NotImplementedError("CleanFID: call update(imgs, real) / compute() / reset()")
+
+
+# ---- KID ------------------------------------------------------------------------------------------------------------------------------
+def kid_subsets(n1: int, n2: int, num_subsets: int = 100, max_subset_size: int = 1000, seed=None):
+    """host int32 `(idx1 [S, m], idx2 [S, m])`, m = min(n1, n2, max_subset_size): rows of feats1 and of feats2, drawn in the package's
+    order -- per subset `choice(n2, m, replace=False)` first, then `choice(n1, m, replace=False)`.  `seed=None`: numpy's global legacy
+    stream (the package's); an int: a private `np.random.RandomState(seed)`; a `RandomState` is used as given."""
+    m = min(int(n1), int(n2), int(max_subset_size))
+    if m < 2:
+        raise ValueError(f"KID needs two images a side: subsets of min(n1 = {n1}, n2 = {n2}, max_subset_size = {max_subset_size}) = {m} "
+                         "(the estimate divides by m - 1)")
+    if num_subsets < 1:
+        raise ValueError(f"KID: num_subsets {num_subsets}")
+    rng = np.random if seed is None else seed if isinstance(seed, np.random.RandomState) else np.random.RandomState(seed)
+    idx1 = np.empty((num_subsets, m), dtype=np.int32)
+    idx2 = np.empty((num_subsets, m), dtype=np.int32)
+    for s in range(num_subsets):
+        idx2[s] = rng.choice(n2, m, replace=False)
+        idx1[s] = rng.choice(n1, m, replace=False)
+    return torch.from_numpy(idx1), torch.from_numpy(idx2)
+
+
+@torch.no_grad()
+def kernel_distance(feats1: torch.Tensor, feats2: torch.Tensor, num_subsets: int = 100, max_subset_size: int = 1000, seed=None, *,
+                    subsets=None, out: Optional[torch.Tensor] = None, info: Optional[torch.Tensor] = None,
+                    per_subset: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`cleanfid.fid.kernel_distance(feats1, feats2, num_subsets, max_subset_size)` of device fp64 features `[n1, d]`, `[n2, d]`: the 0-d
+    fp32 score on the device.  `subsets=(idx1, idx2)` (integer `[S, m]`, rows of feats1 / feats2) replaces the draw of `kid_subsets`;
+    the lists are range-checked here, on the host, before they are uploaded.  `info` (fp64 `[ops.KID_INFO]`) receives the record of
+    `ops.kid_compute`, `per_subset` (fp64 `[S]`) each subset's value."""
+    if not (feats1.is_cuda and feats2.is_cuda):
+        raise RuntimeError("mv_ldm_amd.cleanfid.kernel_distance runs only on a HIP device (no CPU fallback): move the features to 'cuda'")
+    if feats1.dim() != 2 or feats2.dim() != 2 or feats1.shape[1] != feats2.shape[1]:
+        raise ValueError(f"kernel_distance: features {tuple(feats1.shape)} and {tuple(feats2.shape)}; two [n, d] matrices of one width are compared")
+    if feats1.dtype != torch.float64 or feats2.dtype != torch.float64:
+        raise TypeError(f"kernel_distance: features are {feats1.dtype}, {feats2.dtype}; the fp64 features of InceptionPool3.features are scored")
+    n1, n2 = int(feats1.shape[0]), int(feats2.shape[0])
+    if subsets is None:
+        idx1, idx2 = kid_subsets(n1, n2, num_subsets, max_subset_size, seed)
+    else:
+        idx1, idx2 = (t.cpu() if isinstance(t, torch.Tensor) else torch.tensor(np.asarray(t)) for t in subsets)
+        if idx1.dim() != 2 or idx1.shape != idx2.shape or idx1.shape[0] < 1 or idx1.dtype.is_floating_point or idx2.dtype.is_floating_point:
+            raise ValueError(f"kernel_distance: subsets of shapes {tuple(idx1.shape)}, {tuple(idx2.shape)}; two integer [S, m] lists are taken")
+        if idx1.shape[1] < 2:
+            raise ValueError(f"KID needs two images a side: subsets of {idx1.shape[1]}")
+        if idx1.shape[1] > min(n1, n2):
+            raise ValueError(f"kernel_distance: subsets of {idx1.shape[1]} rows out of {n1} and {n2} features")
+        for name, t, n in (("idx1", idx1, n1), ("idx2", idx2, n2)):
+            if int(t.min()) < 0 or int(t.max()) >= n:
+                raise IndexError(f"kernel_distance: {name} holds a row outside [0, {n})")
+        idx1, idx2 = idx1.to(torch.int32).contiguous(), idx2.to(torch.int32).contiguous()
+    dev = feats1.device
+    out = torch.empty((), dtype=torch.float32, device=dev) if out is None else out
+    info = torch.empty(ops.KID_INFO, dtype=torch.float64, device=dev) if info is None else info
+    ops.kid_compute(feats1.contiguous(), feats2.contiguous(), idx1.to(dev), idx2.to(dev), out, info, per_subset, ws)
+    return out.view(())
 
 
 # ---- folders ------------------------------------------------------------------------------------------------------------------------
@@ -445,8 +536,12 @@ def iter_batches(folder, batch: int = 32):
             yield torch.stack(imgs[i:i + batch]).contiguous()
 
 
-def score_folders(dir1, dir2, metric: CleanFID, batch: int = 32, dtype: Optional[torch.dtype] = None) -> dict:
-    """{"fidclean", "n1", "n2", "solve": {...}} of two folders, which need not pair up: a distance of two distributions"""
+def score_folders(dir1, dir2, metric: CleanFID, batch: int = 32, dtype: Optional[torch.dtype] = None, kid: Optional[dict] = None) -> dict:
+    """{"fidclean", "n1", "n2", "solve": {...}} of two folders, which need not pair up: a distance of two distributions.
+    `kid=dict(num_subsets=, max_subset_size=, seed=)` (a `CleanFID(keep_features=True)`) adds "kidclean" and "kid": {"m", "subsets",
+    "seed", "fp64", "scale"}."""
+    if kid is not None and not metric.keep_features:
+        raise RuntimeError("score_folders(kid=...): KID needs the features themselves; construct the CleanFID with keep_features=True")
     dev = metric.real_state.device
     metric.reset()
     counts = []
@@ -460,10 +555,18 @@ def score_folders(dir1, dir2, metric: CleanFID, batch: int = 32, dtype: Optional
         counts.append(n)
     score = float(metric.compute())
     info = metric.info.tolist()
+    rec = {"fidclean": score, "n1": counts[0], "n2": counts[1],
+           "solve": {"sweeps": [int(info[0]), int(info[2])], "residual": [info[1], info[3]], "capped": int(info[4]), "fid_fp64": info[5],
+                     "sum_sqrt": info[6], "scale": info[7]}}
+    if kid is not None:
+        kinfo = torch.empty(ops.KID_INFO, dtype=torch.float64, device=dev)
+        num_subsets, seed = int(kid.get("num_subsets", 100)), kid.get("seed")
+        rec["kidclean"] = float(metric.compute_kid(num_subsets, int(kid.get("max_subset_size", 1000)), seed, info=kinfo))
+        kinfo = kinfo.tolist()
+        rec["kid"] = {"m": int(kinfo[2]), "subsets": num_subsets, "seed": seed if seed is None or isinstance(seed, int) else None,
+                      "fp64": kinfo[0], "scale": kinfo[1]}
     metric.reset()
-    return {"fidclean": score, "n1": counts[0], "n2": counts[1],
-            "solve": {"sweeps": [int(info[0]), int(info[2])], "residual": [info[1], info[3]], "capped": int(info[4]), "fid_fp64": info[5],
-                      "sum_sqrt": info[6], "scale": info[7]}}
+    return rec
 
 
 def _not_empty(*folders) -> None:
@@ -480,23 +583,41 @@ def compute_fid(dir1, dir2, weights, device="cuda", batch: int = 32, dtype: torc
     return score_folders(dir1, dir2, CleanFID(model), batch, dtype)["fidclean"]
 
 
+def compute_kid(dir1, dir2, weights, device="cuda", batch: int = 32, dtype: torch.dtype = torch.float32, num_subsets: int = 100,
+                max_subset_size: int = 1000, seed=None) -> float:
+    """`cleanfid.fid.compute_kid(dir1, dir2)` with the Inception-v3 weights of `weights` (a path, a state dict or an `InceptionPool3`);
+    `seed`: see `kid_subsets`"""
+    _not_empty(dir1, dir2)
+    model = weights if isinstance(weights, InceptionPool3) else InceptionPool3(weights=weights, dtype=dtype).to(device)
+    kid = dict(num_subsets=num_subsets, max_subset_size=max_subset_size, seed=seed)
+    return score_folders(dir1, dir2, CleanFID(model, keep_features=True), batch, dtype, kid=kid)["kidclean"]
+
+
 def main(argv=None) -> int:
     import argparse
-    ap = argparse.ArgumentParser(prog="python -m mv_ldm_amd.cleanfid", description="clean-fid's compute_fid of two PNG folders on the device")
+    ap = argparse.ArgumentParser(prog="python -m mv_ldm_amd.cleanfid", description="clean-fid's compute_fid (and compute_kid) of two PNG folders on the device")
     ap.add_argument("dir1")
     ap.add_argument("dir2")
     ap.add_argument("--weights", required=True, help="pt_inception state dict (torch-fidelity / pytorch-fid key names)")
     ap.add_argument("--json", default=None, help="write the record here too")
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--dtype", default="float32", choices=("float32", "float16", "bfloat16"))
+    ap.add_argument("--kid", action="store_true", help="also score clean-fid's compute_kid (kidclean)")
+    ap.add_argument("--kid-seed", type=int, default=None, help="seed of a private numpy RandomState for the subsets (default: numpy's global stream)")
+    ap.add_argument("--kid-subsets", type=int, default=100)
+    ap.add_argument("--kid-subset-size", type=int, default=1000)
     a = ap.parse_args(argv)
     dtype = getattr(torch, a.dtype)
     _not_empty(a.dir1, a.dir2)
     model = InceptionPool3(weights=a.weights, dtype=dtype).to("cuda")
-    rec = score_folders(a.dir1, a.dir2, CleanFID(model), a.batch, dtype)
+    kid = dict(num_subsets=a.kid_subsets, max_subset_size=a.kid_subset_size, seed=a.kid_seed) if a.kid else None
+    rec = score_folders(a.dir1, a.dir2, CleanFID(model, keep_features=a.kid), a.batch, dtype, kid=kid)
     s = rec["solve"]
-    print(f"fidclean {rec['fidclean']:.6f}  ({rec['n1']} vs {rec['n2']} images; solves: {s['sweeps'][0]} + {s['sweeps'][1]} sweeps, "
-          f"residual {s['residual'][0]:.1e}, {s['residual'][1]:.1e}, capped {s['capped']})")
+    line = (f"fidclean {rec['fidclean']:.6f}  ({rec['n1']} vs {rec['n2']} images; solves: {s['sweeps'][0]} + {s['sweeps'][1]} sweeps, "
+            f"residual {s['residual'][0]:.1e}, {s['residual'][1]:.1e}, capped {s['capped']})")
+    if a.kid:
+        line += f"  kidclean {rec['kidclean']:.6e}  ({rec['kid']['subsets']} subsets of {rec['kid']['m']}, seed {rec['kid']['seed']})"
+    print(line)
     if a.json:
         Path(a.json).write_text(json.dumps(rec, indent=1))
     return 0

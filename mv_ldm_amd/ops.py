@@ -989,3 +989,35 @@ def frechet_compute(state1: torch.Tensor, state2: torch.Tensor, out: torch.Tenso
     L.check(L.load().mvldm_frechet_compute(state1.data_ptr(), state2.data_ptr(), d, ws.data_ptr(), ws.numel() * ws.element_size(), out.data_ptr(),
                                            info.data_ptr(), stream()))
     return out
+
+
+# ------------------------------------------------------------------------------------------ Clean-KID (csrc/kid.hip)
+KID_INFO = 4                                   # doubles of `kid_compute`'s record
+
+
+def kid_workspace_bytes(m: int, num_subsets: int) -> int:
+    """bytes `kid_compute` needs for `num_subsets` subsets of `m` rows a side: one double per Gram tile, two per subset; 0 for a refused
+    size"""
+    return int(L.load().mvldm_kid_workspace_bytes(m, num_subsets))
+
+
+def kid_compute(f1: torch.Tensor, f2: torch.Tensor, idx1: torch.Tensor, idx2: torch.Tensor, out: torch.Tensor, info: torch.Tensor,
+                per_subset: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out (fp32, one element) = cleanfid's kernel_distance of the fp64 features f1 `[n1, d]`, f2 `[n2, d]` over the subsets idx1 (rows of
+    f1), idx2 (rows of f2), int32 `[S, m]` on the same device; per_subset (fp64 `[S]`, optional): each subset's value; info (fp64
+    `[KID_INFO]`): the score in fp64, the mean of the subsets' scales / m, m, the subsets with an index out of range (then `out` is NaN)"""
+    for t in (f1, f2):
+        assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and t.dim() == 2
+    (n1, d), n2 = f1.shape, f2.shape[0]
+    assert f2.shape[1] == d and f2.device == f1.device
+    for t in (idx1, idx2):
+        assert t.dtype == torch.int32 and t.is_contiguous() and t.dim() == 2 and t.device == f1.device
+    s, m = idx1.shape
+    assert tuple(idx2.shape) == (s, m)
+    assert out.dtype == torch.float32 and out.numel() == 1 and info.dtype == torch.float64 and info.is_contiguous() and info.numel() == KID_INFO
+    assert per_subset is None or (per_subset.dtype == torch.float64 and per_subset.is_contiguous() and per_subset.numel() == s)
+    if ws is None:
+        ws = workspace(kid_workspace_bytes(m, s), f1.device, "kid")
+    L.check(L.load().mvldm_kid_compute(f1.data_ptr(), n1, f2.data_ptr(), n2, d, idx1.data_ptr(), idx2.data_ptr(), s, m, ws.data_ptr(),
+                                       ws.numel() * ws.element_size(), out.data_ptr(), ptr(per_subset), info.data_ptr(), stream()))
+    return out
