@@ -40,7 +40,9 @@ extern "C" {
  *    _compute, mvldm_frechet_workspace_bytes (Clean-FID: the whole Inception-v3 and a Frechet distance up to 2048 features): new symbols
  *    only, the number stays 7.
  *    + mvldm_kid_compute, mvldm_kid_workspace_bytes (Clean-KID: the subset Gram sums on the fp64 matrix cores): new symbols only, the number
- *    stays 7. */
+ *    stays 7.
+ *    + mvldm_crop_shim, mvldm_crop_shim_workspace_bytes, mvldm_crop_shim_axis (the dataset readers' crop shim): new symbols only, the
+ *    number stays 7. */
 #define MVLDM_ABI_VERSION 7
 
 typedef void* mvldm_stream_t; /* hipStream_t */
@@ -698,6 +700,39 @@ size_t mvldm_kid_workspace_bytes(int m, int num_subsets);
 int mvldm_kid_compute(const double* f1, int n1, const double* f2, int n2, int d, const int32_t* idx1, const int32_t* idx2, int num_subsets,
                       int m, double* workspace, size_t workspace_bytes, float* score, double* per_subset /* [num_subsets], may be NULL */,
                       double* info /* [4] */, mvldm_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Crop shim: `rescale_and_crop(images, intrinsics, shape)` (src/dataset/shims/crop_shim.py:11-75) for the images -- what every dataset
+ * reader of the reference applies before a batch leaves it.  Per image: quantise to bytes, Image.resize((w_s, h_s), Image.LANCZOS) on the
+ * 8-bit RGB image, centre crop to h_out x w_out, / 255.
+ *   geometry  scale = max(h_out / h, w_out / w) in double; h_s = round(h scale), w_s = round(w scale), half to even as Python's round;
+ *             one of them must meet its target (else MVLDM_ERR_ARG, the reference's assert); row = (h_s - h_out) / 2,
+ *             col = (w_s - w_out) / 2, floored.  scaled_hw (host int[2], may be NULL) receives h_s, w_s: the caller scales fx by
+ *             w_s / w_out and fy by h_s / h_out.
+ *   src       src_u8 = 1: uint8 [n_img][h][w][3], a decoded image as PIL hands it over; src_u8 = 0: fp32 [n_img][3][h][w] in [0, 1],
+ *             quantised as the reference does -- x 255 in fp32, clamp to [0, 255], truncate (not round: 0.999999 is 254, there as
+ *             here).
+ *   resize    PIL's 8-bit resample, bit for bit: per axis scale = in / out, filterscale = max(scale, 1), support = 3 filterscale;
+ *             output i: center = (i + 0.5) scale, xmin = max(0, int(center - support + 0.5)), xmax = min(in, int(center + support +
+ *             0.5)), w_j = lanczos3((j + xmin - center + 0.5) / filterscale) divided by their sum in tap order, all in double on the
+ *             host; k_j = int(w_j 2^22 +- 0.5), the sign of the 0.5 that of w_j; pixel = clip((2^21 + sum_j px_j k_j) >> 22, 0, 255)
+ *             in int32 (arithmetic shift).  Horizontally first, with a uint8 image between the passes; a pass whose size stays is
+ *             the identity.  Only the columns [col, col + w_out) and rows [row, row + h_out) are computed, and the horizontal pass
+ *             only runs over the source rows their taps read.
+ *   dst       fp32 [n_img][3][h_out][w_out] = byte / 255 (one correctly rounded fp32 divide).
+ *   workspace the uint8 image between the passes, [n_img][3][rows read][roundup(w_out, 4)]: mvldm_crop_shim_workspace_bytes (0 for
+ *             a refused shape); a smaller one is MVLDM_ERR_ARG.
+ * The bounds and coefficients of an axis are kept on the device per (device, in, out, first output, outputs) for the life of the
+ * process.  The FIRST call with a new geometry builds them on the host, allocates and uploads (hipMalloc + hipMemcpy: the one
+ * exception to "never allocates"; inside a stream capture it is refused with MVLDM_ERR_UNSUPPORTED instead); every later call is two
+ * launches, reads nothing back and may be captured.  Pointers: 4-byte aligned.  Sources up to 65536 x 16384 (h x w).
+ * mvldm_crop_shim_axis writes the host-side tables of outputs [offset, offset + count) of an axis n_in -> n_out (bounds [count][2]:
+ * first tap, taps; coefs [count][ksize], either may be NULL) and returns ksize, or a negative MVLDM_ERR_*: what the tests compare
+ * with PIL's own tables without a device. */
+size_t mvldm_crop_shim_workspace_bytes(int n_img, int h, int w, int h_out, int w_out);
+int mvldm_crop_shim(const void* src, int src_u8, float* dst, int n_img, int h, int w, int h_out, int w_out, void* workspace,
+                    size_t workspace_bytes, int* scaled_hw /* host [2], may be NULL */, mvldm_stream_t stream);
+int mvldm_crop_shim_axis(int n_in, int n_out, int offset, int count, int32_t* bounds /* host */, int32_t* coefs /* host */, int coefs_len);
 
 /* ------------------------------------------------------------------------------------------------
  * Plans: a whole forward (UNet walk, VAE decoder, DDIM step) as a flat list of the ops above with

@@ -1021,3 +1021,47 @@ def kid_compute(f1: torch.Tensor, f2: torch.Tensor, idx1: torch.Tensor, idx2: to
     L.check(L.load().mvldm_kid_compute(f1.data_ptr(), n1, f2.data_ptr(), n2, d, idx1.data_ptr(), idx2.data_ptr(), s, m, ws.data_ptr(),
                                        ws.numel() * ws.element_size(), out.data_ptr(), ptr(per_subset), info.data_ptr(), stream()))
     return out
+
+
+# ------------------------------------------------------------------------------------------ crop shim (csrc/cropshim.hip)
+def crop_geometry(h: int, w: int, shape) -> tuple:
+    """(h_scaled, w_scaled, row, col) of `rescale_and_crop` (src/dataset/shims/crop_shim.py:51-75) and its `center_crop`: the one scale
+    that makes both edges reach `shape`, Python's round, the floored centre offsets"""
+    h_out, w_out = (int(v) for v in shape)
+    assert h_out <= h and w_out <= w, f"crop shim only shrinks: {h} x {w} -> {h_out} x {w_out}"
+    scale_factor = max(h_out / h, w_out / w)
+    h_scaled, w_scaled = round(h * scale_factor), round(w * scale_factor)
+    assert h_scaled == h_out or w_scaled == w_out
+    return h_scaled, w_scaled, (h_scaled - h_out) // 2, (w_scaled - w_out) // 2
+
+
+def _crop_src(images: torch.Tensor):
+    assert images.is_cuda and images.is_contiguous() and images.dim() == 4, "crop_shim: a contiguous 4-d device tensor"
+    if images.dtype == torch.uint8:
+        assert images.shape[3] == 3, "crop_shim: uint8 images are [n, h, w, 3]"
+        return images.shape[0], images.shape[1], images.shape[2]
+    assert images.dtype == torch.float32 and images.shape[1] == 3, "crop_shim: float images are fp32 [n, 3, h, w]"
+    return images.shape[0], images.shape[2], images.shape[3]
+
+
+def crop_shim_workspace_bytes(n_img: int, h: int, w: int, shape) -> int:
+    """bytes `crop_shim` needs for n_img images of h x w cropped to `shape`: the uint8 image between the two passes; 0 for a refused shape"""
+    return int(L.load().mvldm_crop_shim_workspace_bytes(n_img, h, w, int(shape[0]), int(shape[1])))
+
+
+def crop_shim(images: torch.Tensor, shape, ws: Optional[torch.Tensor] = None):
+    """uint8 `[n, h, w, 3]` (decoded images) or fp32 `[n, 3, h, w]` in [0, 1] -> (fp32 `[n, 3, h_out, w_out]`, (h_scaled, w_scaled)): the
+    reference's crop shim for the images -- quantise (float input: x 255, clamp, truncate), PIL's 8-bit LANCZOS resize to h_scaled x
+    w_scaled bit for bit, centre crop, / 255 -- of which only the cropped window is computed.  The first call with a new geometry uploads
+    its tables; later ones are two launches and can be captured."""
+    n, h, w = _crop_src(images)
+    h_out, w_out = (int(v) for v in shape)
+    h_scaled, w_scaled, _, _ = crop_geometry(h, w, (h_out, w_out))
+    dst = torch.empty(n, 3, h_out, w_out, dtype=torch.float32, device=images.device)
+    if ws is None:
+        ws = workspace(crop_shim_workspace_bytes(n, h, w, (h_out, w_out)), images.device, "cropshim")
+    got = (C.c_int * 2)()
+    L.check(L.load().mvldm_crop_shim(images.data_ptr(), int(images.dtype == torch.uint8), dst.data_ptr(), n, h, w, h_out, w_out, ws.data_ptr(),
+                                     ws.numel() * ws.element_size(), got, stream()))
+    assert (got[0], got[1]) == (h_scaled, w_scaled), (tuple(got), h_scaled, w_scaled)
+    return dst, (h_scaled, w_scaled)
