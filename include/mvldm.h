@@ -42,7 +42,9 @@ extern "C" {
  *    + mvldm_kid_compute, mvldm_kid_workspace_bytes (Clean-KID: the subset Gram sums on the fp64 matrix cores): new symbols only, the number
  *    stays 7.
  *    + mvldm_crop_shim, mvldm_crop_shim_workspace_bytes, mvldm_crop_shim_axis (the dataset readers' crop shim): new symbols only, the
- *    number stays 7. */
+ *    number stays 7.
+ *    + mvldm_crop_shim_flip (the crop shim with a per-image mirrored read, for the training loader's augmentation shim): new symbol only,
+ *    the number stays 7. */
 #define MVLDM_ABI_VERSION 7
 
 typedef void* mvldm_stream_t; /* hipStream_t */
@@ -728,10 +730,20 @@ int mvldm_kid_compute(const double* f1, int n1, const double* f2, int n2, int d,
  * launches, reads nothing back and may be captured.  Pointers: 4-byte aligned.  Sources up to 65536 x 16384 (h x w).
  * mvldm_crop_shim_axis writes the host-side tables of outputs [offset, offset + count) of an axis n_in -> n_out (bounds [count][2]:
  * first tap, taps; coefs [count][ksize], either may be NULL) and returns ksize, or a negative MVLDM_ERR_*: what the tests compare
- * with PIL's own tables without a device. */
+ * with PIL's own tables without a device.
+ * mvldm_crop_shim_flip is mvldm_crop_shim of images of which some are mirrored along w first -- `apply_augmentation_shim`
+ * (src/dataset/shims/augmentation_shim.py:16-36), which flips the full-size image BEFORE rescale_and_crop.  flip: one byte per image on
+ * the device (non-zero: mirrored), or NULL for none, which is mvldm_crop_shim.  The flip happens at the source read: a flagged image's
+ * horizontal pass stages the window's source columns [x0, x1) in flipped coordinates, i.e. columns [w - x1, w - x0) reversed; tables,
+ * workspace, the vertical pass and the launch count are the same, so one call serves a batch that mixes both.  Flipping the result
+ * instead would not give the reference's bytes: PIL's tables are not mirror-symmetric (xmin = (int)(center - support + 0.5) truncates,
+ * the centre crop floors an odd margin). */
 size_t mvldm_crop_shim_workspace_bytes(int n_img, int h, int w, int h_out, int w_out);
 int mvldm_crop_shim(const void* src, int src_u8, float* dst, int n_img, int h, int w, int h_out, int w_out, void* workspace,
                     size_t workspace_bytes, int* scaled_hw /* host [2], may be NULL */, mvldm_stream_t stream);
+int mvldm_crop_shim_flip(const void* src, int src_u8, float* dst, int n_img, int h, int w, int h_out, int w_out,
+                         const uint8_t* flip /* device, n_img bytes; NULL: none */, void* workspace, size_t workspace_bytes,
+                         int* scaled_hw /* host [2], may be NULL */, mvldm_stream_t stream);
 int mvldm_crop_shim_axis(int n_in, int n_out, int offset, int count, int32_t* bounds /* host */, int32_t* coefs /* host */, int coefs_len);
 
 /* ------------------------------------------------------------------------------------------------

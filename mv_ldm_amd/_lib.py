@@ -259,6 +259,7 @@ SIGNATURES = {
     "mvldm_kid_compute": (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, sz, vp, vp, vp, vp]),
     "mvldm_crop_shim_workspace_bytes": (sz, [C.c_int] * 5),
     "mvldm_crop_shim": (C.c_int, [vp, C.c_int, vp] + [C.c_int] * 5 + [vp, sz, C.POINTER(C.c_int), vp]),
+    "mvldm_crop_shim_flip": (C.c_int, [vp, C.c_int, vp] + [C.c_int] * 5 + [vp, vp, sz, C.POINTER(C.c_int), vp]),
     "mvldm_crop_shim_axis": (C.c_int, [C.c_int] * 4 + [C.POINTER(i32), C.POINTER(i32), C.c_int]),
     "mvldm_nchw_to_nhwc": (C.c_int, [vp, vp] + [C.c_int] * 6 + [f32, f32, vp, vp]),
     "mvldm_ray_channels": (C.c_int, [C.c_int, C.c_int, C.c_int]),

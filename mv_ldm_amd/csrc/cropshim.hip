@@ -10,7 +10,10 @@
 //   crop_h_kernel   one workgroup per (image, source row the vertical pass reads): the row's bytes under the crop window's taps go to
 //                   LDS by channel (a uint8 NHWC row in whole dwords, a float NCHW row quantised as the reference does: x 255 in fp32,
 //                   clamp, truncate), then every thread makes 4 adjacent bytes of one channel and stores them as one dword of the
-//                   workspace [n][3][rows][roundup(w_out, 4)]
+//                   workspace [n][3][rows][roundup(w_out, 4)].  An image flagged in `flip` (mvldm_crop_shim_flip: the augmentation shim's
+//                   image.flip(-1) before the resize) is staged mirrored -- the same bytes, reversed slots -- and nothing else changes:
+//                   PIL's tables are not mirror-symmetric (xmin truncates, an odd crop margin is floored), so the flip cannot follow
+//                   the resize
 //   crop_v_kernel   one workgroup per (image, output row): a thread reads one dword of every tap row, keeps 4 int32 sums and writes
 //                   4 floats byte / 255 (one 16-byte store where the row length and the pointer allow)
 #include <math.h>
@@ -151,16 +154,21 @@ __device__ __forceinline__ uint32_t cs_pixel(int acc) {
 }
 
 // Workgroup b: image b / rows, source row y0 + b % rows.  x0, x1: the source columns the window's taps read; LDS [3][x1 - x0] bytes.
+// flip (may be null): one byte per image; an image whose byte is set is read mirrored along w -- the window [x0, x1) is taken in flipped
+// coordinates, i.e. source columns [w - x1, w - x0) are staged and column p lands in slot w - 1 - p - x0, so LDS holds the row of
+// image.flip(-1) and everything after the staging is the same.
 template <bool U8>
 __global__ __launch_bounds__(256) void crop_h_kernel(const void* __restrict__ src, size_t src_bytes, uint8_t* __restrict__ tmp, int h, int w, int rows,
                                                      int y0, int x0, int x1, int w_out, int wp, int ksize, const int32_t* __restrict__ bounds,
-                                                     const int32_t* __restrict__ coefs) {
+                                                     const int32_t* __restrict__ coefs, const uint8_t* __restrict__ flip) {
     extern __shared__ uint8_t cs_row[];
     const int wl = x1 - x0;
     const size_t img = blockIdx.x / (unsigned)rows;
     const int yy = (int)(blockIdx.x % (unsigned)rows), y = y0 + yy;
+    const bool mirror = flip != nullptr && flip[img] != 0;
+    const int s0 = mirror ? w - x1 : x0;    // the first source column staged
     if (U8) {                               // bytes [lo, hi) of the interleaved image, fetched as the dwords that cover them
-        const size_t base = (img * h + y) * (size_t)w * 3, lo = base + (size_t)x0 * 3, hi = base + (size_t)x1 * 3;
+        const size_t base = (img * h + y) * (size_t)w * 3, lo = base + (size_t)s0 * 3, hi = lo + (size_t)wl * 3;
         const uint8_t* p = (const uint8_t*)src;
         for (size_t d = lo / 4 + threadIdx.x; d * 4 < hi; d += 256) {
             uint32_t v;
@@ -175,7 +183,8 @@ __global__ __launch_bounds__(256) void crop_h_kernel(const void* __restrict__ sr
                 const size_t o = d * 4 + j;
                 if (o >= lo && o < hi) {
                     const unsigned q = (unsigned)(o - base);
-                    cs_row[(q % 3) * wl + (q / 3 - x0)] = (uint8_t)(v >> (8 * j));
+                    const int x = (int)(q / 3) - s0;
+                    cs_row[(q % 3) * wl + (mirror ? wl - 1 - x : x)] = (uint8_t)(v >> (8 * j));
                 }
             }
         }
@@ -183,9 +192,9 @@ __global__ __launch_bounds__(256) void crop_h_kernel(const void* __restrict__ sr
         const float* p = (const float*)src;
         for (int e = threadIdx.x; e < 3 * wl; e += 256) {
             const int ch = e / wl, x = e % wl;
-            float v = p[((img * 3 + ch) * h + y) * (size_t)w + x0 + x] * 255.f;     // (image * 255).clip(0, 255).type(torch.uint8)
+            float v = p[((img * 3 + ch) * h + y) * (size_t)w + s0 + x] * 255.f;     // (image * 255).clip(0, 255).type(torch.uint8)
             v = fminf(fmaxf(v, 0.f), 255.f);
-            cs_row[e] = (uint8_t)(int)v;
+            cs_row[ch * wl + (mirror ? wl - 1 - x : x)] = (uint8_t)(int)v;
         }
     }
     __syncthreads();
@@ -269,8 +278,8 @@ size_t crop_shim_workspace_bytes(int n_img, int h, int w, int h_out, int w_out) 
     return (size_t)n_img * 3 * (size_t)(y1 - y0) * (size_t)((w_out + 3) / 4 * 4);
 }
 
-int crop_shim_run(const void* src, int src_u8, float* dst, int n_img, int h, int w, int h_out, int w_out, void* ws, size_t ws_bytes, int* scaled_hw,
-                  hipStream_t s) {
+int crop_shim_run(const void* src, int src_u8, float* dst, int n_img, int h, int w, int h_out, int w_out, const uint8_t* flip, void* ws,
+                  size_t ws_bytes, int* scaled_hw, hipStream_t s) {
     MVLDM_REQUIRE(src_u8 == 0 || src_u8 == 1, "crop_shim: src_u8 %d", src_u8);
     MVLDM_REQUIRE(n_img >= 0, "crop_shim: n_img %d", n_img);
     MVLDM_REQUIRE(h >= 1 && w >= 1 && h_out >= 1 && w_out >= 1, "crop_shim: image %d x %d -> %d x %d: an edge below 1", h, w, h_out, w_out);
@@ -301,10 +310,10 @@ int crop_shim_run(const void* src, int src_u8, float* dst, int n_img, int h, int
     uint8_t* tmp = (uint8_t*)ws;
     if (src_u8)
         hipLaunchKernelGGL(crop_h_kernel<true>, dim3((unsigned)b1), dim3(256), lds, s, src, src_bytes, tmp, h, w, rows, ty.lo, tx.lo, tx.hi, w_out, wp,
-                           tx.ksize, tx.bounds, tx.coefs);
+                           tx.ksize, tx.bounds, tx.coefs, flip);
     else
         hipLaunchKernelGGL(crop_h_kernel<false>, dim3((unsigned)b1), dim3(256), lds, s, src, src_bytes, tmp, h, w, rows, ty.lo, tx.lo, tx.hi, w_out, wp,
-                           tx.ksize, tx.bounds, tx.coefs);
+                           tx.ksize, tx.bounds, tx.coefs, flip);
     if (w_out % 4 == 0 && ((uintptr_t)dst & 15) == 0)
         hipLaunchKernelGGL(crop_v_kernel<true>, dim3((unsigned)b2), dim3(256), 0, s, (const uint8_t*)tmp, dst, rows, ty.lo, h_out, w_out, wp, ty.ksize,
                            ty.bounds, ty.coefs);
@@ -335,7 +344,11 @@ extern "C" size_t mvldm_crop_shim_workspace_bytes(int n_img, int h, int w, int h
 }
 extern "C" int mvldm_crop_shim(const void* src, int src_u8, float* dst, int n_img, int h, int w, int h_out, int w_out, void* workspace, size_t workspace_bytes,
                                int* scaled_hw, mvldm_stream_t stream) {
-    return crop_shim_run(src, src_u8, dst, n_img, h, w, h_out, w_out, workspace, workspace_bytes, scaled_hw, (hipStream_t)stream);
+    return crop_shim_run(src, src_u8, dst, n_img, h, w, h_out, w_out, nullptr, workspace, workspace_bytes, scaled_hw, (hipStream_t)stream);
+}
+extern "C" int mvldm_crop_shim_flip(const void* src, int src_u8, float* dst, int n_img, int h, int w, int h_out, int w_out, const uint8_t* flip, void* workspace,
+                                    size_t workspace_bytes, int* scaled_hw, mvldm_stream_t stream) {
+    return crop_shim_run(src, src_u8, dst, n_img, h, w, h_out, w_out, flip, workspace, workspace_bytes, scaled_hw, (hipStream_t)stream);
 }
 extern "C" int mvldm_crop_shim_axis(int n_in, int n_out, int offset, int count, int32_t* bounds, int32_t* coefs, int coefs_len) {
     return crop_shim_axis(n_in, n_out, offset, count, bounds, coefs, coefs_len);

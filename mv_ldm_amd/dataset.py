@@ -9,13 +9,26 @@ resize, crop and division run on the device (`ops.crop_shim`, csrc/cropshim.hip)
 through `image_io`) stays on the host.  Cameras follow the reference's host arithmetic.  `rescale_and_crop`, `apply_crop_shim_to_views`
 and `apply_crop_shim` are drop-ins for a loader that already produces the reference's `BatchedExample` dicts.
 
-Out of scope: the `bounded` / `arbitrary` training view samplers and the step tracker, the augmentation and random-transform shims, the
-re10kv2 / CO3D / Objaverse readers, JPEG decoding on the device, Lightning's DataModule."""
+Training reads the same chunks through `RE10KTrainLoader`, `DatasetRE10k.__iter__` for `stage = "train" | "val"`: shuffled chunks and
+scenes, the `bounded` / `arbitrary` view samplers (`ViewSamplerBounded`, `ViewSamplerArbitrary`, `get_view_sampler`) under a
+`StepTracker`, the augmentation shim's mirror, all with the reference's draws from torch's global stream in the reference's order:
+
+    loader = RE10KTrainLoader("re10k", view_sampler=get_view_sampler("bounded", num_context_views=2, num_target_views=3,
+                              min_distance_between_context_views=50, max_distance_between_context_views=180, step_tracker=tracker), augment=True)
+    for batch in loader: ...            # [b, v, ...]: images fp32 on the device, cameras on the host -- what MVLDMTrainer takes
+
+The mirror is not a flip of tensors: the flag of each example travels to the crop shim, which reads the flagged images' source rows
+reversed (`ops.crop_shim(flip=)`), so a whole micro-batch of mirrored and unmirrored examples is one upload and one launch pair.
+`apply_augmentation_and_crop_shim` is the drop-in for the reference's `apply_augmentation_shim` followed by `apply_crop_shim`.
+
+Out of scope: the `all` / `random` view samplers, the random-transform shim (`random_transform_extrinsics`, off in the released config: it
+needs an SO(3) sampler), the re10kv2 / CO3D / Objaverse readers, JPEG decoding on the device, Lightning's DataModule."""
 from __future__ import annotations
 
 import json
+import threading
 from pathlib import Path
-from typing import Dict, Iterator, List, Optional, Sequence, Tuple, Union
+from typing import Dict, Iterator, List, NamedTuple, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -191,3 +204,396 @@ class RE10KScenes:
                             break
                     else:
                         yield sample
+
+
+# ------------------------------------------------------------------------------------------ training: step tracker, view samplers
+class StepTracker:
+    """step_tracker.py: the trainer's global step as the view samplers' warm-up schedules read it.  A lock-guarded int: one process per
+    GPU and decode threads only, so no `Manager` process and no shared-memory tensor."""
+
+    def __init__(self, offset: int = 0):
+        self.offset = int(offset)
+        self._lock = threading.Lock()
+        self._step = self.offset
+
+    def set_step(self, step: int) -> None:
+        with self._lock:
+            self._step = int(step) + self.offset
+
+    def get_step(self) -> int:
+        with self._lock:
+            return self._step
+
+
+class ViewIndex(NamedTuple):
+    context: torch.Tensor                   # int64 [context views]
+    target: Optional[torch.Tensor] = None   # int64 [target views]
+
+
+class ViewSampler:
+    """view_sampler.py: `sample(scene, num_views)` -> a list of `(context, target)` index tensors, one per example the scene gives"""
+
+    def __init__(self, stage: str = "train", is_overfitting: bool = False, cameras_are_circular: bool = False,
+                 step_tracker: Optional[StepTracker] = None):
+        self.stage, self.is_overfitting, self.cameras_are_circular = stage, bool(is_overfitting), bool(cameras_are_circular)
+        self.step_tracker = step_tracker
+
+    @property
+    def global_step(self) -> int:
+        return 0 if self.step_tracker is None else self.step_tracker.get_step()
+
+    def sample(self, scene: str, num_views: int) -> List[ViewIndex]:
+        raise NotImplementedError
+
+
+class ViewSamplerBounded(ViewSampler):
+    """view_sampler_bounded.py: two context views a drawn gap apart, the targets drawn without replacement from the frames between them
+    (widened by `max_distance_to_context_views`).  Three draws from torch's global stream, in this order: `randint` (the gap), `randint`
+    (the left context view), `multinomial` (the targets; not drawn at `stage == "test"`, which takes the whole window).  The gaps can
+    warm up linearly from their `initial_*` values over `*_warm_up_steps` of the step tracker.  `ValueError`: the scene is too short
+    for the smallest gap (the reader skips it); what `multinomial` raises for a window of fewer frames than targets is not caught."""
+
+    def __init__(self, num_context_views: int = 2, num_target_views: int = 0, min_distance_between_context_views: int = 0,
+                 max_distance_between_context_views: Optional[int] = None, max_distance_to_context_views: int = 0,
+                 context_gap_warm_up_steps: int = 0, target_gap_warm_up_steps: int = 0, initial_min_distance_between_context_views: int = 0,
+                 initial_max_distance_between_context_views: Optional[int] = None, initial_max_distance_to_context_views: int = 0, **common):
+        super().__init__(**common)
+        self.num_context_views, self.num_target_views = int(num_context_views), int(num_target_views)
+        self.min_distance_between_context_views = int(min_distance_between_context_views)
+        self.max_distance_between_context_views = max_distance_between_context_views
+        self.max_distance_to_context_views = int(max_distance_to_context_views)
+        self.context_gap_warm_up_steps, self.target_gap_warm_up_steps = int(context_gap_warm_up_steps), int(target_gap_warm_up_steps)
+        self.initial_min_distance_between_context_views = int(initial_min_distance_between_context_views)
+        self.initial_max_distance_between_context_views = initial_max_distance_between_context_views
+        self.initial_max_distance_to_context_views = int(initial_max_distance_to_context_views)
+
+    def schedule(self, initial: int, final: int, steps: int) -> int:
+        fraction = self.global_step / steps
+        return min(initial + int((final - initial) * fraction), final)
+
+    def sample(self, scene: str, num_views: int) -> List[ViewIndex]:
+        max_between = self.max_distance_between_context_views or num_views
+        initial_max_between = self.initial_max_distance_between_context_views or num_views
+        if self.stage == "test":            # always the full gap
+            max_context_gap = min_context_gap = max_between
+        elif self.context_gap_warm_up_steps > 0:
+            max_context_gap = self.schedule(initial_max_between, max_between, self.context_gap_warm_up_steps)
+            min_context_gap = self.schedule(self.initial_min_distance_between_context_views, self.min_distance_between_context_views,
+                                            self.context_gap_warm_up_steps)
+        else:
+            max_context_gap, min_context_gap = max_between, self.min_distance_between_context_views
+        if not self.cameras_are_circular:
+            max_context_gap = min(num_views - 1, max_context_gap)
+        if self.stage != "test" and self.target_gap_warm_up_steps > 0:
+            max_target_gap = self.schedule(self.initial_max_distance_to_context_views, self.max_distance_to_context_views,
+                                           self.target_gap_warm_up_steps)
+        else:
+            max_target_gap = self.max_distance_to_context_views
+        if max_context_gap < min_context_gap:
+            raise ValueError("Example does not have enough frames!")
+        context_gap = torch.randint(min_context_gap, max_context_gap + 1, size=tuple()).item()
+        left = torch.randint(low=0, high=num_views if self.cameras_are_circular else num_views - context_gap, size=tuple()).item()
+        if self.stage == "test":
+            left = left * 0
+        right = left + context_gap
+        if self.is_overfitting:
+            left, right = 0, max_context_gap
+        target = None
+        if self.num_target_views > 0:
+            target_left, target_right = left - max_target_gap, right + max_target_gap
+            if not self.cameras_are_circular:
+                target_left, target_right = max(0, target_left), min(num_views - 1, target_right)
+            target = torch.arange(target_left, target_right + 1)
+            if self.stage != "test":        # when testing, all of them
+                picks = torch.multinomial(torch.ones_like(target, dtype=torch.float), num_samples=self.num_target_views, replacement=False)
+                target = target[picks.long()]
+        if self.cameras_are_circular:
+            if target is not None:
+                target %= num_views
+            right %= num_views
+        return [ViewIndex(torch.tensor((left, right)), target)]
+
+
+class ViewSamplerArbitrary(ViewSampler):
+    """view_sampler_arbitrary.py: context and target views drawn anywhere in the scene (`randint`, `randint`; the context draw is made
+    even when `context_views` then replaces it, as there), or fixed lists"""
+
+    def __init__(self, num_context_views: int = 2, num_target_views: int = 0, context_views: Optional[Sequence[int]] = None,
+                 target_views: Optional[Sequence[int]] = None, **common):
+        super().__init__(**common)
+        self.num_context_views, self.num_target_views = int(num_context_views), int(num_target_views)
+        self.context_views = None if context_views is None else list(context_views)
+        self.target_views = None if target_views is None else list(target_views)
+
+    def sample(self, scene: str, num_views: int) -> List[ViewIndex]:
+        context = torch.randint(0, num_views, size=(self.num_context_views,))
+        if self.context_views is not None:
+            assert len(self.context_views) == self.num_context_views
+            context = torch.tensor(self.context_views, dtype=torch.int64)
+        target = None
+        if self.num_target_views > 0:
+            if self.target_views is None:
+                target = torch.randint(0, num_views, size=(self.num_target_views,))
+            else:
+                assert len(self.target_views) == self.num_target_views
+                target = torch.tensor(self.target_views, dtype=torch.int64)
+        return [ViewIndex(context, target)]
+
+
+class ViewSamplerEvaluation(ViewSampler):
+    """view_sampler_evaluation.py: every entry the evaluation index holds for the scene, nothing drawn.  `index`: `load_index`'s dict
+    or the JSON's path"""
+    num_context_views = num_target_views = 0
+
+    def __init__(self, index=None, index_path=None, **common):
+        super().__init__(**common)
+        index = index if index is not None else index_path
+        if index is None:
+            raise ValueError("the evaluation view sampler needs an index (load_index(path), or the path)")
+        self.index = load_index(index) if isinstance(index, (str, Path)) else {k: v for k, v in index.items() if v}
+        self.total_samples = sum(len(v) for v in self.index.values())
+
+    def sample(self, scene: str, num_views: int) -> List[ViewIndex]:
+        entries = self.index.get(scene)
+        if not entries:
+            raise ValueError(f"No indices available for scene {scene}.")
+        return [ViewIndex(torch.tensor(e["context"], dtype=torch.int64), torch.tensor(e["target"], dtype=torch.int64)) for e in entries]
+
+
+VIEW_SAMPLERS = {"bounded": ViewSamplerBounded, "arbitrary": ViewSamplerArbitrary, "evaluation": ViewSamplerEvaluation}
+
+
+def get_view_sampler(name: str, stage: str = "train", overfit: bool = False, cameras_are_circular: bool = False,
+                     step_tracker: Optional[StepTracker] = None, **cfg) -> ViewSampler:
+    """view_sampler/__init__.py: the sampler of the reference's `dataset.view_sampler.name`, its cfg fields as keyword arguments"""
+    if name in ("all", "random"):
+        raise NotImplementedError(f"the `{name}` view sampler is not built (bounded, arbitrary and evaluation are)")
+    if name not in VIEW_SAMPLERS:
+        raise KeyError(f"unknown view sampler `{name}`")
+    return VIEW_SAMPLERS[name](stage=stage, is_overfitting=overfit, cameras_are_circular=cameras_are_circular, step_tracker=step_tracker, **cfg)
+
+
+# ------------------------------------------------------------------------------------------ training: the augmentation shim
+def reflect_extrinsics(extrinsics: torch.Tensor) -> torch.Tensor:
+    """augmentation_shim.py:8-13: the camera-to-world matrices `[*batch, 4, 4]` of the scene mirrored along x, diag(-1, 1, 1, 1) E
+    diag(-1, 1, 1, 1)"""
+    reflect = torch.eye(4, dtype=torch.float32, device=extrinsics.device)
+    reflect[0, 0] = -1
+    return reflect @ extrinsics @ reflect
+
+
+def _crop_views_flagged(views: dict, shape: Tuple[int, int], flip: bool) -> dict:
+    """`apply_crop_shim_to_views` of a view group whose images are mirrored first when `flip`: the flag goes to the device shim, the
+    extrinsics are reflected here"""
+    from . import ops
+    images = views["image"]
+    dev = images.device if images.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    if images.dtype == torch.uint8:
+        *batch, h, w, c = images.shape
+        flat = images.reshape(-1, h, w, c)
+    else:
+        *batch, c, h, w = images.shape
+        flat = images.reshape(-1, c, h, w).float()
+    assert c == 3, f"the crop shim takes RGB images, got {c} channels"
+    flags = torch.full((flat.shape[0],), int(flip), dtype=torch.uint8, device=dev) if flip else None
+    out, scaled = ops.crop_shim(flat.to(dev).contiguous(), shape, flip=flags)
+    extrinsics = reflect_extrinsics(views["extrinsics"]) if flip else views["extrinsics"]
+    return {**views, "image": out.reshape(*batch, 3, *out.shape[-2:]), "extrinsics": extrinsics,
+            "intrinsics": crop_intrinsics(views["intrinsics"], scaled, shape)}
+
+
+def apply_augmentation_and_crop_shim(example: dict, shape: Tuple[int, int], generator: Optional[torch.Generator] = None) -> dict:
+    """`apply_crop_shim(apply_augmentation_shim(example, generator), shape)` (augmentation_shim.py:24-36, crop_shim.py): the reference's
+    coin -- `torch.rand(())`, no mirror when it is below 0.5 -- then, for a mirrored example, the extrinsics of both view groups
+    reflected on the host and the images mirrored by the device shim at its source read (no flipped copy of the images is made).
+    Intrinsics are untouched by the mirror, as there, and rescaled by the crop."""
+    flip = not bool(torch.rand(tuple(), generator=generator) < 0.5)
+    return {**example, **{view: _crop_views_flagged(example[view], shape, flip) for view in ("context", "target")
+                          if view in example and example[view].get("image") is not None}}
+
+
+# ------------------------------------------------------------------------------------------ training: the loader
+def _frame_size(data: bytes) -> Tuple[int, int]:
+    """(h, w) of an encoded frame from its header, without decoding it"""
+    if data[:8] == _PNG:
+        return int.from_bytes(data[20:24], "big"), int.from_bytes(data[16:20], "big")
+    try:
+        from PIL import Image
+    except ImportError as e:
+        raise ImportError("these frames are not PNG (RE10K stores JPEG): reading them needs the Pillow package (`PIL`), which is not installed") from e
+    from io import BytesIO
+    w, h = Image.open(BytesIO(data)).size
+    return h, w
+
+
+def _shuffle(items: list) -> list:
+    return [items[i] for i in torch.randperm(len(items))]
+
+
+class RE10KTrainLoader:
+    """`DatasetRE10k.__iter__` (dataset_re10k.py:79-171) for `stage = "train" | "val"` behind the reference's train `DataLoader`
+    (data_module.py:87-100: batches of `batch_size`, `drop_last`), one pass over the chunks per `iter()`.
+
+    `examples()` is the host-only pass.  Its draws from torch's global stream are the reference's, in its order: `randperm` over the
+    CURRENT chunk order (`self.chunks` stays shuffled between epochs, as there), `randperm` over each chunk, then per scene the field
+    of view skip (nothing drawn), the view sampler's draws (`ValueError`: the scene is skipped), the two-context-view baseline rescale
+    or skip AFTER those draws, and -- `stage == "train"` with `augment` only -- the augmentation coin.  `stage="val"` reads
+    `<root>/test` (and shuffles too); `scenes=[keys]` reads the chunks `<root>/test/index.json` names for them (`overfit_to_scene`).  It
+    yields unbatched records {"scene", "flip", "context" / "target": {"extrinsics" [v, 4, 4] (rescaled, reflected when mirrored),
+    "intrinsics" [v, 3, 3] (the cropped image's: host arithmetic), "near", "far" [v] over the scale, "index" [v], "frames": decoded
+    uint8 [v, h, w, 3], NOT mirrored}}.  Any frame size from `image_shape` up is taken, as in `RE10KScenes`; an example whose frames
+    disagree in size or are smaller is skipped with a message before the coin (the reference's shape check sits there).
+
+    Iterating the loader collates `batch_size` records into one `BatchedExample`-shaped dict: every field `[b, v, ...]`, `scene` a list
+    of b, images fp32 `[b, v, 3, h_out, w_out]` on the device, cameras on the host -- what `MVLDMTrainer.training_step` /
+    `training_window` take.  All b x (v_c + v_t) frames of one frame size go up in ONE pinned upload and through ONE `ops.crop_shim`
+    call with the examples' mirror flags, and are then split into context / target; a batch that mixes frame sizes makes one call per
+    size.  `decode_workers` > 0: the container decode of a batch's frames runs on that many threads (at most 16, results in order;
+    nothing is drawn there, so the order of the draws does not depend on it).  `crop=False` leaves out the device: images are the
+    decoded uint8 frames `[b, v, h, w, 3]` (one frame size per batch) and `flip` `[b]` says which the shim would mirror.
+
+    No rank sharding: like the reference's iterable dataset, every rank walks all chunks, under its own torch seed."""
+
+    MAX_DECODE_WORKERS = 16
+
+    def __init__(self, root, stage: str = "train", view_sampler: Optional[ViewSampler] = None, image_shape: Tuple[int, int] = (256, 256),
+                 batch_size: int = 6, drop_last: bool = True, augment: bool = False, make_baseline_1: bool = True, baseline_epsilon: float = 1e-3,
+                 max_fov: float = 100.0, scenes: Optional[Sequence[str]] = None, decode_workers: int = 0, crop: bool = True,
+                 random_transform_extrinsics: bool = False):
+        if stage not in ("train", "val"):
+            raise ValueError(f"RE10KTrainLoader reads stage train or val, got {stage!r} (RE10KScenes reads test)")
+        if random_transform_extrinsics:
+            raise NotImplementedError("dataset.random_transform_extrinsics (off in the released config) needs an SO(3) sampler that is not built")
+        if view_sampler is None:            # config/experiment/baseline.yaml:16-20
+            view_sampler = ViewSamplerBounded(num_context_views=2, num_target_views=3, min_distance_between_context_views=50,
+                                              max_distance_between_context_views=180, stage=stage)
+        self.stage, self.view_sampler = stage, view_sampler
+        self.scenes = None if scenes is None else list(scenes)
+        self.root = Path(root) / ("test" if stage == "val" or self.scenes is not None else stage)     # `data_stage`
+        self.image_shape = (int(image_shape[0]), int(image_shape[1]))
+        self.batch_size, self.drop_last, self.augment = int(batch_size), bool(drop_last), bool(augment)
+        self.make_baseline_1, self.baseline_epsilon, self.max_fov = bool(make_baseline_1), float(baseline_epsilon), float(max_fov)
+        self.decode_workers = max(0, min(int(decode_workers), self.MAX_DECODE_WORKERS))
+        self.crop = bool(crop)
+        self._pool = None
+        if self.scenes is None:
+            self.chunks = sorted(p for p in self.root.iterdir() if p.suffix == ".torch")
+        else:
+            with open(self.root / "index.json") as f:
+                where = json.load(f)
+            self.chunks = [self.root / where[name] for name in self.scenes]
+
+    # ---- the host-only pass
+    def _records(self, decode: bool) -> Iterator[dict]:
+        from .ops import crop_geometry
+        self.chunks = _shuffle(self.chunks)
+        for chunk_path in self.chunks:
+            chunk = torch.load(chunk_path, weights_only=True)
+            if self.scenes is not None:
+                chunk = [x for x in chunk if x["key"] in self.scenes]
+            for example in _shuffle(chunk):
+                extrinsics, intrinsics = convert_poses(example["cameras"])
+                scene = example["key"]
+                if (get_fov(intrinsics).rad2deg() > self.max_fov).any():
+                    continue
+                try:
+                    view_indices = self.view_sampler.sample(scene, extrinsics.shape[0])
+                except ValueError:          # not enough frames
+                    continue
+                for view_index in view_indices:
+                    context_extrinsics = extrinsics[view_index.context]
+                    if context_extrinsics.shape[0] == 2 and self.make_baseline_1:
+                        a, b = context_extrinsics[:, :3, 3]
+                        scale = (a - b).norm()
+                        if scale < self.baseline_epsilon:
+                            print(f"Skipped {scene} because of insufficient baseline {scale:.6f}")
+                            continue
+                        extrinsics[:, :3, 3] /= scale
+                    else:
+                        scale = 1
+                    groups = {k: v for k, v in view_index._asdict().items() if v is not None}
+                    data = {k: [_frame_bytes(example["images"][i.item()]) for i in v] for k, v in groups.items()}
+                    sizes = {_frame_size(d) for ds in data.values() for d in ds}
+                    h, w = next(iter(sizes))
+                    if len(sizes) != 1 or h < self.image_shape[0] or w < self.image_shape[1]:
+                        print(f"Skipped bad example {scene}. Frame shapes were {sorted(sizes)}.")
+                        continue
+                    flip = False
+                    if self.stage == "train" and self.augment:
+                        flip = not bool(torch.rand(tuple()) < 0.5)
+                    h_s, w_s, _, _ = crop_geometry(h, w, self.image_shape)
+                    record = {"scene": scene, "flip": flip}
+                    for k, idx in groups.items():
+                        bound = lambda v: torch.full((len(idx),), v, dtype=torch.float32) / scale
+                        ext = extrinsics[idx]
+                        record[k] = {"extrinsics": reflect_extrinsics(ext) if flip else ext,
+                                     "intrinsics": crop_intrinsics(intrinsics[idx], (h_s, w_s), self.image_shape),
+                                     "near": bound(NEAR), "far": bound(FAR), "index": idx, "size": (h, w)}
+                        if decode:
+                            record[k]["frames"] = np.stack([decode_image(d) for d in data[k]])
+                        else:
+                            record[k]["data"] = data[k]
+                    yield record
+
+    def examples(self) -> Iterator[dict]:
+        return self._records(decode=True)
+
+    # ---- batches
+    def _decode(self, blobs: List[bytes]) -> List[np.ndarray]:
+        if self.decode_workers == 0 or len(blobs) < 2:
+            return [decode_image(d) for d in blobs]
+        if self._pool is None:
+            from concurrent.futures import ThreadPoolExecutor
+            self._pool = ThreadPoolExecutor(max_workers=self.decode_workers, thread_name_prefix="re10k-decode")
+        return list(self._pool.map(decode_image, blobs))          # in the order of `blobs`
+
+    def _collate(self, records: List[dict]) -> dict:
+        views = [k for k in ("context", "target") if k in records[0]]
+        counts = [records[0][k]["index"].shape[0] for k in views]
+        assert all([r[k]["index"].shape[0] for k in views] == counts for r in records), "one view count per batch (the sampler's)"
+        v = sum(counts)
+        frames = self._decode([d for r in records for k in views for d in r[k]["data"]])
+        batch = {"scene": [r["scene"] for r in records]}
+        by_size: Dict[Tuple[int, int], List[int]] = {}
+        for i, r in enumerate(records):
+            by_size.setdefault(r[views[0]]["size"], []).append(i)
+        flips = torch.tensor([r["flip"] for r in records], dtype=torch.uint8)
+        images = None
+        if not self.crop:
+            assert len(by_size) == 1, "crop=False batches hold one frame size"
+            images = torch.from_numpy(np.stack(frames)).reshape(len(records), v, *frames[0].shape)
+            batch["flip"] = flips.bool()
+        else:
+            from . import ops
+            dev = torch.device("cuda", torch.cuda.current_device())
+            for (h, w), members in by_size.items():
+                staged = torch.empty(len(members) * v, h, w, 3, dtype=torch.uint8, pin_memory=True)          # one upload per frame size
+                host = staged.numpy()
+                for j, i in enumerate(members):
+                    for t in range(v):
+                        host[j * v + t] = frames[i * v + t]
+                flags = flips[members].repeat_interleave(v).to(dev, non_blocking=True)
+                out, _ = ops.crop_shim(staged.to(dev, non_blocking=True), self.image_shape, flip=flags)
+                out = out.reshape(len(members), v, *out.shape[1:])
+                if len(by_size) == 1:
+                    images = out
+                else:
+                    if images is None:
+                        images = torch.empty(len(records), *out.shape[1:], dtype=out.dtype, device=dev)
+                    images[torch.tensor(members, device=dev)] = out
+        at = 0
+        for k, n in zip(views, counts):
+            batch[k] = {name: torch.stack([r[k][name] for r in records]) for name in ("extrinsics", "intrinsics", "near", "far", "index")}
+            batch[k]["image"] = images[:, at:at + n]
+            at += n
+        return batch
+
+    def __iter__(self) -> Iterator[dict]:
+        pending: List[dict] = []
+        for record in self._records(decode=False):
+            pending.append(record)
+            if len(pending) == self.batch_size:
+                yield self._collate(pending)
+                pending = []
+        if pending and not self.drop_last:
+            yield self._collate(pending)

@@ -1049,19 +1049,23 @@ def crop_shim_workspace_bytes(n_img: int, h: int, w: int, shape) -> int:
     return int(L.load().mvldm_crop_shim_workspace_bytes(n_img, h, w, int(shape[0]), int(shape[1])))
 
 
-def crop_shim(images: torch.Tensor, shape, ws: Optional[torch.Tensor] = None):
+def crop_shim(images: torch.Tensor, shape, ws: Optional[torch.Tensor] = None, flip: Optional[torch.Tensor] = None):
     """uint8 `[n, h, w, 3]` (decoded images) or fp32 `[n, 3, h, w]` in [0, 1] -> (fp32 `[n, 3, h_out, w_out]`, (h_scaled, w_scaled)): the
     reference's crop shim for the images -- quantise (float input: x 255, clamp, truncate), PIL's 8-bit LANCZOS resize to h_scaled x
     w_scaled bit for bit, centre crop, / 255 -- of which only the cropped window is computed.  The first call with a new geometry uploads
-    its tables; later ones are two launches and can be captured."""
+    its tables; later ones are two launches and can be captured.  `flip`: a device uint8 / bool tensor `[n]`; image i with flip[i] set is
+    mirrored along w BEFORE the resize (the augmentation shim's `image.flip(-1)`), at the source read of the same two launches."""
     n, h, w = _crop_src(images)
+    if flip is not None:
+        assert flip.is_cuda and flip.device == images.device and flip.is_contiguous() and flip.dtype in (torch.uint8, torch.bool) \
+            and tuple(flip.shape) == (n,), "crop_shim: flip is a contiguous device uint8 / bool tensor [n]"
     h_out, w_out = (int(v) for v in shape)
     h_scaled, w_scaled, _, _ = crop_geometry(h, w, (h_out, w_out))
     dst = torch.empty(n, 3, h_out, w_out, dtype=torch.float32, device=images.device)
     if ws is None:
         ws = workspace(crop_shim_workspace_bytes(n, h, w, (h_out, w_out)), images.device, "cropshim")
     got = (C.c_int * 2)()
-    L.check(L.load().mvldm_crop_shim(images.data_ptr(), int(images.dtype == torch.uint8), dst.data_ptr(), n, h, w, h_out, w_out, ws.data_ptr(),
-                                     ws.numel() * ws.element_size(), got, stream()))
+    L.check(L.load().mvldm_crop_shim_flip(images.data_ptr(), int(images.dtype == torch.uint8), dst.data_ptr(), n, h, w, h_out, w_out,
+                                          None if flip is None or n == 0 else flip.data_ptr(), ws.data_ptr(), ws.numel() * ws.element_size(), got, stream()))
     assert (got[0], got[1]) == (h_scaled, w_scaled), (tuple(got), h_scaled, w_scaled)
     return dst, (h_scaled, w_scaled)

@@ -2203,3 +2203,156 @@ def sample_indices(ctx: dict, tgt: dict, index: int, random: bool = True, second
     cat = lambda k: torch.cat([tgt[k], ctx[k][:, ~mask]], dim=1)
     return (ctx["image"][:, mask], ctx["extrinsics"][:, mask], ctx["intrinsics"][:, mask],
             cat("image"), cat("extrinsics"), cat("intrinsics"), idx)
+
+
+# ================================================================================================ python -m mv_ldm_amd.train
+# the released values of the keys the training entry point reads beside `generate.DEFAULT_CONFIG`'s (file:line = where the reference
+# defines them)
+TRAIN_CONFIG = {
+    "dataset": {"view_sampler": {"name": "bounded", "num_context_views": 2, "num_target_views": 3,          # config/experiment/baseline.yaml:16-20
+                                 "min_distance_between_context_views": 50, "max_distance_between_context_views": 180},
+                "augment": False, "random_transform_extrinsics": False, "make_baseline_1": True, "baseline_epsilon": 1e-3, "max_fov": 100.0,
+                "cameras_are_circular": False, "overfit_to_scene": None},                                   # config/dataset/re10k.yaml
+    "optimizer": {"lr": 2.0e-5},                                                                           # baseline.yaml:64
+    "trainer": {"accumulate_grad_batches": 2, "gradient_clip_val": 0.1},                                    # config/main.yaml:81,84
+    "train": {"step_offset": 0},                                                                            # config/main.yaml:67
+}
+
+
+def main(argv=None, overrides=None):
+    """`python -m mv_ldm_amd.train --dataset ROOT [--stage train] --steps N [--batch 6] [--res 256] [--seed S] [--resume CKPT] [--save CKPT]
+    [--log-every K] [--decode-workers W] [--allow-random-init] [key.sub=value ...]`: N optimizer steps on the RE10K root's chunks
+    (`dataset.RE10KTrainLoader`: the reference's shuffles, view sampler, augmentation coin; images through the crop shim on the device).
+    Overrides as in `generate`: `dataset.view_sampler.*`, `dataset.augment`, `trainer.precision`, `optimizer.lr`,
+    `trainer.accumulate_grad_batches`, and the `model.*` / `checkpointing.load` keys `generate.build_pipeline` reads.  Every optimizer step
+    is one `training_window` over `accumulate_grad_batches` batches with the next window handed on as `prefetch`; the step tracker the
+    view sampler's warm-up reads follows `trainer.global_step`.  One JSON line (step, loss, lr, views/s) every K steps and one at the end.
+    `overrides` = reduced widths for tests, as in `generate.build_pipeline`."""
+    import argparse
+    import json
+    import time
+
+    from . import set_compute_dtype
+    from .dataset import RE10KTrainLoader, StepTracker, get_view_sampler
+    from .dist import env_rank_world
+    from .generate import DEFAULT_CONFIG, apply_overrides, build_pipeline, merge_config
+    ap = argparse.ArgumentParser(prog="python -m mv_ldm_amd.train", description="train the multi-view denoiser on an RE10K root")
+    ap.add_argument("overrides", nargs="*", help="Hydra-style key.sub=value overrides")
+    ap.add_argument("--config", default=None, help="JSON or YAML file merged over the released values")
+    ap.add_argument("--dataset", required=True, help="RE10K root (ROOT/<stage>/*.torch chunks)")
+    ap.add_argument("--stage", default="train", choices=["train", "val"], help="val reads ROOT/test, shuffled, never augmented")
+    ap.add_argument("--steps", type=int, required=True, help="optimizer steps to run (each accumulate_grad_batches batches)")
+    ap.add_argument("--batch", type=int, default=6, help="scenes per batch (config/main.yaml:47)")
+    ap.add_argument("--res", type=int, default=256, help="the crop shim's image shape, res x res")
+    ap.add_argument("--seed", type=int, default=None, help="torch / numpy seed (+ rank): shuffles, view sampler, augmentation, noise, timesteps")
+    ap.add_argument("--resume", default=None, help="a checkpoint `--save` wrote: weights, optimizer, scaler and step counter continue")
+    ap.add_argument("--save", default=None, help="write the trainer's checkpoint here after the last step")
+    ap.add_argument("--log-every", type=int, default=10, metavar="K")
+    ap.add_argument("--decode-workers", type=int, default=0, help="threads for the container decode of a batch's frames (at most 16)")
+    ap.add_argument("--allow-random-init", action="store_true", help="no pretrained weights: random ones of the right shape")
+    args = ap.parse_args(argv)
+    cfg = merge_config(DEFAULT_CONFIG, TRAIN_CONFIG)
+    if args.config:
+        with open(args.config) as f:
+            if args.config.endswith((".yaml", ".yml")):
+                import yaml
+                cfg = merge_config(cfg, yaml.safe_load(f))
+            else:
+                cfg = merge_config(cfg, json.load(f))
+    apply_overrides(cfg, args.overrides)
+    if not torch.cuda.is_available():
+        raise SystemExit("train needs a GPU (the HIP path has no CPU fallback)")
+    L.load()
+    torch.set_grad_enabled(False)
+    rank, world, local_rank = env_rank_world()
+    torch.cuda.set_device(local_rank)
+    if world > 1:
+        import torch.distributed as dist
+        dist.init_process_group("nccl", device_id=torch.device("cuda", local_rank))      # RCCL
+    if args.seed is not None:           # every rank walks all chunks under its own seed, like the reference's iterable dataset
+        torch.manual_seed(args.seed + rank)
+        np.random.seed(args.seed + rank)
+    dtype, _ = training_precision(cfg["trainer"].get("precision"))
+    set_compute_dtype(dtype)
+    fresh = not args.resume and not cfg["checkpointing"].get("load")
+    pipe, report = build_pipeline(cfg, torch.device("cuda", local_rank), allow_random_init=args.allow_random_init or bool(args.resume), overrides=overrides)
+    if fresh and args.allow_random_init:                     # the same on every rank
+        g = torch.Generator(device=pipe.device).manual_seed(0 if cfg["seed"] is None else int(cfg["seed"]))
+        for m in (pipe.denoiser, pipe.autoencoder):
+            for p in m.parameters():
+                if p.dim() > 1:
+                    p.copy_(torch.randn(p.shape, generator=g, device=p.device) * (1.0 / max(p[0].numel(), 1)) ** 0.5)
+    acc = int(cfg["trainer"]["accumulate_grad_batches"])
+    trainer = MVLDMTrainer(pipe.denoiser, pipe.autoencoder, pipe.scheduler, OptimizerCfg(lr=float(cfg["optimizer"]["lr"])),
+                           TrainCfg(accumulate_grad_batches=acc, gradient_clip_val=float(cfg["trainer"]["gradient_clip_val"])), dtype=dtype,
+                           world=world, rank=rank, rays=pipe.rays, ema_decay=0.995 if cfg["model"].get("ema") else None)
+    if args.resume:
+        trainer.load_checkpoint(args.resume)
+    d = cfg["dataset"]
+    tracker = StepTracker(int(cfg["train"]["step_offset"]))
+    tracker.set_step(trainer.global_step)
+    sampler_cfg = dict(d["view_sampler"])
+    sampler = get_view_sampler(sampler_cfg.pop("name"), stage=args.stage, overfit=d["overfit_to_scene"] is not None,
+                               cameras_are_circular=bool(d["cameras_are_circular"]), step_tracker=tracker, **sampler_cfg)
+    scenes = d["overfit_to_scene"]
+    loader = RE10KTrainLoader(args.dataset, args.stage, view_sampler=sampler, image_shape=(args.res, args.res), batch_size=args.batch, augment=bool(d["augment"]),
+                              make_baseline_1=bool(d["make_baseline_1"]), baseline_epsilon=float(d["baseline_epsilon"]), max_fov=float(d["max_fov"]),
+                              scenes=[scenes] if isinstance(scenes, str) else scenes, decode_workers=args.decode_workers,
+                              random_transform_extrinsics=bool(d["random_transform_extrinsics"]))
+
+    def windows():
+        """`acc` batches at a time, epoch after epoch"""
+        window = []
+        while True:
+            empty = True
+            for batch in loader:
+                empty = False
+                window.append(batch)
+                if len(window) == acc:
+                    yield window
+                    window = []
+            if empty:
+                raise SystemExit(f"{loader.root} gives no full batch of {args.batch} scenes")
+
+    def views_of(window):
+        return world * sum(bt[k]["image"].shape[0] * bt[k]["image"].shape[1] for bt in window for k in ("context", "target"))
+
+    def line(step, losses, views, secs, **more):
+        if rank == 0:
+            print(json.dumps({"step": step, "loss": round(float(torch.stack([l.float().mean() for l in losses]).mean()), 6), "lr": trainer.opt.lr(),
+                              "views_per_s": round(views / max(secs, 1e-9), 3), **more}), flush=True)
+
+    feed = windows()
+    window = next(feed)
+    done = views = total_views = 0
+    losses = []
+    t_start = t_log = time.perf_counter()
+    while done < args.steps:
+        nxt = next(feed) if done + 1 < args.steps else None
+        losses.append(trainer.training_window(window, prefetch=(nxt, None) if nxt is not None else None))
+        views += views_of(window)
+        tracker.set_step(trainer.global_step)
+        done += 1
+        window = nxt
+        if args.log_every > 0 and done % args.log_every == 0 and done < args.steps:
+            torch.cuda.synchronize()
+            now = time.perf_counter()
+            line(trainer.global_step, losses[-args.log_every:], views, now - t_log)
+            total_views, views, t_log = total_views + views, 0, now
+    torch.cuda.synchronize()
+    secs = time.perf_counter() - t_start
+    if args.save:
+        trainer.save_checkpoint(args.save)
+    line(trainer.global_step, losses[-max(args.log_every, 1):] or [torch.zeros(1)], total_views + views, secs, steps=done, seconds=round(secs, 3), n_gpus=world,
+         dtype=str(dtype).split(".")[-1], data=f"{args.dataset} ({args.stage})", weights="checkpoint" if not fresh else "random init"
+         if args.allow_random_init else "pretrained", final=True)
+    if world > 1:
+        import torch.distributed as dist
+        dist.barrier()
+        dist.destroy_process_group()
+    return 0
+
+
+if __name__ == "__main__":
+    from mv_ldm_amd.train import main as _main           # the module under its own name: one set of classes in the process
+    raise SystemExit(_main())
