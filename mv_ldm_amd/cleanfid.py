@@ -29,24 +29,19 @@ the subsets the package would draw), as noise is everywhere else at this boundar
 from __future__ import annotations
 
 import json
-import math
 import sys
-import warnings
 from pathlib import Path
 from typing import Optional
 
 import numpy as np
 import torch
-from torch import nn
 
 from . import ops
-from .fid import BN_EPS, _BN
-from .lpips import _read
+from ._metric_nets import FLOATS, FrechetStats, InceptionStack, check_images, conv, pack_conv      # noqa: F401  (`conv`, `pack_conv`: importable from here)
 
 SIZE = 299                      # the extractor's input edge
 FEATURES = 2048
 MAPS = ("stem", "Mixed_5d", "Mixed_6a", "Mixed_6e", "Mixed_7a", "Mixed_7c")      # what `features(return_maps=...)` can hand back
-_IGNORED = ("AuxLogits.", "fc.")
 
 
 def _layers():
@@ -108,129 +103,16 @@ LAYERS = _layers()
 _LARGEST = 35 * 35 * 25 * 48
 
 
-class _Conv(nn.Module):
-    """parameter holder with nn.Conv2d's names; the kernel may be oblong"""
-
-    def __init__(self, c_out: int, c_in: int, kh: int, kw: int):
-        super().__init__()
-        self.weight = nn.Parameter(torch.empty(c_out, c_in, kh, kw), requires_grad=False)
-
-
-class _BasicConv(nn.Module):
-    def __init__(self, c_in: int, c_out: int, k):
-        super().__init__()
-        self.conv = _Conv(c_out, c_in, *k)
-        self.bn = _BN(c_out)
-
-
-def pack_conv(w: torch.Tensor, dtype: torch.dtype) -> ops.PackedWeight:
-    """fp32 `[n_out, c_in, kh, kw]` on the device -> the packed weight `conv` reads: a 1 x 1 or 3 x 3 kernel as the implicit GEMM takes
-    it, any other as the 1 x 1 weight `[n_out, kh kw c_in]` over the unfolded map (tap-major, then channel)"""
-    kh, kw = w.shape[2:]
-    if kh == kw and kh in (1, 3):
-        return ops.pack_weight(w, dtype)
-    return ops.pack_weight(w.permute(0, 2, 3, 1).reshape(w.shape[0], -1).contiguous(), dtype)
-
-
-def conv(x: torch.Tensor, pw: ops.PackedWeight, bias, k, stride: int = 1, pad=(0, 0)) -> torch.Tensor:
-    """the pre-activation convolution of NHWC `x`: 1 x 1 and 3 x 3 straight through `ops.conv2d`, every other kernel (stride 1, padding
-    that keeps the size) as `ops.inception_unfold` and a 1 x 1 convolution"""
-    kh, kw = k
-    if kh == kw and kh in (1, 3):
-        return ops.conv2d(x, pw, bias, stride=stride, pad=pad[0])
-    assert stride == 1 and tuple(pad) == (kh // 2, kw // 2)
-    return ops.conv2d(ops.inception_unfold(x, kh, kw), pw, bias, pad=0)
-
-
-class InceptionPool3(nn.Module):
+class InceptionPool3(InceptionStack):
     """The FID Inception-v3 up to its 2048-wide pool; fp32 parameters under torch-fidelity's `pt_inception` key names
     (`Mixed_6b.branch7x7_2.conv.weight`, `.bn.{weight,bias,running_mean,running_var}`).  `dtype`: the compute dtype of the activations and
     packed weights (float32 by default: a metric; float16 / bfloat16 are allowed)."""
+    LAYERS = LAYERS
+    IGNORED = ("AuxLogits.", "fc.")
 
     def __init__(self, weights=None, dtype: torch.dtype = torch.float32, allow_random_init: bool = False):
-        super().__init__()
-        if dtype not in (torch.float32, torch.float16, torch.bfloat16):
-            raise TypeError(f"InceptionPool3: compute dtype {dtype}")
-        self.compute_dtype = dtype
-        for name, c_in, c_out, k, _, _ in LAYERS:
-            parent = self
-            *path, leaf = name.split(".")
-            for p in path:
-                if not hasattr(parent, p):
-                    setattr(parent, p, nn.Module())
-                parent = getattr(parent, p)
-            setattr(parent, leaf, _BasicConv(c_in, c_out, k))
-        self._packs: dict = {}
-        self.reset_parameters()
-        if weights is not None:
-            self.load_weights(weights)
-        elif not allow_random_init:
-            warnings.warn("InceptionPool3(): no weight file given -- the module keeps RANDOM initial weights and its scores mean nothing "
-                          "(pass weights=... / call load_weights, or allow_random_init=True to silence)", stacklevel=2)
-
-    def reset_parameters(self, seed: Optional[int] = None):
-        """Kaiming-normal convs, BatchNorm close to the identity"""
-        g = None if seed is None else torch.Generator().manual_seed(seed)
-        with torch.no_grad():
-            for name, *_ in LAYERS:
-                m = self.get_submodule(name)
-                w = m.conv.weight
-                m.conv.weight.copy_(torch.randn(w.shape, generator=g) * math.sqrt(2.0 / (w.shape[1] * w.shape[2] * w.shape[3])))
-                m.bn.weight.copy_(0.5 + torch.rand(m.bn.weight.shape, generator=g))
-                m.bn.bias.copy_(0.1 * torch.randn(m.bn.bias.shape, generator=g))
-                m.bn.running_mean.copy_(0.1 * torch.randn(m.bn.running_mean.shape, generator=g))
-                m.bn.running_var.copy_(0.5 + torch.rand(m.bn.running_var.shape, generator=g))
-        self._packs.clear()
-
-    # ---- weights ---------------------------------------------------------------------------------------------------------------
-    def load_weights(self, weights) -> "InceptionPool3":
-        """`weights`: a state dict or the path of one (read with `torch.load(weights_only=True)`): torch-fidelity's `pt_inception` or the
-        same keys under `inception.`.  Ignored: `num_batches_tracked`, `fc.*`, `AuxLogits.*`.  Anything else, or a missing key, raises a
-        KeyError that names it; a wrong shape or a non-positive `running_var + 1e-3` a ValueError.  A refused file changes nothing."""
-        sd = _read(weights)
-        if any(k.startswith("inception.") for k in sd):
-            sd = {(k[len("inception."):] if k.startswith("inception.") else k): v for k, v in sd.items()}
-        want = dict(self.state_dict())
-        ignored = lambda k: k.endswith("num_batches_tracked") or k.startswith(_IGNORED)
-        missing = sorted(k for k in want if k not in sd)
-        unexpected = sorted(k for k in sd if k not in want and not ignored(k))
-        if missing or unexpected:
-            raise KeyError(f"InceptionPool3.load_weights: missing keys {missing}, unexpected keys {unexpected}")
-        for k, ref in want.items():
-            if tuple(sd[k].shape) != tuple(ref.shape):
-                raise ValueError(f"InceptionPool3.load_weights: {k} has shape {tuple(sd[k].shape)}, expected {tuple(ref.shape)}")
-            if k.endswith("running_var") and not bool((sd[k].detach().double() + BN_EPS > 0).all()):
-                raise ValueError(f"InceptionPool3.load_weights: {k} + {BN_EPS} is not positive everywhere; BatchNorm divides by its root")
-        with torch.no_grad():
-            for k, ref in want.items():
-                ref.copy_(sd[k].detach().to(torch.float32))
-        self._packs.clear()
-        return self
-
-    def _apply(self, fn, *args, **kw):
-        self._packs.clear()                     # .to(device) / .float(): the packs follow the parameters
-        return super()._apply(fn, *args, **kw)
-
-    def _packed(self, dtype: torch.dtype) -> dict:
-        """name -> (packed weight, fp32 bias) with BatchNorm folded in, in fp64 on the host"""
-        mods = [self.get_submodule(name) for name, *_ in LAYERS]
-        dev = mods[0].conv.weight.device
-        key = (dtype, str(dev))
-        version = tuple(t._version for m in mods for t in (m.conv.weight, m.bn.weight, m.bn.bias, m.bn.running_mean, m.bn.running_var))
-        hit = self._packs.get(key)
-        if hit is None or hit[0] != version:
-            packs = {}
-            for (name, *_), m in zip(LAYERS, mods):
-                var = m.bn.running_var.detach().double().cpu() + BN_EPS
-                if not bool((var > 0).all()):
-                    raise ValueError(f"InceptionPool3: {name}.bn.running_var + {BN_EPS} is not positive everywhere")
-                g = m.bn.weight.detach().double().cpu() / var.sqrt()
-                w = m.conv.weight.detach().double().cpu() * g.view(-1, 1, 1, 1)
-                b = m.bn.bias.detach().double().cpu() - m.bn.running_mean.detach().double().cpu() * g
-                packs[name] = (pack_conv(w.float().to(dev), dtype), b.float().to(dev))
-            hit = (version, packs)
-            self._packs[key] = hit
-        return hit[1]
+        super().__init__(dtype)
+        self._init_weights(weights, allow_random_init)
 
     # ---- the network -----------------------------------------------------------------------------------------------------------
     @staticmethod
@@ -245,22 +127,6 @@ class InceptionPool3(nn.Module):
         m = min(n, self.chunk_images(self.compute_dtype if dtype is None else dtype, h, w))
         return ops._roundup(ops.inception_workspace_bytes(m, h, SIZE), 16) + m * FEATURES * 8
 
-    def _check(self, imgs: torch.Tensor) -> torch.Tensor:
-        if not imgs.is_cuda:
-            raise RuntimeError("mv_ldm_amd modules run only on a HIP device (no CPU fallback): move the module and its inputs to 'cuda'")
-        if imgs.dim() != 4 or imgs.shape[1] != 3:
-            raise ValueError(f"InceptionPool3: imgs must be [n, 3, h, w], got {tuple(imgs.shape)}")
-        if imgs.dtype not in (torch.uint8, torch.float32, torch.float16, torch.bfloat16):
-            raise TypeError(f"InceptionPool3: imgs is {imgs.dtype}; uint8 images, or float images in [0, 1], are scored")
-        if not imgs.is_contiguous():
-            raise ValueError(f"InceptionPool3: imgs must be contiguous NCHW (got strides {imgs.stride()}); call .contiguous() first")
-        if self.Conv2d_1a_3x3.conv.weight.device != imgs.device:
-            raise RuntimeError(f"InceptionPool3: the module is on {self.Conv2d_1a_3x3.conv.weight.device}, the images on {imgs.device} "
-                               "(no CPU fallback: module.to('cuda'))")
-        if imgs.shape[2] < 1 or imgs.shape[3] < 1:
-            raise ValueError(f"InceptionPool3: imgs {tuple(imgs.shape)} has an empty edge")
-        return imgs if imgs.dtype in (torch.float32, torch.uint8) else ops.convert(imgs, torch.float32)
-
     def _forward(self, x: torch.Tensor, packs: dict, keep: dict, wanted) -> torch.Tensor:
         """the prepared NHWC input -> the post-ReLU 8 x 8 x 2048 map; every stored map is post-ReLU"""
         spec = {name: (k, stride, pad) for name, _, _, k, stride, pad in LAYERS}
@@ -269,7 +135,7 @@ class InceptionPool3(nn.Module):
             k, stride, pad = spec[name]
             y = conv(x, packs[name][0], packs[name][1], k, stride, pad)
             if dst is None:
-                return ops.lpips_relu(y)
+                return ops.relu_(y)
             return ops.inception_concat(y, dst, off, relu=True)
 
         def new(x, h, w, c):
@@ -333,7 +199,8 @@ class InceptionPool3(nn.Module):
         return x
 
     def _run(self, imgs: torch.Tensor, out: Optional[torch.Tensor], state: Optional[torch.Tensor], dtype, ws, wanted=()):
-        imgs = self._check(imgs)
+        imgs = check_images("InceptionPool3", "imgs", imgs, self.Conv2d_1a_3x3.conv.weight.device, (torch.uint8, *FLOATS),
+                            "uint8 images, or float images in [0, 1], are scored")
         bad = [m for m in wanted if m not in MAPS]
         if bad:
             raise ValueError(f"InceptionPool3: return_maps {bad}; known: {MAPS}")
@@ -381,29 +248,17 @@ class InceptionPool3(nn.Module):
         raise NotImplementedError("InceptionPool3: call features(imgs)")
 
 
-class CleanFID(nn.Module):
+class CleanFID(FrechetStats):
     """`update(imgs, real)`, `compute()`, `reset()` around an `InceptionPool3`.  The two running states (count, sum f, sum f^T f; fp64,
     1 + 2048 + 2048^2 doubles each) live on the device; the sample counts are kept on the host too, so `compute()` can refuse without
-    a synchronisation."""
+    a synchronisation.  `compute(out=, ws=)`: `ws` is `ops.frechet_compute`'s workspace."""
 
     def __init__(self, model: InceptionPool3, keep_features: bool = False):
         super().__init__()
         self.model = model
         self.keep_features = bool(keep_features)
         self._feats = {True: [], False: []}
-        dev = model.Conv2d_1a_3x3.conv.weight.device
-        size = ops.frechet_state_size(FEATURES)
-        self.register_buffer("real_state", torch.zeros(size, dtype=torch.float64, device=dev), persistent=False)
-        self.register_buffer("fake_state", torch.zeros(size, dtype=torch.float64, device=dev), persistent=False)
-        self.register_buffer("info", torch.zeros(ops.FID_INFO, dtype=torch.float64, device=dev), persistent=False)
-        self._n = {True: 0, False: 0}
-
-    def _apply(self, fn, *args, **kw):
-        out = super()._apply(fn, *args, **kw)
-        for name in ("real_state", "fake_state", "info"):      # the statistics stay fp64 whatever the module is cast to
-            if self._buffers[name].dtype != torch.float64:
-                self._buffers[name] = self._buffers[name].double()
-        return out
+        self._init_stats(FEATURES, model.Conv2d_1a_3x3.conv.weight.device)
 
     @torch.no_grad()
     def update(self, imgs: torch.Tensor, real: bool, *, dtype: Optional[torch.dtype] = None, ws: Optional[torch.Tensor] = None) -> None:
@@ -420,15 +275,8 @@ class CleanFID(nn.Module):
             self.model._run(imgs, None, state, dtype, ws)
         self._n[bool(real)] += int(imgs.shape[0])
 
-    @torch.no_grad()
-    def compute(self, *, out: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """the 0-d fp32 score on the device.  Raises below 2 samples on a side (host counters: no synchronisation).  `self.info` then
-        holds the solves' record (`ops.frechet_compute`)."""
-        if self._n[True] < 2 or self._n[False] < 2:
-            raise RuntimeError("More than one sample is required for both the real and fake distributed to compute FID")
-        out = torch.empty((), dtype=torch.float32, device=self.real_state.device) if out is None else out
+    def _solve(self, out: torch.Tensor, ws: Optional[torch.Tensor] = None) -> None:
         ops.frechet_compute(self.real_state, self.fake_state, out, self.info, ws)
-        return out.view(())
 
     def features(self, real: bool) -> torch.Tensor:
         """the kept fp64 `[n, 2048]` features of one side, in the order of the `update` calls (`keep_features=True` only)"""
@@ -449,9 +297,7 @@ class CleanFID(nn.Module):
 
     def reset(self) -> None:
         """both sides empty again (stream-ordered fills of the two states); the kept features are dropped"""
-        self.real_state.zero_()
-        self.fake_state.zero_()
-        self._n = {True: 0, False: 0}
+        super().reset()
         self._feats = {True: [], False: []}
 
     def forward(self, *args, **kw):

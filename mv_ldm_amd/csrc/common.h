@@ -208,4 +208,9 @@ template <typename F> inline int dispatch_dtype(int dtype, F&& f) {
 }
 inline size_t dtype_size(int dtype) { return dtype == MVLDM_F32 ? 4 : 2; }
 
+// host: the argument checks the metric files (lpips / dists / fid / inception / kid .hip) share
+inline bool dtype_ok(int dtype) { return dtype == MVLDM_F32 || dtype == MVLDM_BF16 || dtype == MVLDM_F16; }
+inline bool aligned(const void* p, size_t a) { return p != nullptr && ((uintptr_t)p & (a - 1)) == 0; }
+inline bool channels_ok(int c) { return c >= 64 && c <= 512 && c % 64 == 0; }      // what the tap / pool kernels' chunk walks are built for
+
 }  // namespace mvldm

@@ -216,13 +216,10 @@ __global__ __launch_bounds__(256) void dists_fold_kernel(const double* __restric
 }
 
 // ---- host -------------------------------------------------------------------------------------------------------------------------
-static bool dists_c_ok(int c) { return c >= 64 && c <= 512 && c % 64 == 0; }
 static int dists_ppb(int c) { return c == 3 ? kDistsPpb0 : max(256, 32768 / c); }     // pixels of one workgroup: 512 at C = 64, else 256
-static bool dists_dtype_ok(int dtype) { return dtype == MVLDM_F32 || dtype == MVLDM_BF16 || dtype == MVLDM_F16; }
-static bool aligned(const void* p, size_t a) { return p != nullptr && ((uintptr_t)p & (a - 1)) == 0; }
 
 int dists_stat_slots(int h, int w, int c) {
-    if (h < 1 || w < 1 || !(c == 3 || dists_c_ok(c))) return 0;
+    if (h < 1 || w < 1 || !(c == 3 || channels_ok(c))) return 0;
     const long long px = (long long)h * w;
     if (px > 0x7FFFFFFF) return 0;
     return (int)((px + dists_ppb(c) - 1) / dists_ppb(c));
@@ -260,7 +257,7 @@ size_t dists_workspace_bytes(int n_img, int h, int w) {
 int dists_prep_run(const float* in0, const float* in1, void* dst, int n_img, int h, int w, int c_pad, int dtype, hipStream_t s) {
     MVLDM_REQUIRE(n_img >= 0, "dists_prep: n_img %d", n_img);
     MVLDM_REQUIRE(h >= 1 && w >= 1, "dists_prep: image %d x %d", h, w);
-    MVLDM_REQUIRE(dists_dtype_ok(dtype), "dists_prep: unknown dtype %d", dtype);
+    MVLDM_REQUIRE(dtype_ok(dtype), "dists_prep: unknown dtype %d", dtype);
     MVLDM_REQUIRE(c_pad == (dtype == MVLDM_F32 ? 4 : 8), "dists_prep: c_pad %d is not the 16-byte padding of 3 channels in dtype %d", c_pad, dtype);
     MVLDM_REQUIRE((long long)h * w <= 0x7FFFFFFF, "dists_prep: a %d x %d image is too large", h, w);
     if (n_img == 0) return MVLDM_OK;
@@ -278,8 +275,8 @@ int dists_prep_run(const float* in0, const float* in1, void* dst, int n_img, int
 int dists_stats_run(const void* feat, const void* feat_b, int n_img, int h, int w, int c, int dtype, double* ws, size_t ws_bytes, int off,
                     int stride, hipStream_t s) {
     MVLDM_REQUIRE(n_img >= 0 && h >= 1 && w >= 1, "dists_stats: n_img %d, map %d x %d", n_img, h, w);
-    MVLDM_REQUIRE(c == 3 || dists_c_ok(c), "dists_stats: C = %d channels; multiples of 64 up to 512 (or the 3 of the raw image) are supported", c);
-    MVLDM_REQUIRE(dists_dtype_ok(dtype), "dists_stats: unknown dtype %d", dtype);
+    MVLDM_REQUIRE(c == 3 || channels_ok(c), "dists_stats: C = %d channels; multiples of 64 up to 512 (or the 3 of the raw image) are supported", c);
+    MVLDM_REQUIRE(dtype_ok(dtype), "dists_stats: unknown dtype %d", dtype);
     MVLDM_REQUIRE(c != 3 || dtype == MVLDM_F32, "dists_stats: the raw image (C = 3) is fp32 NCHW, not dtype %d", dtype);
     const int blocks_per_img = dists_stat_slots(h, w, c);
     MVLDM_REQUIRE(blocks_per_img > 0, "dists_stats: a %d x %d map is too large", h, w);
@@ -311,8 +308,8 @@ int dists_stats_run(const void* feat, const void* feat_b, int n_img, int h, int 
 
 int dists_l2pool_run(const void* feat, void* out, int n_img, int h, int w, int c, int dtype, hipStream_t s) {
     MVLDM_REQUIRE(n_img >= 0 && h >= 1 && w >= 1, "dists_l2pool: n_img %d, map %d x %d", n_img, h, w);
-    MVLDM_REQUIRE(dists_c_ok(c), "dists_l2pool: C = %d channels; multiples of 64 up to 512 are supported", c);
-    MVLDM_REQUIRE(dists_dtype_ok(dtype), "dists_l2pool: unknown dtype %d", dtype);
+    MVLDM_REQUIRE(channels_ok(c), "dists_l2pool: C = %d channels; multiples of 64 up to 512 are supported", c);
+    MVLDM_REQUIRE(dtype_ok(dtype), "dists_l2pool: unknown dtype %d", dtype);
     MVLDM_REQUIRE((long long)h * w <= 0x7FFFFFFF, "dists_l2pool: a %d x %d map is too large", h, w);
     if (n_img == 0) return MVLDM_OK;
     MVLDM_REQUIRE(aligned(feat, 16) && aligned(out, 16), "dists_l2pool: null or unaligned pointer");

@@ -8,8 +8,8 @@
 //                   the pooled map per channel in fp64 from the first add.  The pooled map is never written.  A lane owns one 16-byte
 //                   channel chunk and walks every `rows`-th output pixel of the workgroup's band of output rows; the lanes that own the same
 //                   chunk are added through LDS in row order.  One fp64 partial per (image, band, channel), no atomics.
-//   fid_accumulate  two launches: the partials of each image in band order / pixels -> the fp64 features [n][c]; then one thread per
-//                   entry of the state (count, sum f, sum f^T f) adds the images in order and adds that to the state
+//   fid_accumulate  the partials of each image in band order / pixels -> the fp64 features [n][c]; then frechet_accumulate (inception.hip)
+//                   adds them to the state (count, sum f, sum f^T f)
 //   fid_compute     ONE workgroup: mu and Sigma of both states in fp64, Sigma1 = V D V^T by cyclic Jacobi in LDS, the eigenvalues of
 //                   S = D^1/2 V^T Sigma2 V D^1/2 (the spectrum of Sigma1^1/2 Sigma2 Sigma1^1/2) the same way,
 //                   fid = |mu1 - mu2|^2 + tr Sigma1 + tr Sigma2 - 2 sum sqrt(max(lambda_i, 0))
@@ -113,22 +113,6 @@ __global__ __launch_bounds__(256) void fid_features_kernel(const double* __restr
         feat[(size_t)blockIdx.x * C + c] = v;
         if (feat_out) feat_out[(size_t)blockIdx.x * C + c] = v;
     }
-}
-
-// entry 0: the count; 1 + a: sum_i f[i][a]; 1 + C + a C + b: sum_i f[i][a] f[i][b] -- the images in order, then one add to the state
-__global__ __launch_bounds__(256) void fid_state_kernel(const double* __restrict__ feat, int n, int C, double* __restrict__ state) {
-    const int e = blockIdx.x * 256 + threadIdx.x;
-    if (e >= 1 + C + C * C) return;
-    double v = 0.0;
-    if (e == 0) {
-        v = (double)n;
-    } else if (e <= C) {
-        for (int i = 0; i < n; ++i) v += feat[(size_t)i * C + (e - 1)];
-    } else {
-        const int a = (e - 1 - C) / C, b = (e - 1 - C) % C;
-        for (int i = 0; i < n; ++i) v += feat[(size_t)i * C + a] * feat[(size_t)i * C + b];
-    }
-    state[e] += v;
 }
 
 // ---- the Frechet distance: one workgroup of 256 threads -------------------------------------------------------------------------------
@@ -343,13 +327,11 @@ __global__ __launch_bounds__(256) void fid_compute_kernel(const double* __restri
 }
 
 // ---- host -------------------------------------------------------------------------------------------------------------------------
-static bool fid_c_ok(int c) { return c >= 64 && c <= 512 && c % 64 == 0; }
-static bool fid_dtype_ok(int dtype) { return dtype == MVLDM_F32 || dtype == MVLDM_BF16 || dtype == MVLDM_F16; }
-static bool fid_aligned(const void* p, size_t a) { return p != nullptr && ((uintptr_t)p & (a - 1)) == 0; }
+int frechet_accumulate_run(const double* features, int n, int d, double* state, hipStream_t s);      // inception.hip: d a multiple of 64 up to 2048
 static int fid_band(int ow) { return (kFidBandPx + ow - 1) / ow; }      // output rows of one workgroup
 
 int fid_pool_slots(int h, int w, int c) {
-    if (h < 3 || w < 3 || !fid_c_ok(c) || (long long)h * w > 0x7FFFFFFF) return 0;
+    if (h < 3 || w < 3 || !channels_ok(c) || (long long)h * w > 0x7FFFFFFF) return 0;
     const int oh = (h - 3) / 2 + 1, ow = (w - 3) / 2 + 1, band = fid_band(ow);
     return (oh + band - 1) / band;
 }
@@ -364,11 +346,11 @@ int fid_prep_run(const void* src, int src_u8, void* dst, int n_img, int h, int w
     MVLDM_REQUIRE(n_img >= 0, "fid_prep: n_img %d", n_img);
     MVLDM_REQUIRE(h >= 1 && w >= 1 && oh >= 1 && ow >= 1, "fid_prep: image %d x %d -> %d x %d: an edge below 1", h, w, oh, ow);
     MVLDM_REQUIRE(src_u8 == 0 || src_u8 == 1, "fid_prep: src_u8 %d", src_u8);
-    MVLDM_REQUIRE(fid_dtype_ok(dtype), "fid_prep: unknown dtype %d", dtype);
+    MVLDM_REQUIRE(dtype_ok(dtype), "fid_prep: unknown dtype %d", dtype);
     MVLDM_REQUIRE(c_pad == (dtype == MVLDM_F32 ? 4 : 8), "fid_prep: c_pad %d is not the 16-byte padding of 3 channels in dtype %d", c_pad, dtype);
     MVLDM_REQUIRE((long long)h * w <= 0x7FFFFFFF && (long long)oh * ow <= 0x7FFFFFFF, "fid_prep: %d x %d -> %d x %d is too large", h, w, oh, ow);
     if (n_img == 0) return MVLDM_OK;
-    MVLDM_REQUIRE(fid_aligned(src, src_u8 ? 1 : 4) && fid_aligned(dst, 16), "fid_prep: null or unaligned pointer");
+    MVLDM_REQUIRE(aligned(src, src_u8 ? 1 : 4) && aligned(dst, 16), "fid_prep: null or unaligned pointer");
     const size_t n_px = (size_t)n_img * oh * ow, blocks = (n_px + 255) / 256;
     MVLDM_REQUIRE(blocks <= 0x7FFFFFFFu, "fid_prep: %zu workgroups", blocks);
     const float scale_h = (float)h / (float)oh, scale_w = (float)w / (float)ow;
@@ -383,14 +365,14 @@ int fid_prep_run(const void* src, int src_u8, void* dst, int n_img, int h, int w
 int fid_pool_run(const void* feat, int n_img, int h, int w, int c, int dtype, double* ws, size_t ws_bytes, hipStream_t s) {
     MVLDM_REQUIRE(n_img >= 0, "fid_pool: n_img %d", n_img);
     MVLDM_REQUIRE(h >= 3 && w >= 3, "fid_pool: a %d x %d map holds no 3 x 3 window", h, w);
-    MVLDM_REQUIRE(fid_c_ok(c), "fid_pool: C = %d channels; multiples of 64 up to 512 are supported", c);
-    MVLDM_REQUIRE(fid_dtype_ok(dtype), "fid_pool: unknown dtype %d", dtype);
+    MVLDM_REQUIRE(channels_ok(c), "fid_pool: C = %d channels; multiples of 64 up to 512 are supported", c);
+    MVLDM_REQUIRE(dtype_ok(dtype), "fid_pool: unknown dtype %d", dtype);
     const int slots = fid_pool_slots(h, w, c);
     MVLDM_REQUIRE(slots > 0, "fid_pool: a %d x %d map is too large", h, w);
     const size_t need = (size_t)n_img * slots * c * sizeof(double);
     MVLDM_REQUIRE(ws_bytes >= need, "fid_pool: workspace of %zu bytes, need %zu", ws_bytes, need);
     if (n_img == 0) return MVLDM_OK;
-    MVLDM_REQUIRE(fid_aligned(feat, 16) && fid_aligned(ws, 8), "fid_pool: null or unaligned pointer");
+    MVLDM_REQUIRE(aligned(feat, 16) && aligned(ws, 8), "fid_pool: null or unaligned pointer");
     const size_t blocks = (size_t)n_img * slots;
     MVLDM_REQUIRE(blocks <= 0x7FFFFFFFu, "fid_pool: %zu workgroups", blocks);
     const int oh = (h - 3) / 2 + 1, ow = (w - 3) / 2 + 1;
@@ -408,18 +390,17 @@ int fid_accumulate_run(double* ws, size_t ws_bytes, int n_img, int h, int w, int
     const size_t need = (size_t)n_img * ((size_t)slots + 1) * c * sizeof(double);
     MVLDM_REQUIRE(ws_bytes >= need, "fid_accumulate: workspace of %zu bytes, need %zu", ws_bytes, need);
     if (n_img == 0) return MVLDM_OK;
-    MVLDM_REQUIRE(fid_aligned(ws, 8) && (state == nullptr || fid_aligned(state, 8)) && (features == nullptr || fid_aligned(features, 8)),
+    MVLDM_REQUIRE(aligned(ws, 8) && (state == nullptr || aligned(state, 8)) && (features == nullptr || aligned(features, 8)),
                   "fid_accumulate: null or unaligned pointer");
     const int oh = (h - 3) / 2 + 1, ow = (w - 3) / 2 + 1;
     double* feat = ws + (size_t)n_img * slots * c;
     hipLaunchKernelGGL(fid_features_kernel, dim3(n_img), dim3(256), 0, s, (const double*)ws, slots, c, (double)oh * (double)ow, feat, features);
-    if (state) hipLaunchKernelGGL(fid_state_kernel, dim3((1 + c + c * c + 255) / 256), dim3(256), 0, s, (const double*)feat, n_img, c, state);
-    return check_launch();
+    return state ? frechet_accumulate_run(feat, n_img, c, state, s) : check_launch();
 }
 
 int fid_compute_run(const double* s1, const double* s2, int c, float* score, double* info, hipStream_t s) {
     MVLDM_REQUIRE(c == kFidD, "fid_compute: C = %d features; the solve is built for 64 (feature=64)", c);
-    MVLDM_REQUIRE(fid_aligned(s1, 8) && fid_aligned(s2, 8) && fid_aligned(score, 4) && fid_aligned(info, 8), "fid_compute: null or unaligned pointer");
+    MVLDM_REQUIRE(aligned(s1, 8) && aligned(s2, 8) && aligned(score, 4) && aligned(info, 8), "fid_compute: null or unaligned pointer");
     static std::atomic<uint64_t> mask{0};
     const int rc = ensure_dyn_smem((const void*)fid_compute_kernel, kFidSmemBytes, mask);
     if (rc != MVLDM_OK) return rc;

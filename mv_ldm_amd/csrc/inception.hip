@@ -10,7 +10,8 @@
 //                       the taps inside the map; inception_concat copies a contiguous map (with ReLU if asked): all three write a channel
 //                       slice of a wider NHWC buffer, so a block's concatenation costs no pass of its own
 //   inception_features  NHWC [n][h][w][c] -> fp64 means [n][c]: one thread per (image, channel), pixels in order, fp64 from the first add
-//   frechet_accumulate  fid_state_kernel's contract at width d: state (count, sum f, sum f^T f) += n feature rows, images in order
+//   frechet_accumulate  state (count, sum f, sum f^T f) += n feature rows of width d, images in order: one thread per entry of the state adds the
+//                       images and then adds that to the state.  fid_accumulate (fid.hip) ends in it too, at width 64
 //   frechet_compute     the Frechet distance at d <= 2048 with the matrices in global memory: Sigma1 = V D V^T and the spectrum of
 //                       D^1/2 V^T Sigma2 V D^1/2 by ONE-SIDED Jacobi (Hestenes): G = A V is kept by columns, a workgroup owns one pair of
 //                       columns of a round (round-robin ordering, d / 2 disjoint pairs, one launch a round), takes the rotation from three
@@ -478,8 +479,6 @@ __global__ __launch_bounds__(256) void frechet_score_kernel(int d, const double*
 }
 
 // ---- host -------------------------------------------------------------------------------------------------------------------------
-static bool inc_dtype_ok(int dtype) { return dtype == MVLDM_F32 || dtype == MVLDM_BF16 || dtype == MVLDM_F16; }
-static bool inc_aligned(const void* p, size_t a) { return p != nullptr && ((uintptr_t)p & (a - 1)) == 0; }
 static bool frechet_d_ok(int d) { return d >= 64 && d <= kFrMaxD && d % 64 == 0; }
 constexpr long long kOffsetMax = 0x7FFFFFFFll;      // bytes of an operand the convolutions behind these kernels can address
 
@@ -493,7 +492,7 @@ int inception_prep_run(const void* src, int src_u8, void* dst, int n_img, int h,
     MVLDM_REQUIRE(n_img >= 0, "inception_prep: n_img %d", n_img);
     MVLDM_REQUIRE(h >= 1 && w >= 1 && oh >= 1 && ow >= 1, "inception_prep: image %d x %d -> %d x %d: an edge below 1", h, w, oh, ow);
     MVLDM_REQUIRE(src_u8 == 0 || src_u8 == 1, "inception_prep: src_u8 %d", src_u8);
-    MVLDM_REQUIRE(inc_dtype_ok(dtype), "inception_prep: unknown dtype %d", dtype);
+    MVLDM_REQUIRE(dtype_ok(dtype), "inception_prep: unknown dtype %d", dtype);
     MVLDM_REQUIRE(c_pad == (dtype == MVLDM_F32 ? 4 : 8), "inception_prep: c_pad %d is not the 16-byte padding of 3 channels in dtype %d", c_pad, dtype);
     MVLDM_REQUIRE((long long)h * w <= kOffsetMax && (long long)oh * ow <= kOffsetMax && (long long)h * ow <= kOffsetMax,
                   "inception_prep: %d x %d -> %d x %d is too large", h, w, oh, ow);
@@ -502,7 +501,7 @@ int inception_prep_run(const void* src, int src_u8, void* dst, int n_img, int h,
     MVLDM_REQUIRE(ws_bytes >= need, "inception_prep: workspace of %zu bytes, need %zu", ws_bytes, need);
     MVLDM_REQUIRE((double)n_img * oh * ow * c_pad * (double)dtype_size(dtype) <= (double)kOffsetMax,
                   "inception_prep: the output of %d images is past the 32-bit offset range", n_img);
-    MVLDM_REQUIRE(inc_aligned(src, src_u8 ? 1 : 4) && inc_aligned(dst, 16) && inc_aligned(ws, 4), "inception_prep: null or unaligned pointer");
+    MVLDM_REQUIRE(aligned(src, src_u8 ? 1 : 4) && aligned(dst, 16) && aligned(ws, 4), "inception_prep: null or unaligned pointer");
     const size_t total = (size_t)n_img * 3 * h * ow, n_px = (size_t)n_img * oh * ow;
     const size_t b1 = (total + 255) / 256, b2 = (n_px + 255) / 256;
     MVLDM_REQUIRE(b1 <= 0x7FFFFFFFu && b2 <= 0x7FFFFFFFu, "inception_prep: %zu workgroups", b1 > b2 ? b1 : b2);
@@ -520,7 +519,7 @@ int inception_prep_run(const void* src, int src_u8, void* dst, int n_img, int h,
 static int inc_map_ok(const char* who, int n_img, int h, int w, int c, int dtype) {
     MVLDM_REQUIRE(n_img >= 0, "%s: n_img %d", who, n_img);
     MVLDM_REQUIRE(h >= 1 && w >= 1, "%s: map %d x %d: an edge below 1", who, h, w);
-    MVLDM_REQUIRE(inc_dtype_ok(dtype), "%s: unknown dtype %d", who, dtype);
+    MVLDM_REQUIRE(dtype_ok(dtype), "%s: unknown dtype %d", who, dtype);
     MVLDM_REQUIRE(c >= 1 && c % (16 / (int)dtype_size(dtype)) == 0, "%s: C = %d channels are no whole 16-byte chunks", who, c);
     MVLDM_REQUIRE((double)n_img * h * w * c * (double)dtype_size(dtype) <= (double)kOffsetMax, "%s: %d x %d x %d x %d is past the 32-bit offset range", who,
                   n_img, h, w, c);
@@ -542,7 +541,7 @@ int inception_unfold_run(const void* src, void* dst, int n_img, int h, int w, in
     MVLDM_REQUIRE((double)n_img * h * w * c * kh * kw * (double)dtype_size(dtype) <= (double)kOffsetMax,
                   "inception_unfold: the unfolded map is past the 32-bit offset range");
     if (n_img == 0) return MVLDM_OK;
-    MVLDM_REQUIRE(inc_aligned(src, 16) && inc_aligned(dst, 16), "inception_unfold: null or unaligned pointer");
+    MVLDM_REQUIRE(aligned(src, 16) && aligned(dst, 16), "inception_unfold: null or unaligned pointer");
     const int cp = c / (16 / (int)dtype_size(dtype));
     const size_t total = (size_t)n_img * h * w * kh * kw * cp, blocks = (total + 255) / 256;
     return dispatch_dtype(dtype, [&](auto tag) {
@@ -563,7 +562,7 @@ int inception_pool_run(bool is_max, const void* src, void* dst, int n_img, int h
     rc = inc_slice_ok(who, c, dst_ld, dst_c_off, dtype, (double)n_img * oh * ow);
     if (rc != MVLDM_OK) return rc;
     if (n_img == 0) return MVLDM_OK;
-    MVLDM_REQUIRE(inc_aligned(src, 16) && inc_aligned(dst, 16), "%s: null or unaligned pointer", who);
+    MVLDM_REQUIRE(aligned(src, 16) && aligned(dst, 16), "%s: null or unaligned pointer", who);
     const int cp = c / (16 / (int)dtype_size(dtype));
     const size_t total = (size_t)n_img * oh * ow * cp, blocks = (total + 255) / 256;
     return dispatch_dtype(dtype, [&](auto tag) {
@@ -575,13 +574,13 @@ int inception_pool_run(bool is_max, const void* src, void* dst, int n_img, int h
 }
 
 int inception_concat_run(const void* src, void* dst, size_t rows, int c, int dst_ld, int dst_c_off, int relu, int dtype, hipStream_t s) {
-    MVLDM_REQUIRE(inc_dtype_ok(dtype), "inception_concat: unknown dtype %d", dtype);
+    MVLDM_REQUIRE(dtype_ok(dtype), "inception_concat: unknown dtype %d", dtype);
     MVLDM_REQUIRE(c >= 1 && c % (16 / (int)dtype_size(dtype)) == 0, "inception_concat: C = %d channels are no whole 16-byte chunks", c);
     MVLDM_REQUIRE(relu == 0 || relu == 1, "inception_concat: relu %d", relu);
     int rc = inc_slice_ok("inception_concat", c, dst_ld, dst_c_off, dtype, (double)rows);
     if (rc != MVLDM_OK) return rc;
     if (rows == 0) return MVLDM_OK;
-    MVLDM_REQUIRE(inc_aligned(src, 16) && inc_aligned(dst, 16), "inception_concat: null or unaligned pointer");
+    MVLDM_REQUIRE(aligned(src, 16) && aligned(dst, 16), "inception_concat: null or unaligned pointer");
     const int cp = c / (16 / (int)dtype_size(dtype));
     const size_t total = rows * cp, blocks = (total + 255) / 256;
     return dispatch_dtype(dtype, [&](auto tag) {
@@ -596,7 +595,7 @@ int inception_features_run(const void* feat, int n_img, int h, int w, int c, int
     if (rc != MVLDM_OK) return rc;
     MVLDM_REQUIRE((long long)h * w <= kOffsetMax && n_img <= 65535, "inception_features: %d maps of %d x %d are too many or too large", n_img, h, w);
     if (n_img == 0) return MVLDM_OK;
-    MVLDM_REQUIRE(inc_aligned(feat, 16) && inc_aligned(out, 8), "inception_features: null or unaligned pointer");
+    MVLDM_REQUIRE(aligned(feat, 16) && aligned(out, 8), "inception_features: null or unaligned pointer");
     return dispatch_dtype(dtype, [&](auto tag) {
         using T = decltype(tag);
         hipLaunchKernelGGL(inception_features_kernel<T>, dim3((c + 255) / 256, n_img), dim3(256), 0, s, (const T*)feat, h * w, c, out);
@@ -608,7 +607,7 @@ int frechet_accumulate_run(const double* features, int n, int d, double* state, 
     MVLDM_REQUIRE(n >= 0, "frechet_accumulate: n %d", n);
     MVLDM_REQUIRE(frechet_d_ok(d), "frechet_accumulate: d = %d features; multiples of 64 up to %d are supported", d, kFrMaxD);
     if (n == 0) return MVLDM_OK;
-    MVLDM_REQUIRE(inc_aligned(features, 8) && inc_aligned(state, 8), "frechet_accumulate: null or unaligned pointer");
+    MVLDM_REQUIRE(aligned(features, 8) && aligned(state, 8), "frechet_accumulate: null or unaligned pointer");
     const size_t entries = (size_t)1 + d + (size_t)d * d;
     hipLaunchKernelGGL(frechet_state_kernel, dim3((unsigned)((entries + 255) / 256)), dim3(256), 0, s, features, n, d, state);
     return check_launch();
@@ -629,7 +628,7 @@ static void frechet_solve(int d, double tol, const FrWs& w, hipStream_t s) {
 int frechet_compute_run(const double* s1, const double* s2, int d, double* ws, size_t ws_bytes, float* score, double* info, hipStream_t s) {
     MVLDM_REQUIRE(frechet_d_ok(d), "frechet_compute: d = %d features; multiples of 64 up to %d are supported", d, kFrMaxD);
     MVLDM_REQUIRE(ws_bytes >= frechet_workspace_bytes(d), "frechet_compute: workspace of %zu bytes, need %zu", ws_bytes, frechet_workspace_bytes(d));
-    MVLDM_REQUIRE(inc_aligned(s1, 8) && inc_aligned(s2, 8) && inc_aligned(ws, 8) && inc_aligned(score, 4) && inc_aligned(info, 8),
+    MVLDM_REQUIRE(aligned(s1, 8) && aligned(s2, 8) && aligned(ws, 8) && aligned(score, 4) && aligned(info, 8),
                   "frechet_compute: null or unaligned pointer");
     const FrWs w = frechet_ws(ws, d);
     const double tol = sqrt((double)d) * 2.220446049250313e-16;     // dgesvj's: the round-off of a d-term dot product of unit vectors

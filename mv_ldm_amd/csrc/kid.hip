@@ -27,7 +27,6 @@ constexpr int kKidLd = kKidBk + 1;      // doubles per LDS row: rows r and r + 1
 constexpr int kKidMaxD = 2048;          // the widths mvldm_frechet_* takes
 
 static bool kid_d_ok(int d) { return d >= 64 && d <= kKidMaxD && d % 64 == 0; }
-static bool kid_aligned(const void* p, size_t a) { return p != nullptr && ((uintptr_t)p & (a - 1)) == 0; }
 static long long kid_tiles(int m) { return (m + kKidTile - 1) / kKidTile; }
 // tiles of one subset: the pairs a <= b of the two symmetric Grams, then every tile of the cross Gram
 static long long kid_tiles_per_subset(int m) {
@@ -201,8 +200,8 @@ int kid_compute_run(const double* f1, int n1, const double* f2, int n2, int d, c
     MVLDM_REQUIRE(blocks <= 0x7FFFFFFFll && (long long)num_subsets * m <= 0x7FFFFFFFll, "kid_compute: %d subsets of %d rows are too many", num_subsets, m);
     MVLDM_REQUIRE(ws_bytes >= kid_workspace_bytes(m, num_subsets), "kid_compute: workspace of %zu bytes, need %zu", ws_bytes,
                   kid_workspace_bytes(m, num_subsets));
-    MVLDM_REQUIRE(kid_aligned(f1, 16) && kid_aligned(f2, 16) && kid_aligned(idx1, 4) && kid_aligned(idx2, 4) && kid_aligned(ws, 8) &&
-                      kid_aligned(score, 4) && kid_aligned(info, 8) && (per_subset == nullptr || kid_aligned(per_subset, 8)),
+    MVLDM_REQUIRE(aligned(f1, 16) && aligned(f2, 16) && aligned(idx1, 4) && aligned(idx2, 4) && aligned(ws, 8) &&
+                      aligned(score, 4) && aligned(info, 8) && (per_subset == nullptr || aligned(per_subset, 8)),
                   "kid_compute: null or unaligned pointer");
     const int T = (int)kid_tiles(m), pairs = T * (T + 1) / 2;
     double* per = per_subset ? per_subset : ws + (size_t)blocks;

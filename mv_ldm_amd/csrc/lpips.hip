@@ -198,11 +198,10 @@ __global__ __launch_bounds__(256) void lpips_fold_kernel(const double* __restric
 }
 
 // ---- host -------------------------------------------------------------------------------------------------------------------------
-static bool lpips_c_ok(int c) { return c >= 64 && c <= 512 && c % 64 == 0; }
 static int lpips_qpb(int c) { return max(8, (4096 / c) & ~7); }      // quads of one workgroup: 64 at C = 64 ... 8 at C = 512, whatever the dtype
 
 int lpips_tap_slots(int h, int w, int c) {
-    if (h < 1 || w < 1 || !lpips_c_ok(c)) return 0;
+    if (h < 1 || w < 1 || !channels_ok(c)) return 0;
     const long long Q = (long long)((h + 1) / 2) * ((w + 1) / 2);
     const long long blocks = (Q + lpips_qpb(c) - 1) / lpips_qpb(c);
     return blocks > 0x7FFFFFFF ? 0 : (int)blocks;
@@ -228,7 +227,7 @@ int lpips_prep_run(const float* in0, const float* in1, void* dst, int n_img, int
     MVLDM_REQUIRE(n_img >= 0, "lpips_prep: n_img %d", n_img);
     MVLDM_REQUIRE(h >= kLpipsMinEdge && w >= kLpipsMinEdge, "lpips_prep: a %d x %d image leaves nothing after four 2x2 pool stages (at least %d x %d)",
                   h, w, kLpipsMinEdge, kLpipsMinEdge);
-    MVLDM_REQUIRE(dtype == MVLDM_F32 || dtype == MVLDM_BF16 || dtype == MVLDM_F16, "lpips_prep: unknown dtype %d", dtype);
+    MVLDM_REQUIRE(dtype_ok(dtype), "lpips_prep: unknown dtype %d", dtype);
     MVLDM_REQUIRE(c_pad == (dtype == MVLDM_F32 ? 4 : 8), "lpips_prep: c_pad %d is not the 16-byte padding of 3 channels in dtype %d", c_pad, dtype);
     if (n_img == 0) return MVLDM_OK;
     MVLDM_REQUIRE(in0 && in1 && dst, "lpips_prep: null pointer");
@@ -243,11 +242,11 @@ int lpips_prep_run(const float* in0, const float* in1, void* dst, int n_img, int
 }
 
 int lpips_relu_run(void* x, size_t n, int dtype, hipStream_t s) {
-    MVLDM_REQUIRE(dtype == MVLDM_F32 || dtype == MVLDM_BF16 || dtype == MVLDM_F16, "lpips_relu: unknown dtype %d", dtype);
+    MVLDM_REQUIRE(dtype_ok(dtype), "lpips_relu: unknown dtype %d", dtype);
     const size_t epc = dtype == MVLDM_F32 ? 4 : 8;
     MVLDM_REQUIRE(n % epc == 0, "lpips_relu: %zu elements are no whole number of 16-byte chunks", n);
     if (n == 0) return MVLDM_OK;
-    MVLDM_REQUIRE(x && ((uintptr_t)x & 15) == 0, "lpips_relu: null or unaligned pointer");
+    MVLDM_REQUIRE(aligned(x, 16), "lpips_relu: null or unaligned pointer");
     const size_t chunks = n / epc, blocks = (chunks + 1023) / 1024;
     MVLDM_REQUIRE(blocks <= 0x7FFFFFFFu, "lpips_relu: %zu workgroups", blocks);
     return dispatch_dtype(dtype, [&](auto tag) {
@@ -260,8 +259,8 @@ int lpips_relu_run(void* x, size_t n, int dtype, hipStream_t s) {
 int lpips_tap_run(const void* feat, const float* weight, void* pooled, int n_img, int h, int w, int c, int dtype, double* ws, size_t ws_bytes,
                   int slot0, int slots, hipStream_t s) {
     MVLDM_REQUIRE(n_img >= 0 && h >= 1 && w >= 1, "lpips_tap: n_img %d, map %d x %d", n_img, h, w);
-    MVLDM_REQUIRE(lpips_c_ok(c), "lpips_tap: C = %d channels; multiples of 64 up to 512 are supported", c);
-    MVLDM_REQUIRE(dtype == MVLDM_F32 || dtype == MVLDM_BF16 || dtype == MVLDM_F16, "lpips_tap: unknown dtype %d", dtype);
+    MVLDM_REQUIRE(channels_ok(c), "lpips_tap: C = %d channels; multiples of 64 up to 512 are supported", c);
+    MVLDM_REQUIRE(dtype_ok(dtype), "lpips_tap: unknown dtype %d", dtype);
     const int blocks_per_img = lpips_tap_slots(h, w, c);
     MVLDM_REQUIRE(blocks_per_img > 0, "lpips_tap: a %d x %d map is too large", h, w);
     MVLDM_REQUIRE(slot0 >= 0 && slots >= 1 && (long long)slot0 + blocks_per_img <= slots, "lpips_tap: partials [%d, %d + %d) of %d per image", slot0,

@@ -12,27 +12,18 @@ against the package itself ("parity unpinned").
 """
 from __future__ import annotations
 
-import math
-import warnings
-from typing import List, Optional
+from typing import Optional
 
 import torch
 from torch import nn
 
 from . import ops
-from .lpips import LPIPS, _Conv, _read
+from ._metric_nets import VGG_SLICES as VGG_STAGES, VGG_WIDTH, VGGTrunk, load_state      # noqa: F401  (the stage table stays importable from here)
 
-# stage -> torchvision `features` indices of its convs (the ReLUs and L2 pools between them hold no parameters)
-VGG_STAGES = {1: (0, 2), 2: (5, 7), 3: (10, 12, 14), 4: (17, 19, 21), 5: (24, 26, 28)}
-VGG_WIDTH = {1: 64, 2: 128, 3: 256, 4: 512, 5: 512}
 L2POOLS = {2: 4, 3: 9, 4: 16, 5: 23}          # stage -> index of the L2pooling that opens it (its `filter` buffer is a constant here)
 MEAN = (0.485, 0.456, 0.406)
 STD = (0.229, 0.224, 0.225)
 N_CHANNELS = sum(ops.DISTS_CHANNELS)          # 1475
-
-
-def _conv_names() -> List[str]:
-    return [f"stage{s}.{i}" for s, idx in VGG_STAGES.items() for i in idx]
 
 
 def _constants() -> dict:
@@ -45,47 +36,29 @@ def _constants() -> dict:
     return out
 
 
-class DISTS(nn.Module):
+class DISTS(VGGTrunk):
     """`DISTS_pytorch.DISTS()`; fp32 parameters under the package's key names (`stage1.{0,2}`, `stage2.{5,7}`, `stage3.{10,12,14}`,
     `stage4.{17,19,21}`, `stage5.{24,26,28}`, each `.weight|.bias`, and `alpha`, `beta` `[1, 1475, 1, 1]`).  `dtype`: the compute dtype
     of the activations and packed weights (float32 by default: a metric; float16 / bfloat16 are allowed).  `weights` / `alpha_beta`:
     see `load_weights`; without them the module keeps a random init and says so."""
+    KEY = "stage{s}.{i}"
 
     def __init__(self, weights=None, alpha_beta=None, dtype: torch.dtype = torch.float32, allow_random_init: bool = False):
-        super().__init__()
-        if dtype not in (torch.float32, torch.float16, torch.bfloat16):
-            raise TypeError(f"DISTS: compute dtype {dtype}")
-        self.compute_dtype = dtype
-        c_in = 3
-        for s, idx in VGG_STAGES.items():
-            convs = {}
-            for i in idx:
-                convs[str(i)] = _Conv(VGG_WIDTH[s], c_in, 3)
-                c_in = VGG_WIDTH[s]
-            setattr(self, f"stage{s}", nn.ModuleDict(convs))
+        super().__init__(dtype)
+        self._add_convs()
         self.alpha = nn.Parameter(torch.empty(1, N_CHANNELS, 1, 1), requires_grad=False)
         self.beta = nn.Parameter(torch.empty(1, N_CHANNELS, 1, 1), requires_grad=False)
-        self._packs: dict = {}
-        self.reset_parameters()
-        if weights is not None:
-            self.load_weights(weights, alpha_beta)
-        elif not allow_random_init:
-            warnings.warn("DISTS(): no weight file given -- the module keeps RANDOM initial weights and its scores mean nothing "
-                          "(pass weights=... / call load_weights, or allow_random_init=True to silence)", stacklevel=2)
+        self._init_weights(weights, allow_random_init, alpha_beta)
 
     def reset_parameters(self, seed: Optional[int] = None):
         """Kaiming-normal convs, small biases, alpha and beta |N(0.1, 0.01)| as the package initialises them"""
         g = None if seed is None else torch.Generator().manual_seed(seed)
         with torch.no_grad():
-            for name in _conv_names():
-                m = self.get_submodule(name)
-                m.weight.copy_(torch.randn(m.weight.shape, generator=g) * math.sqrt(2.0 / (9 * m.weight.shape[1])))
-                m.bias.copy_(torch.randn(m.bias.shape, generator=g) * 0.05)
+            self._reset_convs(g)
             for p in (self.alpha, self.beta):
                 p.copy_((0.1 + 0.01 * torch.randn(p.shape, generator=g)).abs())
         self._packs.clear()
 
-    # ---- weights ---------------------------------------------------------------------------------------------------------------
     def load_weights(self, weights, alpha_beta=None) -> "DISTS":
         """`weights`: a state dict or the path of one (read with `torch.load(weights_only=True)`), either
           * a full `DISTS_pytorch.DISTS().state_dict()` (`stage*`, `alpha`, `beta`; its `mean`, `std` and `stage{2..5}.{4,9,16,23}.filter`
@@ -93,60 +66,18 @@ class DISTS(nn.Module):
           * torchvision's VGG-16 (`features.{idx}.weight|bias`; its `classifier.*` is not part of DISTS and is ignored) together with
             `alpha_beta`: the package's `weights.pt` (`alpha`, `beta`).
         Missing and unexpected keys raise a KeyError that names them."""
-        sd = _read(weights)
-        if any(k.startswith("features.") for k in sd):
-            if alpha_beta is None:
-                raise KeyError("a torchvision VGG-16 state dict holds no `alpha` / `beta`: pass the DISTS_pytorch package's weights.pt as `alpha_beta`")
-            mapped = {}
-            for k, v in sd.items():
-                if k.startswith("classifier."):
-                    continue
-                parts = k.split(".")
-                owner = next((s for s, idx in VGG_STAGES.items() if len(parts) == 3 and parts[1].isdigit() and int(parts[1]) in idx), None)
-                mapped[k if owner is None else f"stage{owner}.{parts[1]}.{parts[2]}"] = v
-            mapped.update(_read(alpha_beta))
-            sd = mapped
-        elif alpha_beta is not None:
-            sd.update(_read(alpha_beta))
-        want = dict(self.state_dict())
-        consts = _constants()
-        missing = sorted(k for k in want if k not in sd)
-        unexpected = sorted(k for k in sd if k not in want and k not in consts)
-        if missing or unexpected:
-            raise KeyError(f"DISTS.load_weights: missing keys {missing}, unexpected keys {unexpected}")
-        for k, v in sd.items():
-            ref = want[k] if k in want else consts[k]
-            if tuple(v.shape) != tuple(ref.shape):
-                raise ValueError(f"DISTS.load_weights: {k} has shape {tuple(v.shape)}, expected {tuple(ref.shape)}")
-        for k in consts.keys() & sd.keys():     # the kernels carry the package's constants: a file that disagrees is another metric
-            if not torch.allclose(sd[k].detach().float().cpu(), consts[k], rtol=0, atol=1e-6):
-                raise ValueError(f"DISTS.load_weights: {k} is not the DISTS_pytorch package's constant (mean / std of ImageNet, the 3x3 Hann filter)")
-        wsum = float(sd["alpha"].detach().double().sum() + sd["beta"].detach().double().sum())
-        if not wsum > 0:
-            raise ValueError(f"DISTS.load_weights: sum(alpha) + sum(beta) = {wsum}; the score divides by it")
-        with torch.no_grad():
-            for k, v in sd.items():
-                if k in want:
-                    want[k].copy_(v.detach().to(torch.float32))
+        sd = self._read_weights(weights, alpha_beta,
+                                "a torchvision VGG-16 state dict holds no `alpha` / `beta`: pass the DISTS_pytorch package's weights.pt as `alpha_beta`")
+
+        def check(read):
+            wsum = float(read["alpha"].detach().double().sum() + read["beta"].detach().double().sum())
+            if not wsum > 0:
+                raise ValueError(f"DISTS.load_weights: sum(alpha) + sum(beta) = {wsum}; the score divides by it")
+
+        load_state(self, sd, constants=_constants(), check=check,
+                   source="the DISTS_pytorch package's constant (mean / std of ImageNet, the 3x3 Hann filter)")
         self._packs.clear()
         return self
-
-    def _apply(self, fn, *args, **kw):
-        self._packs.clear()                     # .to(device) / .float(): the packs follow the parameters
-        return super()._apply(fn, *args, **kw)
-
-    def _packed(self, dtype: torch.dtype):
-        convs = [self.get_submodule(n) for n in _conv_names()]
-        key = (dtype, str(convs[0].weight.device))
-        version = tuple(m.weight._version for m in convs)
-        hit = self._packs.get(key)
-        if hit is None or hit[0] != version:
-            hit = (version, [ops.pack_weight(m.weight, dtype) for m in convs])
-            self._packs[key] = hit
-        return convs, hit[1]
-
-    # ---- forward ---------------------------------------------------------------------------------------------------------------
-    chunk_pairs = staticmethod(LPIPS.chunk_pairs)       # the same largest operand: conv1's output, 2 x pairs x h x w x 64
 
     @torch.no_grad()
     def forward(self, x: torch.Tensor, y: torch.Tensor, require_grad: bool = False, batch_average: bool = False, *,
@@ -158,21 +89,7 @@ class DISTS(nn.Module):
             raise NotImplementedError("DISTS: no backward pass is built (require_grad=True)")
         if batch_average:
             raise NotImplementedError("DISTS: batch_average=True is not built; take .mean() of the per-pair scores")
-        for name, t in (("x", x), ("y", y)):
-            if not t.is_cuda:
-                raise RuntimeError("mv_ldm_amd modules run only on a HIP device (no CPU fallback): move the module and its inputs to 'cuda'")
-            if t.dim() != 4 or t.shape[1] != 3:
-                raise ValueError(f"DISTS: {name} must be [n, 3, h, w], got {tuple(t.shape)}")
-            if t.dtype not in (torch.float32, torch.float16, torch.bfloat16):
-                raise TypeError(f"DISTS: {name} is {t.dtype}; float32, bfloat16 or float16 images are scored")
-            if not t.is_contiguous():
-                raise ValueError(f"DISTS: {name} must be contiguous NCHW (got strides {t.stride()}); call .contiguous() first")
-        if x.shape != y.shape or x.device != y.device:
-            raise ValueError(f"DISTS: x {tuple(x.shape)} on {x.device} against y {tuple(y.shape)} on {y.device}")
-        if self.alpha.device != x.device:
-            raise RuntimeError(f"DISTS: the module is on {self.alpha.device}, the images on {x.device} (no CPU fallback: module.to('cuda'))")
-        x = x if x.dtype == torch.float32 else ops.convert(x, torch.float32)
-        y = y if y.dtype == torch.float32 else ops.convert(y, torch.float32)
+        x, y = self._check_pair(("x", "y"), x, y)
         dtype = self.compute_dtype if dtype is None else dtype
         n, _, h, w = x.shape
         out = torch.empty(n, dtype=torch.float32, device=x.device) if out is None else out
@@ -194,13 +111,8 @@ class DISTS(nn.Module):
             xa, ya = x[i0:i0 + m], y[i0:i0 + m]
             ops.dists_stats(xa, ws, taps[0][3], stride, feat_b=ya)          # tap 0: the raw fp32 images
             f = ops.dists_prep(xa, ya, dtype)
-            k = 0
-            for l, idx in enumerate(VGG_STAGES.values()):
-                for j in range(len(idx)):
-                    f = ops.conv2d(f, packs[k], convs[k].bias)
-                    k += 1
-                    if j + 1 < len(idx):
-                        ops.lpips_relu(f)
+            for l in range(5):
+                f = self._stage(f, l, convs, packs)
                 ops.dists_stats(f, ws, taps[l + 1][3], stride)              # ReLU on load
                 if l < 4:
                     f = ops.dists_l2pool(f)

@@ -728,11 +728,14 @@ def lpips_prep(in0: torch.Tensor, in1: torch.Tensor, dtype: torch.dtype, normali
     return dst
 
 
-def lpips_relu(x: torch.Tensor) -> torch.Tensor:
-    """in-place ReLU of a contiguous conv output"""
+def relu_(x: torch.Tensor) -> torch.Tensor:
+    """in-place ReLU of a contiguous conv output (the C entry keeps the name of its first user, LPIPS)"""
     assert x.is_cuda and x.is_contiguous()
     L.check(L.load().mvldm_lpips_relu(x.data_ptr(), x.numel(), dt(x), stream()))
     return x
+
+
+lpips_relu = relu_
 
 
 def lpips_tap(feat: torch.Tensor, weight: torch.Tensor, ws: torch.Tensor, slot0: int, slots: int, pool: bool = True) -> Optional[torch.Tensor]:

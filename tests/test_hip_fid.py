@@ -238,6 +238,30 @@ def test_accumulate_folds_and_adds_in_a_fixed_order():
     print(f"accumulate: worst rel err {record_err('fid_accumulate/rel', worst):.3e}")
 
 
+def test_accumulate_and_frechet_accumulate_write_the_same_state():
+    """fid_accumulate ends in frechet_accumulate's kernel: the same bits, a second call adds, and no images leave the state alone"""
+    from mv_ldm_amd import ops
+    n, h, w, c = 3, 5, 5, 64                                            # a 2 x 2 pooled map
+    x = torch.randn(n, h, w, c, generator=torch.Generator().manual_seed(11)).cuda()
+    ws = torch.zeros(ops.fid_workspace_bytes(n, h, w, c), dtype=torch.uint8, device="cuda")
+    ops.fid_pool(x, ws)
+    s1 = torch.zeros(ops.FID_STATE, dtype=torch.float64, device="cuda")
+    s2 = torch.zeros(ops.frechet_state_size(c), dtype=torch.float64, device="cuda")
+    f = torch.full((n, c), -7.0, dtype=torch.float64, device="cuda")
+    ops.fid_accumulate(ws, n, h, w, c, state=s1, features=f)
+    once = s1.clone()
+    assert float(once[0]) == n and float(once[1:].abs().max()) > 0 and bool((f >= 0).all())
+    ops.fid_accumulate(ws, n, h, w, c, state=s1, features=f)
+    assert torch.equal(s1, 2 * once) and not torch.equal(s1, once)     # the second call adds: v + v, exact in binary
+    ops.frechet_accumulate(f, s2)
+    assert torch.equal(s2, once)
+    ops.frechet_accumulate(f, s2)
+    assert torch.equal(s1, s2)
+    ops.fid_accumulate(ws, 0, h, w, c, state=s1)
+    ops.frechet_accumulate(f[:0], s2)
+    assert torch.equal(s1, 2 * once) and torch.equal(s2, 2 * once)
+
+
 # ---- the Frechet distance alone -----------------------------------------------------------------------------------------------------
 def _compute(s1, s2):
     from mv_ldm_amd import ops

@@ -46,9 +46,9 @@ for views in (4, 64):
         # the operands of every launch, as update() makes them
         x = ops.fid_prep(sets[0][0], dtype, SIZE, SIZE)
         conv_jobs, flops, edge = [], 0, SIZE
-        for k, (_, c_in, c_out, stride, pad) in enumerate(LAYERS):
-            conv_jobs.append((x, packs[k][0], packs[k][1], stride, pad))
-            x = ops.conv2d(x, packs[k][0], packs[k][1], stride=stride, pad=pad)
+        for layer, c_in, c_out, _, stride, (pad, _) in LAYERS:           # three 3 x 3 kernels with square padding
+            conv_jobs.append((x, *packs[layer], stride, pad))
+            x = ops.conv2d(x, *packs[layer], stride=stride, pad=pad)
             edge = x.shape[1]
             flops += 2 * views * edge * edge * 9 * c_in * c_out
         assert edge == MAP
