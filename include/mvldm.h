@@ -44,7 +44,9 @@ extern "C" {
  *    + mvldm_crop_shim, mvldm_crop_shim_workspace_bytes, mvldm_crop_shim_axis (the dataset readers' crop shim): new symbols only, the
  *    number stays 7.
  *    + mvldm_crop_shim_flip (the crop shim with a per-image mirrored read, for the training loader's augmentation shim): new symbol only,
- *    the number stays 7. */
+ *    the number stays 7.
+ *    + mvldm_jpeg_probe / _entropy / _coef_count / _workspace_bytes / _decode / _idct_host (baseline JPEG frames: entropy decoding on the
+ *    host, dequantisation, inverse DCT, upsampling and colour on the device): new symbols and enums only, the number stays 7. */
 #define MVLDM_ABI_VERSION 7
 
 typedef void* mvldm_stream_t; /* hipStream_t */
@@ -745,6 +747,77 @@ int mvldm_crop_shim_flip(const void* src, int src_u8, float* dst, int n_img, int
                          const uint8_t* flip /* device, n_img bytes; NULL: none */, void* workspace, size_t workspace_bytes,
                          int* scaled_hw /* host [2], may be NULL */, mvldm_stream_t stream);
 int mvldm_crop_shim_axis(int n_in, int n_out, int offset, int count, int32_t* bounds /* host */, int32_t* coefs /* host */, int coefs_len);
+
+/* ------------------------------------------------------------------------------------------------
+ * JPEG frames: what `Image.open(BytesIO(frame)).convert("RGB")` gives for the dataset's frames (src/dataset/dataset_re10k.py:157-169,
+ * `convert_images`), bit for bit with Pillow on libjpeg / libjpeg-turbo (ISLOW inverse DCT, fancy upsampling: the library's defaults).
+ * The serial half -- markers and the Huffman-coded scan -- runs on the host, without Pillow, into a buffer the caller owns; the
+ * parallel half -- dequantise, inverse DCT, chroma upsampling, colour conversion: integer and exactly specified -- runs on the device.
+ *   streams   baseline sequential (SOF0), Huffman coded, 8-bit samples, 8-bit quantisation tables, ONE scan that interleaves every
+ *             component, restart intervals (DRI / RSTn) included; 1 component (sampling 1 x 1), or 3 components that libjpeg reads
+ *             as YCbCr (a JFIF APP0, or ids 1, 2, 3 and no Adobe APP14) with luma sampling 1 x 1, 2 x 1 or 2 x 2 and 1 x 1 chroma:
+ *             MVLDM_JPEG_GRAY / _444 / _422 / _420.  Anything else is refused with a MVLDM_JPEG_* reason (> 0): the caller decodes that
+ *             frame some other way (mv_ldm_amd: through Pillow).  No read leaves data[0 .. len); every loop over the stream is
+ *             bounded by len.
+ *   layout    mcux = ceil(w / (8 hmax)), mcuy = ceil(h / (8 vmax)); component c has a grid of bh_c x bw_c = (mcuy v_c) x (mcux h_c)
+ *             blocks (MCU-padded) and cw_c x ch_c = ceil(w h_c / hmax) x ceil(h v_c / vmax) real samples.  coef: int16, per frame the
+ *             components one after another, per component the blocks row-major over its grid, per block the 64 QUANTISED
+ *             coefficients in natural (row-major, de-zigzagged) order: mvldm_jpeg_coef_count values (0 for a refused shape).
+ *             qt: uint16 [3][64] per frame, the table of component c in natural order (unused ones zero).
+ *   guard     S = sum_k |coef_k qt_k| of a block.  A frame with a block above B = 5905 is refused (MVLDM_JPEG_RANGE): only below it do
+ *             libjpeg's 64-bit C code, libjpeg-turbo's 16-bit SIMD code and an int32 kernel agree.  Derivation: csrc/jpeg_common.h.
+ *   idct      value = coef qt in int32; jidctint.c: CONST_BITS 13, PASS1_BITS 2, columns first with DESCALE(., 11), then rows with
+ *             DESCALE(., 18), DESCALE(x, n) = (x + (1 << (n - 1))) >> n (arithmetic); even part z1 = (in2 + in6) 4433, tmp2 = z1 - in6
+ *             15137, tmp3 = z1 + in2 6270, tmp0 / tmp1 = (in0 +- in4) << 13; odd part on in7, in5, in3, in1 with z5 = (z3 + z4) 9633 and
+ *             the constants 2446, 16819, 25172, 12299, -7373, -20995, -16069, -3196; sample = clip(x + 128, 0, 255).
+ *   upsample  jdsample.c's fancy upsampling on the component's REAL size (the row above the first is the first, the row below the last
+ *             real row is the last real row).  h2v1: out[2i] = (3 in[i] + in[i-1] + 1) >> 2, out[2i+1] = (3 in[i] + in[i+1] + 2) >> 2,
+ *             out[0] = in[0], the last odd output is in[last].  h2v2: s[i] = 3 near[i] + far[i] (far: the row above for an even
+ *             output row, below for an odd one); out[2i] = (3 s[i] + s[i-1] + 8) >> 4, out[2i+1] = (3 s[i] + s[i+1] + 7) >> 4, the
+ *             first (4 s[0] + 8) >> 4, the last (4 s[last] + 7) >> 4.  A component of one or two samples per row is replicated
+ *             instead, as libjpeg does (jinit_upsampler: the filters need downsampled_width > 2).
+ *   colour    cb, cr centred by -128: R = y + ((91881 cr + 32768) >> 16), G = y + ((-22554 cb - 46802 cr + 32768) >> 16),
+ *             B = y + ((116130 cb + 32768) >> 16), each clipped to [0, 255]; grayscale writes y three times.
+ *   dst       uint8 [n_img][h][w][3]: what mvldm_crop_shim takes with src_u8 = 1.
+ * mvldm_jpeg_probe (host) reads the markers up to the scan: info[0..7] = h, w, sampling (MVLDM_JPEG_GRAY ...), reason, blocks of
+ * component 0, blocks of each chroma component, mcux, mcuy.  h and w are set as soon as a frame header was read (0 otherwise), the
+ * rest only for a supported stream.  Returns the reason: 0 supported, > 0 a MVLDM_JPEG_* reason, MVLDM_ERR_ARG for a null pointer.
+ * mvldm_jpeg_entropy (host) decodes the scan into coef (room for coef_len values; a supported frame that needs more is MVLDM_ERR_ARG and
+ * nothing is written) and qt; max_s (may be NULL) receives the largest S of the blocks decoded.  Returns like the probe, with
+ * MVLDM_JPEG_RANGE for a frame outside the guard.  After a refusal the contents of coef and qt are unspecified, but nothing outside
+ * coef[0 .. coef_len) and qt[0 .. 192) is ever written.  Both keep no state and may run on many threads at once.
+ * mvldm_jpeg_decode (device) turns n_img frames of ONE (h, w, sampling) into pixels: jpeg_idct_kernel (every block of every component
+ * of every frame -> uint8 planes in the workspace, 64 bytes per block: mvldm_jpeg_workspace_bytes), then jpeg_color_kernel.  Two
+ * launches, no allocation, nothing read back; may be captured.  coef [n_img][coef_count], qt [n_img][3][64], dst, workspace: device
+ * pointers, 4-byte aligned; a null or misaligned pointer, a short workspace or a refused shape is MVLDM_ERR_ARG.  It trusts the
+ * coefficients: values outside the guard give wrapped int32 arithmetic, never an access outside the buffers.
+ * mvldm_jpeg_idct_host (host) is the same arithmetic (the same inline functions) for one frame in plain C++: what the CPU tests pin to
+ * Pillow and a sanitizer build exercises.  Edges up to 16384. */
+enum { MVLDM_JPEG_GRAY = 0, MVLDM_JPEG_444 = 1, MVLDM_JPEG_422 = 2, MVLDM_JPEG_420 = 3 };
+enum {
+    MVLDM_JPEG_OK = 0,
+    MVLDM_JPEG_NOT_JPEG = 1,    /* no SOI at the start */
+    MVLDM_JPEG_TRUNCATED = 2,   /* the stream ends inside a marker segment or inside the scan */
+    MVLDM_JPEG_CORRUPT = 3,     /* a segment, a Huffman table, a code, a coefficient index or a restart marker that cannot be */
+    MVLDM_JPEG_PROGRESSIVE = 4, /* SOF2 */
+    MVLDM_JPEG_CODING = 5,      /* any other frame type: extended, lossless, hierarchical, arithmetic coding */
+    MVLDM_JPEG_PRECISION = 6,   /* samples or quantisation tables that are not 8-bit */
+    MVLDM_JPEG_COMPONENTS = 7,  /* neither 1 nor 3 components */
+    MVLDM_JPEG_SAMPLING = 8,    /* sampling factors outside the four layouts */
+    MVLDM_JPEG_COLORSPACE = 9,  /* 3 components libjpeg would not read as YCbCr */
+    MVLDM_JPEG_SCANS = 10,      /* a scan that does not hold every component */
+    MVLDM_JPEG_SIZE = 11,       /* an edge of 0 or above 16384 */
+    MVLDM_JPEG_RANGE = 12       /* a block outside the range guard */
+};
+int mvldm_jpeg_probe(const uint8_t* data /* host */, size_t len, int32_t* info /* host [8] */);
+size_t mvldm_jpeg_coef_count(int h, int w, int sampling);
+int mvldm_jpeg_entropy(const uint8_t* data /* host */, size_t len, int16_t* coef /* host */, size_t coef_len, uint16_t* qt /* host [192] */,
+                       int32_t* max_s /* host, may be NULL */);
+size_t mvldm_jpeg_workspace_bytes(int n_img, int h, int w, int sampling);
+int mvldm_jpeg_decode(const int16_t* coef, const uint16_t* qt, uint8_t* dst, int n_img, int h, int w, int sampling, void* workspace,
+                      size_t workspace_bytes, mvldm_stream_t stream);
+int mvldm_jpeg_idct_host(const int16_t* coef /* host */, const uint16_t* qt /* host [192] */, uint8_t* dst /* host [h][w][3] */, int h, int w,
+                         int sampling);
 
 /* ------------------------------------------------------------------------------------------------
  * Plans: a whole forward (UNet walk, VAE decoder, DDIM step) as a flat list of the ops above with

@@ -18,6 +18,10 @@ RAYS_RAW, RAYS_POSITIONAL, RAYS_SRT = 0, 1, 2
 ELT_COPY, ELT_SILU, ELT_GELU = 0, 1, 2
 NORM_BWD_STORE = 0x100          # include/mvldm.h MVLDM_NORM_BWD_STORE: norm backward writes (=) dgamma / dbeta instead of +=
 GN_MAX_CHUNKS = 32
+JPEG_GRAY, JPEG_444, JPEG_422, JPEG_420 = 0, 1, 2, 3            # include/mvldm.h MVLDM_JPEG_*: sampling layouts
+JPEG_REASONS = ("ok", "not a JPEG", "truncated", "corrupt", "progressive", "frame type", "precision", "components", "sampling", "colour space",
+                "scans", "size", "range guard")                 # MVLDM_JPEG_OK .. MVLDM_JPEG_RANGE, by value
+JPEG_RANGE = 12
 
 (OP_IGEMM, OP_GROUPNORM, OP_LAYERNORM, OP_ATTENTION, OP_TIMESTEP_EMBED, OP_ELTWISE, OP_DDIM_STEP, OP_DDIM_ADVANCE,
  OP_NCHW_TO_NHWC, OP_NHWC_TO_NCHW, OP_MEMCPY, OP_RAY_ENCODE, OP_POSTERIOR_SAMPLE,
@@ -261,6 +265,12 @@ SIGNATURES = {
     "mvldm_crop_shim": (C.c_int, [vp, C.c_int, vp] + [C.c_int] * 5 + [vp, sz, C.POINTER(C.c_int), vp]),
     "mvldm_crop_shim_flip": (C.c_int, [vp, C.c_int, vp] + [C.c_int] * 5 + [vp, vp, sz, C.POINTER(C.c_int), vp]),
     "mvldm_crop_shim_axis": (C.c_int, [C.c_int] * 4 + [C.POINTER(i32), C.POINTER(i32), C.c_int]),
+    "mvldm_jpeg_probe": (C.c_int, [vp, sz, C.POINTER(i32)]),
+    "mvldm_jpeg_coef_count": (sz, [C.c_int] * 3),
+    "mvldm_jpeg_entropy": (C.c_int, [vp, sz, vp, sz, vp, C.POINTER(i32)]),
+    "mvldm_jpeg_workspace_bytes": (sz, [C.c_int] * 4),
+    "mvldm_jpeg_decode": (C.c_int, [vp, vp, vp] + [C.c_int] * 4 + [vp, sz, vp]),
+    "mvldm_jpeg_idct_host": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int]),
     "mvldm_nchw_to_nhwc": (C.c_int, [vp, vp] + [C.c_int] * 6 + [f32, f32, vp, vp]),
     "mvldm_ray_channels": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "mvldm_ray_encode": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp] + [C.c_int] * 4 + [vp]),

@@ -1,0 +1,407 @@
+// The host half of the JPEG decoder (include/mvldm.h, "JPEG frames"): the marker parser, the Huffman decoder of a baseline scan and the
+// plain C++ restatement of the device half.  No HIP call, no global or static state: every table lives in the caller's frame, so any
+// number of threads may decode at once.  Every read of the stream goes through an index checked against `len`.
+#include <string.h>
+
+#include "jpeg_common.h"
+
+namespace mvldm {
+
+int set_error(int code, const char* fmt, ...);      // api.cpp (thread-local text)
+
+namespace {
+
+const uint8_t kZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
+                             41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
+                             30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+
+struct Huff {                   // one DHT table: canonical codes by length, and the codes of up to kLook bits by direct lookup
+    static constexpr int kLook = 9;
+    bool defined = false;
+    uint8_t vals[256];
+    int32_t maxcode[18];        // largest code of length l, -1 if none; [17] a sentinel above every 16-bit code
+    int32_t valoff[17];         // vals index of the first code of length l, minus that code
+    uint16_t look[1 << kLook];  // (length << 8) | symbol, 0 for a longer code
+};
+
+// DHT payload at p[0 .. n): counts[16], symbols.  false: the counts do not describe a prefix code
+bool huff_build(Huff* t, const uint8_t* counts, const uint8_t* syms, int nsyms) {
+    memset(t->look, 0, sizeof(t->look));
+    memcpy(t->vals, syms, (size_t)nsyms);
+    int32_t code = 0;
+    int k = 0;
+    for (int l = 1; l <= 16; ++l) {
+        const int n = counts[l - 1];
+        t->valoff[l] = k - code;
+        if (n) {
+            if (code + n > (1 << l)) return false;
+            for (int i = 0; i < n; ++i, ++k, ++code)
+                if (l <= Huff::kLook) {
+                    const int first = code << (Huff::kLook - l);
+                    for (int j = 0; j < (1 << (Huff::kLook - l)); ++j) t->look[first + j] = (uint16_t)((l << 8) | t->vals[k]);
+                }
+            t->maxcode[l] = code - 1;
+        } else {
+            t->maxcode[l] = -1;
+        }
+        code <<= 1;
+    }
+    t->maxcode[17] = 0x7FFFFFFF;
+    t->defined = true;
+    return true;
+}
+
+struct Component {
+    int id, hs, vs, tq, td, ta;
+};
+
+struct Header {                 // what the markers in front of the scan say
+    int h = 0, w = 0, sampling = -1, ncomp = 0;
+    Component comp[3];
+    uint16_t qt[4][64];         // natural order
+    bool qt_defined[4] = {false, false, false, false};
+    Huff dc[4], ac[4];
+    int restart = 0;            // MCUs per restart interval, 0: none
+    bool jfif = false, adobe = false;
+    size_t scan = 0;            // index of the first byte of entropy-coded data
+};
+
+inline int be16(const uint8_t* p) { return (p[0] << 8) | p[1]; }
+
+// Walks the markers from SOI to the first SOS.  Returns a MVLDM_JPEG_* reason; hd->h / w are set once a frame header was read.
+int parse_header(const uint8_t* d, size_t len, Header* hd) {
+    if (len < 2 || d[0] != 0xFF || d[1] != 0xD8) return MVLDM_JPEG_NOT_JPEG;
+    size_t pos = 2;
+    bool sof = false;
+    int reason = MVLDM_JPEG_OK;                 // the first thing that makes the frame unsupported; parsing goes on to the size
+    auto refuse = [&](int r) {
+        if (reason == MVLDM_JPEG_OK) reason = r;
+    };
+    while (true) {
+        // a marker: 0xFF, any number of fill 0xFF, the code
+        if (pos >= len) return MVLDM_JPEG_TRUNCATED;
+        if (d[pos] != 0xFF) return MVLDM_JPEG_CORRUPT;
+        while (pos < len && d[pos] == 0xFF) ++pos;
+        if (pos >= len) return MVLDM_JPEG_TRUNCATED;
+        const int m = d[pos++];
+        if (m == 0x00 || m == 0xD8 || (m >= 0xD0 && m <= 0xD7)) return MVLDM_JPEG_CORRUPT;
+        if (m == 0xD9) return MVLDM_JPEG_TRUNCATED;     // EOI before any scan
+        if (m == 0x01) continue;                        // TEM: no payload
+        if (len - pos < 2) return MVLDM_JPEG_TRUNCATED;
+        const size_t seg = (size_t)be16(d + pos);
+        if (seg < 2) return MVLDM_JPEG_CORRUPT;
+        if (len - pos < seg) return MVLDM_JPEG_TRUNCATED;
+        const uint8_t* p = d + pos + 2;
+        const size_t n = seg - 2;
+        pos += seg;
+        if (m == 0xE0) {
+            if (n >= 5 && memcmp(p, "JFIF", 5) == 0) hd->jfif = true;
+        } else if (m == 0xEE) {
+            if (n >= 12 && memcmp(p, "Adobe", 5) == 0) hd->adobe = true;
+        } else if (m == 0xDB) {                 // DQT: any number of tables
+            size_t at = 0;
+            while (at < n) {
+                const int pq = p[at] >> 4, tq = p[at] & 15;
+                if (tq > 3 || pq > 1) return MVLDM_JPEG_CORRUPT;
+                const size_t need = 1 + (pq ? 128 : 64);
+                if (n - at < need) return MVLDM_JPEG_CORRUPT;
+                if (pq) {
+                    refuse(MVLDM_JPEG_PRECISION);
+                } else {
+                    for (int k = 0; k < 64; ++k) hd->qt[tq][kZigzag[k]] = p[at + 1 + k];
+                    hd->qt_defined[tq] = true;
+                }
+                at += need;
+            }
+        } else if (m == 0xC4) {                 // DHT: any number of tables
+            size_t at = 0;
+            while (at < n) {
+                if (n - at < 17) return MVLDM_JPEG_CORRUPT;
+                const int tc = p[at] >> 4, th = p[at] & 15;
+                if (tc > 1 || th > 3) return MVLDM_JPEG_CORRUPT;
+                int total = 0;
+                for (int l = 0; l < 16; ++l) total += p[at + 1 + l];
+                if (total > 256 || n - at - 17 < (size_t)total) return MVLDM_JPEG_CORRUPT;
+                if (!huff_build(tc ? &hd->ac[th] : &hd->dc[th], p + at + 1, p + at + 17, total)) return MVLDM_JPEG_CORRUPT;
+                at += 17 + (size_t)total;
+            }
+        } else if (m == 0xDD) {                 // DRI
+            if (n != 2) return MVLDM_JPEG_CORRUPT;
+            hd->restart = be16(p);
+        } else if (m >= 0xC0 && m <= 0xCF && m != 0xC8 && m != 0xCC) {      // a frame header
+            if (sof) return MVLDM_JPEG_CORRUPT;
+            sof = true;
+            if (n < 6) return MVLDM_JPEG_CORRUPT;
+            hd->h = be16(p + 1);
+            hd->w = be16(p + 3);
+            hd->ncomp = p[5];
+            if (n != 6 + 3 * (size_t)hd->ncomp) return MVLDM_JPEG_CORRUPT;
+            if (m == 0xC2) refuse(MVLDM_JPEG_PROGRESSIVE);
+            else if (m != 0xC0) refuse(MVLDM_JPEG_CODING);
+            if (p[0] != 8) refuse(MVLDM_JPEG_PRECISION);
+            if (hd->h < 1 || hd->w < 1 || hd->h > kJpegMaxDim || hd->w > kJpegMaxDim) refuse(MVLDM_JPEG_SIZE);
+            if (hd->ncomp != 1 && hd->ncomp != 3) {
+                refuse(MVLDM_JPEG_COMPONENTS);
+            } else {
+                for (int c = 0; c < hd->ncomp; ++c) {
+                    const uint8_t* q = p + 6 + 3 * c;
+                    hd->comp[c] = Component{q[0], q[1] >> 4, q[1] & 15, q[2], 0, 0};
+                    if (q[2] > 3) return MVLDM_JPEG_CORRUPT;
+                }
+                const Component* cc = hd->comp;
+                if (hd->ncomp == 1) {
+                    if (cc[0].hs == 1 && cc[0].vs == 1) hd->sampling = MVLDM_JPEG_GRAY;
+                } else if (cc[1].hs == 1 && cc[1].vs == 1 && cc[2].hs == 1 && cc[2].vs == 1) {
+                    if (cc[0].hs == 1 && cc[0].vs == 1) hd->sampling = MVLDM_JPEG_444;
+                    if (cc[0].hs == 2 && cc[0].vs == 1) hd->sampling = MVLDM_JPEG_422;
+                    if (cc[0].hs == 2 && cc[0].vs == 2) hd->sampling = MVLDM_JPEG_420;
+                }
+                if (hd->sampling < 0) refuse(MVLDM_JPEG_SAMPLING);
+            }
+        } else if (m == 0xDA) {                 // SOS
+            if (!sof) return MVLDM_JPEG_CORRUPT;
+            if (reason != MVLDM_JPEG_OK) return reason;
+            if (n < 1) return MVLDM_JPEG_CORRUPT;
+            const int ns = p[0];
+            if (ns < 1 || ns > 4 || n != 4 + 2 * (size_t)ns) return MVLDM_JPEG_CORRUPT;
+            if (ns != hd->ncomp) return MVLDM_JPEG_SCANS;
+            for (int c = 0; c < ns; ++c) {      // in the frame's order, as an interleaved scan must list them
+                if (p[1 + 2 * c] != hd->comp[c].id) return MVLDM_JPEG_SCANS;
+                hd->comp[c].td = p[2 + 2 * c] >> 4;
+                hd->comp[c].ta = p[2 + 2 * c] & 15;
+                if (hd->comp[c].td > 3 || hd->comp[c].ta > 3) return MVLDM_JPEG_CORRUPT;
+                if (!hd->dc[hd->comp[c].td].defined || !hd->ac[hd->comp[c].ta].defined || !hd->qt_defined[hd->comp[c].tq]) return MVLDM_JPEG_CORRUPT;
+            }
+            if (p[1 + 2 * ns] != 0 || p[2 + 2 * ns] != 63 || p[3 + 2 * ns] != 0) return MVLDM_JPEG_CORRUPT;      // Ss, Se, Ah / Al of a sequential scan
+            if (hd->ncomp == 3 && !hd->jfif) {  // jdapimin.c default_decompress_parms
+                if (hd->adobe) return MVLDM_JPEG_COLORSPACE;
+                if (hd->comp[0].id != 1 || hd->comp[1].id != 2 || hd->comp[2].id != 3) return MVLDM_JPEG_COLORSPACE;
+            }
+            hd->scan = pos;
+            return MVLDM_JPEG_OK;
+        }
+        // APPn, COM and anything else with a length: skipped
+    }
+}
+
+struct Bits {                   // the scan's bit stream: byte stuffing removed, stops in front of a marker
+    const uint8_t* d;
+    size_t pos, len;
+    uint64_t acc = 0;           // the low `n` bits are the unread bits, oldest highest
+    int n = 0;
+    bool stop = false;          // a marker or the end of the data lies at pos
+    void fill() {
+        while (n <= 56 && !stop) {
+            if (pos >= len) {
+                stop = true;
+                break;
+            }
+            const uint8_t b = d[pos];
+            if (b == 0xFF) {
+                if (pos + 1 >= len) {           // the data ends inside a stuffed pair or a marker
+                    pos = len;
+                    stop = true;
+                    break;
+                }
+                if (d[pos + 1] != 0x00) {       // a marker: stay in front of it
+                    stop = true;
+                    break;
+                }
+                pos += 2;
+            } else {
+                ++pos;
+            }
+            acc = (acc << 8) | b;
+            n += 8;
+        }
+    }
+    // the next k <= 16 bits, zero-padded past the end, not consumed
+    int peek(int k) {
+        if (n < k) fill();
+        return n >= k ? (int)((acc >> (n - k)) & ((1u << k) - 1)) : (int)((acc << (k - n)) & ((1u << k) - 1));
+    }
+    bool skip(int k) {
+        if (k > n) return false;
+        n -= k;
+        return true;
+    }
+};
+
+// one Huffman symbol, or -1 (a code that does not exist, or the data ran out)
+inline int huff_decode(Bits* b, const Huff& t) {
+    const int v = b->peek(16);
+    const int e = t.look[v >> (16 - Huff::kLook)];
+    if (e) return b->skip(e >> 8) ? (e & 255) : -1;
+    for (int l = Huff::kLook + 1; l <= 16; ++l) {
+        const int code = v >> (16 - l);
+        if (code <= t.maxcode[l]) return b->skip(l) ? t.vals[(code + t.valoff[l]) & 255] : -1;
+    }
+    return -1;
+}
+// s >= 1 magnitude bits, sign-extended as in F.2.2.1; false when the data ran out
+inline bool receive_extend(Bits* b, int s, int* out) {
+    const int v = b->peek(s);
+    if (!b->skip(s)) return false;
+    *out = v < (1 << (s - 1)) ? v - (1 << s) + 1 : v;
+    return true;
+}
+
+// The scan.  coef: room for L.blocks * 64 values (checked by the caller).  Returns a reason.
+int decode_scan(const uint8_t* d, size_t len, const Header& hd, const JpegLayout& L, int16_t* coef, int32_t* max_s) {
+    Bits b{d, hd.scan, len};
+    int pred[3] = {0, 0, 0};
+    int32_t worst = 0;
+    const int mcus = L.mcux * L.mcuy;
+    int next_rst = 0, until_rst = hd.restart;
+    memset(coef, 0, (size_t)L.blocks * 64 * sizeof(int16_t));
+    for (int m = 0; m < mcus; ++m) {
+        if (hd.restart && until_rst == 0) {     // byte-align, RSTn, predictors back to 0
+            b.fill();
+            if (!b.stop || b.n >= 8) return MVLDM_JPEG_CORRUPT;
+            size_t p = b.pos;
+            if (p >= len) return MVLDM_JPEG_TRUNCATED;
+            while (p < len && d[p] == 0xFF) ++p;
+            if (p >= len) return MVLDM_JPEG_TRUNCATED;
+            if (d[p] != 0xD0 + next_rst) return d[p] == 0xD9 ? MVLDM_JPEG_TRUNCATED : MVLDM_JPEG_CORRUPT;
+            b.pos = p + 1;
+            b.acc = 0;
+            b.n = 0;
+            b.stop = false;
+            next_rst = (next_rst + 1) & 7;
+            until_rst = hd.restart;
+            pred[0] = pred[1] = pred[2] = 0;
+        }
+        --until_rst;
+        const int my = m / L.mcux, mx = m % L.mcux;
+        for (int c = 0; c < L.ncomp; ++c) {
+            const int hs = c == 0 ? L.hmax : 1, vs = c == 0 ? L.vmax : 1;
+            const Huff& dc = hd.dc[hd.comp[c].td];
+            const Huff& ac = hd.ac[hd.comp[c].ta];
+            const uint16_t* q = hd.qt[hd.comp[c].tq];
+            for (int by = 0; by < vs; ++by)
+                for (int bx = 0; bx < hs; ++bx) {
+                    int16_t* blk = coef + ((size_t)L.off[c] + (size_t)(my * vs + by) * L.bw[c] + (mx * hs + bx)) * 64;
+                    int s = huff_decode(&b, dc);
+                    if (s < 0) return b.stop && b.pos >= len ? MVLDM_JPEG_TRUNCATED : MVLDM_JPEG_CORRUPT;
+                    if (s > 15) return MVLDM_JPEG_CORRUPT;
+                    int diff = 0;
+                    if (s && !receive_extend(&b, s, &diff)) return b.pos >= len ? MVLDM_JPEG_TRUNCATED : MVLDM_JPEG_CORRUPT;
+                    pred[c] += diff;
+                    if (pred[c] < -32768 || pred[c] > 32767) return MVLDM_JPEG_CORRUPT;
+                    blk[0] = (int16_t)pred[c];
+                    int32_t sum = (pred[c] < 0 ? -pred[c] : pred[c]) * (int32_t)q[0];
+                    for (int k = 1; k < 64; ++k) {
+                        const int rs = huff_decode(&b, ac);
+                        if (rs < 0) return b.stop && b.pos >= len ? MVLDM_JPEG_TRUNCATED : MVLDM_JPEG_CORRUPT;
+                        const int r = rs >> 4;
+                        s = rs & 15;
+                        if (s == 0) {
+                            if (r != 15) break;             // EOB
+                            k += 15;                        // ZRL
+                            continue;
+                        }
+                        k += r;
+                        if (k > 63) return MVLDM_JPEG_CORRUPT;
+                        int v = 0;
+                        if (!receive_extend(&b, s, &v)) return b.pos >= len ? MVLDM_JPEG_TRUNCATED : MVLDM_JPEG_CORRUPT;
+                        const int nat = kZigzag[k];
+                        blk[nat] = (int16_t)v;              // |v| < 2^15
+                        sum += (v < 0 ? -v : v) * (int32_t)q[nat];     // <= 64 * 32767 * 255 < 2^31
+                    }
+                    if (sum > worst) worst = sum;
+                }
+        }
+    }
+    // what follows the last MCU: padding bits, then EOI
+    b.fill();
+    if (!b.stop || b.n >= 8) return MVLDM_JPEG_CORRUPT;
+    size_t p = b.pos;
+    while (p < len && d[p] == 0xFF) ++p;
+    if (p >= len) return MVLDM_JPEG_TRUNCATED;
+    if (p == b.pos || d[p] != 0xD9) return MVLDM_JPEG_CORRUPT;      // more scans, tables or restart markers than the frame has MCUs for
+    if (max_s) *max_s = worst;
+    return worst > kJpegGuard ? MVLDM_JPEG_RANGE : MVLDM_JPEG_OK;
+}
+
+}  // namespace
+
+size_t jpeg_coef_count(int h, int w, int sampling) {
+    JpegLayout L;
+    return jpeg_layout(h, w, sampling, &L) ? (size_t)L.blocks * 64 : 0;
+}
+
+}  // namespace mvldm
+
+using namespace mvldm;
+
+extern "C" int mvldm_jpeg_probe(const uint8_t* data, size_t len, int32_t* info) {
+    if (data == nullptr || info == nullptr) return set_error(MVLDM_ERR_ARG, "jpeg_probe: null pointer");
+    Header hd;
+    const int reason = parse_header(data, len, &hd);
+    for (int i = 0; i < 8; ++i) info[i] = 0;
+    info[0] = hd.h;
+    info[1] = hd.w;
+    info[2] = -1;
+    info[3] = reason;
+    JpegLayout L;
+    if (reason == MVLDM_JPEG_OK && jpeg_layout(hd.h, hd.w, hd.sampling, &L)) {
+        info[2] = hd.sampling;
+        info[4] = L.bw[0] * L.bh[0];
+        info[5] = L.bw[1] * L.bh[1];
+        info[6] = L.mcux;
+        info[7] = L.mcuy;
+    }
+    return reason;
+}
+
+extern "C" size_t mvldm_jpeg_coef_count(int h, int w, int sampling) { return jpeg_coef_count(h, w, sampling); }
+
+extern "C" int mvldm_jpeg_entropy(const uint8_t* data, size_t len, int16_t* coef, size_t coef_len, uint16_t* qt, int32_t* max_s) {
+    if (data == nullptr || coef == nullptr || qt == nullptr) return set_error(MVLDM_ERR_ARG, "jpeg_entropy: null pointer");
+    if (max_s) *max_s = 0;
+    Header hd;
+    const int reason = parse_header(data, len, &hd);
+    if (reason != MVLDM_JPEG_OK) return reason;
+    JpegLayout L;
+    if (!jpeg_layout(hd.h, hd.w, hd.sampling, &L)) return MVLDM_JPEG_SIZE;
+    if (coef_len < (size_t)L.blocks * 64)
+        return set_error(MVLDM_ERR_ARG, "jpeg_entropy: room for %zu coefficients, the %d x %d frame has %zu", coef_len, hd.h, hd.w, (size_t)L.blocks * 64);
+    for (int c = 0; c < 3; ++c)
+        for (int k = 0; k < 64; ++k) qt[c * 64 + k] = c < L.ncomp ? hd.qt[hd.comp[c].tq][k] : 0;
+    return decode_scan(data, len, hd, L, coef, max_s);
+}
+
+extern "C" int mvldm_jpeg_idct_host(const int16_t* coef, const uint16_t* qt, uint8_t* dst, int h, int w, int sampling) {
+    if (coef == nullptr || qt == nullptr || dst == nullptr) return set_error(MVLDM_ERR_ARG, "jpeg_idct_host: null pointer");
+    JpegLayout L;
+    if (!jpeg_layout(h, w, sampling, &L)) return set_error(MVLDM_ERR_ARG, "jpeg_idct_host: frame %d x %d, sampling %d", h, w, sampling);
+    uint8_t* planes = new uint8_t[(size_t)L.blocks * 64];
+    for (int c = 0; c < L.ncomp; ++c) {
+        const int ld = L.bw[c] * 8;
+        uint8_t* plane = planes + (size_t)L.off[c] * 64;
+        for (int by = 0; by < L.bh[c]; ++by)
+            for (int bx = 0; bx < L.bw[c]; ++bx) {
+                const int16_t* blk = coef + ((size_t)L.off[c] + (size_t)by * L.bw[c] + bx) * 64;
+                int32_t ws[8][8], v[8];
+                for (int x = 0; x < 8; ++x) {           // columns
+                    for (int k = 0; k < 8; ++k) v[k] = (int32_t)blk[k * 8 + x] * (int32_t)qt[c * 64 + k * 8 + x];
+                    jpeg_idct_1d(v, 11);
+                    for (int k = 0; k < 8; ++k) ws[k][x] = v[k];
+                }
+                for (int y = 0; y < 8; ++y) {           // rows
+                    jpeg_idct_1d(ws[y], 18);
+                    for (int x = 0; x < 8; ++x) plane[(size_t)(by * 8 + y) * ld + bx * 8 + x] = (uint8_t)jpeg_sample(ws[y][x]);
+                }
+            }
+    }
+    for (int y = 0; y < h; ++y)
+        for (int x = 0; x < w; ++x) {
+            const uint32_t px = jpeg_pixel(planes, L, y, x);
+            uint8_t* o = dst + ((size_t)y * w + x) * 3;
+            o[0] = (uint8_t)px;
+            o[1] = (uint8_t)(px >> 8);
+            o[2] = (uint8_t)(px >> 16);
+        }
+    delete[] planes;
+    return MVLDM_OK;
+}

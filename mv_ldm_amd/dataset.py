@@ -5,8 +5,10 @@ and the `evaluation` view sampler (`src/dataset/view_sampler/view_sampler_evalua
     for example in scenes: ...          # the dict `generate.synthetic_example` returns, with target["image"]
 
 The images take the reference's path bit for bit -- 8-bit decode, PIL's LANCZOS resize of the 8-bit image, centre crop, / 255 -- but the
-resize, crop and division run on the device (`ops.crop_shim`, csrc/cropshim.hip); only the container decode (JPEG through Pillow, PNG
-through `image_io`) stays on the host.  Cameras follow the reference's host arithmetic.  `rescale_and_crop`, `apply_crop_shim_to_views`
+resize, crop and division run on the device (`ops.crop_shim`, csrc/cropshim.hip).  The container decode (JPEG through Pillow, PNG
+through `image_io`) runs on the host by default; with `device_decode=True` a JPEG frame's Huffman scan is decoded by the library's own
+host code and everything after it -- dequantisation, inverse DCT, upsampling, colour -- on the device (`ops.jpeg_decode`, csrc/jpeg.hip),
+bit for bit with Pillow, so no decoded frame exists on the host.  Cameras follow the reference's host arithmetic.  `rescale_and_crop`, `apply_crop_shim_to_views`
 and `apply_crop_shim` are drop-ins for a loader that already produces the reference's `BatchedExample` dicts.
 
 Training reads the same chunks through `RE10KTrainLoader`, `DatasetRE10k.__iter__` for `stage = "train" | "val"`: shuffled chunks and
@@ -22,7 +24,7 @@ reversed (`ops.crop_shim(flip=)`), so a whole micro-batch of mirrored and unmirr
 `apply_augmentation_and_crop_shim` is the drop-in for the reference's `apply_augmentation_shim` followed by `apply_crop_shim`.
 
 Out of scope: the `all` / `random` view samplers, the random-transform shim (`random_transform_extrinsics`, off in the released config: it
-needs an SO(3) sampler), the re10kv2 / CO3D / Objaverse readers, JPEG decoding on the device, Lightning's DataModule."""
+needs an SO(3) sampler), the re10kv2 / CO3D / Objaverse readers, entropy decoding of JPEG on the device, Lightning's DataModule."""
 from __future__ import annotations
 
 import json
@@ -142,12 +144,16 @@ class RE10KScenes:
     an entry whose frames disagree in size or are smaller than `image_shape` -- any size from `image_shape` up is taken, not only
     360 x 640.  With exactly two context views and `make_baseline_1` the world is rescaled so that they are 1 apart (in place on the
     scene's poses, as the reference does: a later entry of the same scene starts from the rescaled world); near / far = 0.1 / 1000 over
-    that scale.  A view group's frames are decoded on the host, stacked, uploaded as uint8 and go through `ops.crop_shim` in one call.
+    that scale.  A view group's frames are decoded on the host, stacked, uploaded as uint8 and go through `ops.crop_shim` in one call;
+    with `device_decode` (and `crop`) they go through `ops.jpeg_decode` instead -- the scan decoded by the library on the host, the rest
+    on the device, PNG frames and frames the library refuses through `decode_image` into their slots -- and its device tensor feeds
+    the crop shim: the same bytes.
     `crop=False` leaves out the device: the groups then carry the decoded uint8 frames `[1, v, h, w, 3]` and the unscaled intrinsics
     (inspection, CPU tests)."""
 
     def __init__(self, root, stage: str = "test", index=None, image_shape: Tuple[int, int] = (256, 256), make_baseline_1: bool = True,
-                 baseline_epsilon: float = 1e-3, max_fov: float = 100.0, scenes: Optional[Sequence[str]] = None, crop: bool = True):
+                 baseline_epsilon: float = 1e-3, max_fov: float = 100.0, scenes: Optional[Sequence[str]] = None, crop: bool = True,
+                 device_decode: bool = False):
         if index is None:
             raise ValueError("RE10KScenes needs an evaluation index (load_index(path), or the path)")
         self.root = Path(root) / stage
@@ -156,6 +162,7 @@ class RE10KScenes:
         self.make_baseline_1, self.baseline_epsilon, self.max_fov = bool(make_baseline_1), float(baseline_epsilon), float(max_fov)
         self.scenes = None if scenes is None else list(scenes)
         self.crop = bool(crop)
+        self.device_decode = bool(device_decode) and self.crop
         if self.scenes is None:
             self.chunks = sorted(p for p in self.root.iterdir() if p.suffix == ".torch")
         else:
@@ -164,15 +171,22 @@ class RE10KScenes:
             self.chunks = [self.root / where[name] for name in self.scenes]
 
     def _views(self, example: dict, indices: Sequence[int], extrinsics, intrinsics, scale) -> Optional[dict]:
-        frames = [decode_image(_frame_bytes(example["images"][i])) for i in indices]
-        sizes = {f.shape for f in frames}
         h_out, w_out = self.image_shape
-        if len(sizes) != 1 or frames[0].shape[0] < h_out or frames[0].shape[1] < w_out:
+        if self.device_decode:
+            from . import ops
+            data = [_frame_bytes(example["images"][i]) for i in indices]
+            sizes = {(*_frame_size(d, probe=True), 3) for d in data}
+        else:
+            frames = [decode_image(_frame_bytes(example["images"][i])) for i in indices]
+            sizes = {f.shape for f in frames}
+        h, w, _ = next(iter(sizes))
+        if len(sizes) != 1 or h < h_out or w < w_out:
             print(f"Skipped bad example {example['key']}. Frame shapes were {sorted(sizes)}.")
             return None
+        images = ops.jpeg_decode(data) if self.device_decode else torch.from_numpy(np.stack(frames))
         idx = torch.tensor(list(indices), dtype=torch.int64)
         bound = lambda v: (torch.full((len(indices),), v, dtype=torch.float32) / scale)[None]
-        views = {"extrinsics": extrinsics[idx][None], "intrinsics": intrinsics[idx][None], "image": torch.from_numpy(np.stack(frames))[None],
+        views = {"extrinsics": extrinsics[idx][None], "intrinsics": intrinsics[idx][None], "image": images[None],
                  "near": bound(NEAR), "far": bound(FAR), "index": idx[None]}
         return apply_crop_shim_to_views(views, self.image_shape) if self.crop else views
 
@@ -413,10 +427,16 @@ def apply_augmentation_and_crop_shim(example: dict, shape: Tuple[int, int], gene
 
 
 # ------------------------------------------------------------------------------------------ training: the loader
-def _frame_size(data: bytes) -> Tuple[int, int]:
-    """(h, w) of an encoded frame from its header, without decoding it"""
+def _frame_size(data: bytes, probe: bool = False) -> Tuple[int, int]:
+    """(h, w) of an encoded frame from its header, without decoding it.  `probe`: a JPEG the library decodes is sized by its own marker
+    parser (`ops.jpeg_probe`: the frame header's numbers, which are Pillow's `size`); any other goes to Pillow as before"""
     if data[:8] == _PNG:
         return int.from_bytes(data[20:24], "big"), int.from_bytes(data[16:20], "big")
+    if probe:
+        from .ops import jpeg_probe
+        info = jpeg_probe(data)
+        if info.supported:
+            return info.h, info.w
     try:
         from PIL import Image
     except ImportError as e:
@@ -451,6 +471,10 @@ class RE10KTrainLoader:
     size.  `decode_workers` > 0: the container decode of a batch's frames runs on that many threads (at most 16, results in order;
     nothing is drawn there, so the order of the draws does not depend on it).  `crop=False` leaves out the device: images are the
     decoded uint8 frames `[b, v, h, w, 3]` (one frame size per batch) and `flip` `[b]` says which the shim would mirror.
+    `device_decode` (with `crop`): the batch's encoded frames go to `ops.jpeg_decode` -- the Huffman scans decoded by the library's host
+    code on the `decode_workers` threads (no GIL) into one pinned tensor of coefficients, the inverse DCT, upsampling and colour on the
+    device -- and its uint8 device tensor feeds the crop shim, so no decoded frame exists on the host; PNG frames and JPEG frames the
+    library refuses are decoded as before and uploaded into their slots, so a batch may mix them.  The bytes, and the draws, are the same.
 
     No rank sharding: like the reference's iterable dataset, every rank walks all chunks, under its own torch seed."""
 
@@ -459,7 +483,7 @@ class RE10KTrainLoader:
     def __init__(self, root, stage: str = "train", view_sampler: Optional[ViewSampler] = None, image_shape: Tuple[int, int] = (256, 256),
                  batch_size: int = 6, drop_last: bool = True, augment: bool = False, make_baseline_1: bool = True, baseline_epsilon: float = 1e-3,
                  max_fov: float = 100.0, scenes: Optional[Sequence[str]] = None, decode_workers: int = 0, crop: bool = True,
-                 random_transform_extrinsics: bool = False):
+                 random_transform_extrinsics: bool = False, device_decode: bool = False):
         if stage not in ("train", "val"):
             raise ValueError(f"RE10KTrainLoader reads stage train or val, got {stage!r} (RE10KScenes reads test)")
         if random_transform_extrinsics:
@@ -475,6 +499,7 @@ class RE10KTrainLoader:
         self.make_baseline_1, self.baseline_epsilon, self.max_fov = bool(make_baseline_1), float(baseline_epsilon), float(max_fov)
         self.decode_workers = max(0, min(int(decode_workers), self.MAX_DECODE_WORKERS))
         self.crop = bool(crop)
+        self.device_decode = bool(device_decode) and self.crop
         self._pool = None
         if self.scenes is None:
             self.chunks = sorted(p for p in self.root.iterdir() if p.suffix == ".torch")
@@ -513,7 +538,7 @@ class RE10KTrainLoader:
                         scale = 1
                     groups = {k: v for k, v in view_index._asdict().items() if v is not None}
                     data = {k: [_frame_bytes(example["images"][i.item()]) for i in v] for k, v in groups.items()}
-                    sizes = {_frame_size(d) for ds in data.values() for d in ds}
+                    sizes = {_frame_size(d, probe=self.device_decode and not decode) for ds in data.values() for d in ds}
                     h, w = next(iter(sizes))
                     if len(sizes) != 1 or h < self.image_shape[0] or w < self.image_shape[1]:
                         print(f"Skipped bad example {scene}. Frame shapes were {sorted(sizes)}.")
@@ -539,20 +564,26 @@ class RE10KTrainLoader:
         return self._records(decode=True)
 
     # ---- batches
-    def _decode(self, blobs: List[bytes]) -> List[np.ndarray]:
-        if self.decode_workers == 0 or len(blobs) < 2:
-            return [decode_image(d) for d in blobs]
+    def _workers(self):
+        if self.decode_workers == 0:
+            return None
         if self._pool is None:
             from concurrent.futures import ThreadPoolExecutor
             self._pool = ThreadPoolExecutor(max_workers=self.decode_workers, thread_name_prefix="re10k-decode")
-        return list(self._pool.map(decode_image, blobs))          # in the order of `blobs`
+        return self._pool
+
+    def _decode(self, blobs: List[bytes]) -> List[np.ndarray]:
+        if self.decode_workers == 0 or len(blobs) < 2:
+            return [decode_image(d) for d in blobs]
+        return list(self._workers().map(decode_image, blobs))     # in the order of `blobs`
 
     def _collate(self, records: List[dict]) -> dict:
         views = [k for k in ("context", "target") if k in records[0]]
         counts = [records[0][k]["index"].shape[0] for k in views]
         assert all([r[k]["index"].shape[0] for k in views] == counts for r in records), "one view count per batch (the sampler's)"
         v = sum(counts)
-        frames = self._decode([d for r in records for k in views for d in r[k]["data"]])
+        blobs = [d for r in records for k in views for d in r[k]["data"]]
+        frames = None if self.device_decode else self._decode(blobs)
         batch = {"scene": [r["scene"] for r in records]}
         by_size: Dict[Tuple[int, int], List[int]] = {}
         for i, r in enumerate(records):
@@ -567,13 +598,17 @@ class RE10KTrainLoader:
             from . import ops
             dev = torch.device("cuda", torch.cuda.current_device())
             for (h, w), members in by_size.items():
-                staged = torch.empty(len(members) * v, h, w, 3, dtype=torch.uint8, pin_memory=True)          # one upload per frame size
-                host = staged.numpy()
-                for j, i in enumerate(members):
-                    for t in range(v):
-                        host[j * v + t] = frames[i * v + t]
+                if self.device_decode:      # coefficients up, frames decoded on the device
+                    source = ops.jpeg_decode([blobs[i * v + t] for i in members for t in range(v)], pool=self._workers())
+                else:
+                    staged = torch.empty(len(members) * v, h, w, 3, dtype=torch.uint8, pin_memory=True)      # one upload per frame size
+                    host = staged.numpy()
+                    for j, i in enumerate(members):
+                        for t in range(v):
+                            host[j * v + t] = frames[i * v + t]
+                    source = staged.to(dev, non_blocking=True)
                 flags = flips[members].repeat_interleave(v).to(dev, non_blocking=True)
-                out, _ = ops.crop_shim(staged.to(dev, non_blocking=True), self.image_shape, flip=flags)
+                out, _ = ops.crop_shim(source, self.image_shape, flip=flags)
                 out = out.reshape(len(members), v, *out.shape[1:])
                 if len(by_size) == 1:
                     images = out

@@ -10,10 +10,11 @@ from __future__ import annotations
 import ctypes as C
 import os
 from dataclasses import dataclass
-from typing import Optional, Sequence
+from typing import NamedTuple, Optional, Sequence
 
 import math
 
+import numpy as np
 import torch
 
 from . import _lib as L
@@ -1072,3 +1073,135 @@ def crop_shim(images: torch.Tensor, shape, ws: Optional[torch.Tensor] = None, fl
                                           None if flip is None or n == 0 else flip.data_ptr(), ws.data_ptr(), ws.numel() * ws.element_size(), got, stream()))
     assert (got[0], got[1]) == (h_scaled, w_scaled), (tuple(got), h_scaled, w_scaled)
     return dst, (h_scaled, w_scaled)
+
+
+# ------------------------------------------------------------------------------------------ JPEG frames (csrc/jpeg_host.cpp, csrc/jpeg.hip)
+class JpegInfo(NamedTuple):
+    """`mvldm_jpeg_probe` of an encoded frame.  `reason` 0: the library decodes it (`sampling`: `_lib.JPEG_GRAY` / `_444` / `_422` / `_420`);
+    otherwise an index into `_lib.JPEG_REASONS`, `sampling` is -1, and h, w are the frame header's if one was read (else 0)."""
+    h: int
+    w: int
+    sampling: int
+    reason: int
+    luma_blocks: int
+    chroma_blocks: int
+    mcu_cols: int
+    mcu_rows: int
+
+    @property
+    def supported(self) -> bool:
+        return self.reason == 0
+
+
+def jpeg_probe(blob: bytes) -> JpegInfo:
+    """size, sampling layout and block counts of an encoded frame from its markers, without decoding it (host only)"""
+    info = (C.c_int32 * 8)()
+    rc = L.load().mvldm_jpeg_probe(blob, len(blob), info)
+    if rc < 0:
+        L.check(rc)
+    return JpegInfo(*info)
+
+
+def jpeg_coef_count(h: int, w: int, sampling: int) -> int:
+    """int16 coefficients of one h x w frame in a sampling layout (64 per block of every component's MCU-padded grid); 0 for a refused shape"""
+    return int(L.load().mvldm_jpeg_coef_count(h, w, sampling))
+
+
+def jpeg_workspace_bytes(n_img: int, h: int, w: int, sampling: int) -> int:
+    """bytes `jpeg_decode_coefs` needs for n_img frames: the components' uint8 planes between the two kernels"""
+    return int(L.load().mvldm_jpeg_workspace_bytes(n_img, h, w, sampling))
+
+
+def jpeg_entropy(blob: bytes, coef: np.ndarray, qt: np.ndarray):
+    """the host's entropy decoder: the frame's quantised coefficients into `coef` (a contiguous int16 array with room for
+    `jpeg_coef_count` values) and its tables into `qt` (uint16 or int16, 192 values) -> (reason, largest S of a block).  Releases the GIL;
+    keeps no state."""
+    assert coef.dtype == np.int16 and coef.flags.c_contiguous and qt.dtype.itemsize == 2 and qt.flags.c_contiguous and qt.size >= 192
+    max_s = C.c_int32(0)
+    rc = L.load().mvldm_jpeg_entropy(blob, len(blob), coef.ctypes.data, coef.size, qt.ctypes.data, C.byref(max_s))
+    if rc < 0:
+        L.check(rc)
+    return rc, max_s.value
+
+
+def jpeg_idct_host(coef: np.ndarray, qt: np.ndarray, h: int, w: int, sampling: int) -> np.ndarray:
+    """the device half of the decoder in plain C++ on the host (same arithmetic) -> uint8 `[h, w, 3]`: tests and tools"""
+    assert coef.dtype == np.int16 and coef.flags.c_contiguous and coef.size >= jpeg_coef_count(h, w, sampling) > 0
+    assert qt.dtype.itemsize == 2 and qt.flags.c_contiguous and qt.size >= 192
+    out = np.empty((h, w, 3), dtype=np.uint8)
+    L.check(L.load().mvldm_jpeg_idct_host(coef.ctypes.data, qt.ctypes.data, out.ctypes.data, h, w, sampling))
+    return out
+
+
+def jpeg_decode_coefs(coef: torch.Tensor, qt: torch.Tensor, h: int, w: int, sampling: int, dst: Optional[torch.Tensor] = None,
+                      ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`mvldm_jpeg_decode`: coefficients int16 `[n, jpeg_coef_count]` and tables int16 `[n, 192]` (uint16 bit patterns) on the device ->
+    uint8 `[n, h, w, 3]`.  Two launches; nothing is allocated when `dst` and `ws` are given, so the call can be captured."""
+    n = coef.shape[0]
+    assert coef.is_cuda and coef.is_contiguous() and coef.dtype == torch.int16 and tuple(coef.shape) == (n, jpeg_coef_count(h, w, sampling))
+    assert qt.is_cuda and qt.is_contiguous() and qt.dtype == torch.int16 and tuple(qt.shape) == (n, 192)
+    if dst is None:
+        dst = torch.empty(n, h, w, 3, dtype=torch.uint8, device=coef.device)
+    assert dst.is_cuda and dst.is_contiguous() and dst.dtype == torch.uint8 and tuple(dst.shape) == (n, h, w, 3)
+    if ws is None:
+        ws = workspace(jpeg_workspace_bytes(n, h, w, sampling), coef.device, "jpeg")
+    L.check(L.load().mvldm_jpeg_decode(coef.data_ptr(), qt.data_ptr(), dst.data_ptr(), n, h, w, sampling, ws.data_ptr(), ws.numel() * ws.element_size(),
+                                       stream()))
+    return dst
+
+
+def jpeg_decode(blobs: Sequence[bytes], pool=None, device=None) -> torch.Tensor:
+    """encoded frames of ONE size -> uint8 `[n, h, w, 3]` on the current device, the bytes `Image.open(...).convert("RGB")` gives.
+
+    Per frame the host parses the markers and decodes the Huffman scan (`mvldm_jpeg_entropy`: no Pillow, no GIL; on `pool`, a
+    `concurrent.futures` executor, when one is given) straight into one pinned staging tensor per sampling layout; each layout is one
+    upload and one `mvldm_jpeg_decode` call.  A frame the library refuses -- progressive, CMYK, outside the range guard, PNG, ... -- is
+    decoded by `dataset.decode_image` (Pillow) on the host and uploaded into its slot: the result never depends on which path ran."""
+    from .dataset import decode_image
+    n = len(blobs)
+    if n == 0:
+        raise ValueError("jpeg_decode: no frames")
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    infos = [jpeg_probe(b) for b in blobs]
+    groups: dict = {}
+    for i, info in enumerate(infos):
+        if info.supported:
+            groups.setdefault(info.sampling, []).append(i)
+    sizes = {(info.h, info.w) for info in infos if info.supported}
+    if len(sizes) > 1:
+        raise ValueError(f"jpeg_decode: frames of one size, got {sorted(sizes)}")
+    refused = [i for i, info in enumerate(infos) if not info.supported]
+    staged, jobs = {}, []
+    for sampling, members in groups.items():
+        h, w = infos[members[0]].h, infos[members[0]].w
+        count = jpeg_coef_count(h, w, sampling)
+        buf = torch.empty(len(members) * (count + 192), dtype=torch.int16, pin_memory=True)         # [coefficients | tables]: one upload
+        host = buf.numpy()
+        staged[sampling] = (buf, count)
+        for j, i in enumerate(members):
+            jobs.append((i, host[j * count:(j + 1) * count], host[len(members) * count + j * 192:len(members) * count + (j + 1) * 192]))
+    run = lambda job: jpeg_entropy(blobs[job[0]], job[1], job[2])[0]
+    reasons = list(pool.map(run, jobs)) if pool is not None and len(jobs) > 1 else [run(j) for j in jobs]
+    refused += [job[0] for job, reason in zip(jobs, reasons) if reason != 0]      # the scan itself: corrupt, or outside the guard
+    late = [blobs[i] for i in sorted(refused)]
+    late = list(pool.map(decode_image, late)) if pool is not None and len(late) > 1 else [decode_image(b) for b in late]
+    sizes |= {f.shape[:2] for f in late}
+    if len(sizes) != 1:
+        raise ValueError(f"jpeg_decode: frames of one size, got {sorted(sizes)}")
+    (h, w), = sizes
+    dst = torch.empty(n, h, w, 3, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        for sampling, members in groups.items():
+            buf, count = staged[sampling]
+            m = len(members)
+            on_dev = buf.to(dev, non_blocking=True)
+            whole = m == n                      # the common case: every frame in one layout, decoded in place
+            out = jpeg_decode_coefs(on_dev[:m * count].view(m, count), on_dev[m * count:].view(m, 192), h, w, sampling, dst if whole else None)
+            if not whole:
+                dst[torch.tensor(members, device=dev)] = out
+        if late:
+            host = torch.empty(len(late), h, w, 3, dtype=torch.uint8, pin_memory=True)
+            for j, f in enumerate(late):
+                host.numpy()[j] = f
+            dst[torch.tensor(sorted(refused), device=dev)] = host.to(dev, non_blocking=True)         # after the kernels: a refused scan's slot is overwritten
+    return dst

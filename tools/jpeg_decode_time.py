@@ -1,0 +1,89 @@
+"""time the JPEG decoder (mv_ldm_amd/ops.py jpeg_decode: csrc/jpeg_host.cpp on the host, csrc/jpeg.hip on the device) next to Pillow:
+    python tools/jpeg_decode_time.py [--json OUT]
+Two 360 x 640 4:2:0 quality-90 frames built here: "fixture" (tests/train_fixture.py's kind: 45 x 80 noise repeated 8 x each way, so every
+luma block is flat) and "photo" (smooth ramps plus +-12 of noise: every block has AC coefficients).  Per frame:
+  * host: `mvldm_jpeg_entropy` (markers + Huffman scan into a reused buffer) on ONE thread, best of 5 passes of 20 calls, ms a frame; and
+    Pillow's whole decode of the same bytes (`Image.open(...).convert("RGB")` to a numpy array) on one core of the same box, likewise.
+  * device: `mvldm_jpeg_decode` of n = 5 and n = 30 copies, coefficients already on the device, microseconds per frame.  "hot": the median
+    of 5 windows of back-to-back calls between device events; "cold": one call per window behind a 640 MB fill that evicts the 256 MiB
+    last-level cache, median of 7.
+The device result is checked against Pillow's before anything is timed.  No threshold: the figures go to DESIGN.md and profiles/."""
+import json, os, sys, time
+from io import BytesIO
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+import torch
+from PIL import Image
+from mv_ldm_amd import ops
+
+H, W = 360, 640
+rng = np.random.default_rng(0)
+yy, xx = np.mgrid[0:H, 0:W]
+FRAMES = {
+    "fixture": rng.integers(0, 256, (H // 8, W // 8, 3), dtype=np.uint8).repeat(8, axis=0).repeat(8, axis=1),
+    "photo": np.clip(np.stack([yy * 255 // (H - 1), xx * 255 // (W - 1), (yy + xx) * 255 // (H + W - 2)], axis=-1) + rng.integers(-12, 13, (H, W, 3)), 0, 255).astype(np.uint8),
+}
+rec = {"frame": [H, W], "format": "4:2:0, quality 90, Pillow " + __import__("PIL").__version__, "device": torch.cuda.get_device_name(0),
+       "arch": torch.cuda.get_device_properties(0).gcnArchName, "host_cpus_visible": len(os.sched_getaffinity(0)),
+       "note": "host: ms per frame, one thread, best of 5 passes of 20; device: us per frame, hot = median of 5 windows of back-to-back calls, "
+               "cold = one call behind a 640 MB fill, median of 7; one run on one box"}
+flush = torch.empty(640 << 20, dtype=torch.uint8, device="cuda")
+torch.set_num_threads(1)
+
+
+def event_us(fn, iters):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(iters):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) * 1e3 / iters
+
+
+def best_ms(fn):
+    best = float("inf")
+    for _ in range(5):
+        t0 = time.perf_counter()
+        for _ in range(20):
+            fn()
+        best = min(best, (time.perf_counter() - t0) / 20)
+    return best * 1e3
+
+
+for name, pixels in FRAMES.items():
+    buf = BytesIO()
+    Image.fromarray(pixels).save(buf, format="JPEG", quality=90, subsampling=2)
+    blob = buf.getvalue()
+    want = np.asarray(Image.open(BytesIO(blob)).convert("RGB"))
+    info = ops.jpeg_probe(blob)
+    assert info.supported and info.sampling == 3
+    count = ops.jpeg_coef_count(H, W, 3)
+    coef, qt = np.zeros(count, dtype=np.int16), np.zeros(192, dtype=np.int16)
+    reason, max_s = ops.jpeg_entropy(blob, coef, qt)
+    assert reason == 0, reason
+    r = rec[name] = {"stream_bytes": len(blob), "largest_block_S": max_s,
+                     "host_entropy_ms_per_frame": round(best_ms(lambda: ops.jpeg_entropy(blob, coef, qt)), 4),
+                     "pillow_decode_ms_per_frame": round(best_ms(lambda: np.asarray(Image.open(BytesIO(blob)).convert("RGB"))), 4)}
+    for n in (5, 30):
+        dc = torch.from_numpy(coef).cuda().repeat(n, 1)
+        dq = torch.from_numpy(qt).cuda().repeat(n, 1)
+        dst = torch.empty(n, H, W, 3, dtype=torch.uint8, device="cuda")
+        ws = torch.empty(ops.jpeg_workspace_bytes(n, H, W, 3), dtype=torch.uint8, device="cuda")
+        call = lambda: ops.jpeg_decode_coefs(dc, dq, H, W, 3, dst, ws)
+        call()
+        torch.cuda.synchronize()
+        assert all(np.array_equal(dst[i].cpu().numpy(), want) for i in (0, n - 1)), "the device result is not Pillow's"
+        hot = sorted(event_us(call, 50 if n == 5 else 20) for _ in range(5))[2]
+        cold = []
+        for _ in range(7):
+            flush.fill_(1)
+            cold.append(event_us(call, 1))
+        cold = sorted(cold)[3]
+        r[f"device_n{n}"] = {"hot_us_per_frame": round(hot / n, 3), "cold_us_per_frame": round(cold / n, 3), "hot_us_per_call": round(hot, 2),
+                             "cold_us_per_call": round(cold, 2), "coefficient_bytes_per_frame": count * 2}
+    print(name, json.dumps(r), flush=True)
+if "--json" in sys.argv:
+    with open(sys.argv[sys.argv.index("--json") + 1], "w") as f:
+        json.dump(rec, f, indent=1)
+print(json.dumps(rec))
