@@ -46,7 +46,9 @@ extern "C" {
  *    + mvldm_crop_shim_flip (the crop shim with a per-image mirrored read, for the training loader's augmentation shim): new symbol only,
  *    the number stays 7.
  *    + mvldm_jpeg_probe / _entropy / _coef_count / _workspace_bytes / _decode / _idct_host (baseline JPEG frames: entropy decoding on the
- *    host, dequantisation, inverse DCT, upsampling and colour on the device): new symbols and enums only, the number stays 7. */
+ *    host, dequantisation, inverse DCT, upsampling and colour on the device): new symbols and enums only, the number stays 7.
+ *    + mvldm_jpeg_scan_room / _scan_prepare / _entropy_chunk_subseqs / _entropy_device / _entropy_emul_host and the reason
+ *    MVLDM_JPEG_RESTART (the Huffman scan decoded on the device): new symbols and one new enum value only, the number stays 7. */
 #define MVLDM_ABI_VERSION 7
 
 typedef void* mvldm_stream_t; /* hipStream_t */
@@ -818,6 +820,70 @@ int mvldm_jpeg_decode(const int16_t* coef, const uint16_t* qt, uint8_t* dst, int
                       size_t workspace_bytes, mvldm_stream_t stream);
 int mvldm_jpeg_idct_host(const int16_t* coef /* host */, const uint16_t* qt /* host [192] */, uint8_t* dst /* host [h][w][3] */, int h, int w,
                          int sampling);
+
+/* ------------------------------------------------------------------------------------------------
+ * JPEG frames: the scan on the device.  An opt-in second way to the coefficients mvldm_jpeg_decode takes: the host only removes the byte
+ * stuffing and builds the tables (mvldm_jpeg_scan_prepare); the Huffman-coded scan is decoded by a self-synchronising decoder (Klein and
+ * Wiseman; Weissenberger and Schmidt) in mvldm_jpeg_entropy_device.  The result is mvldm_jpeg_entropy's, value for value.
+ *   streams   those of mvldm_jpeg_entropy WITHOUT restart intervals: a frame with DRI != 0 is MVLDM_JPEG_RESTART, and the caller decodes
+ *             its scan with mvldm_jpeg_entropy.  The scan ends at the first 0xFF followed by a non-zero byte; after optional 0xFF fill
+ *             bytes that marker must be EOI (else MVLDM_JPEG_CORRUPT; no marker before len: MVLDM_JPEG_TRUNCATED).
+ *   scan      the entropy-coded bytes with every FF 00 reduced to FF, in stream order, at a 16-byte aligned offset of a packed buffer the
+ *             caller owns, followed by zeros up to mvldm_jpeg_scan_room(bytes) = round_up(bytes, 16) + 16.  The device reads aligned
+ *             dwords and swaps their bytes; the widest read for a symbol that starts at the last bit ends 12 bytes past the scan.
+ *             mvldm_jpeg_scan_room(len) is also the room a frame of len encoded bytes can need: destuffing only shrinks.
+ *   desc      int32 [4] per frame: byte offset of the scan in the packed buffer (a multiple of 16), bit_len (8 x destuffed bytes), bytes
+ *             occupied with the padding, 0.  The device checks a descriptor against scan_bytes before it reads the scan.
+ *   tables    MVLDM_JPEG_TABLE_BYTES per frame: six Huffman tables of MVLDM_JPEG_HUFF_TABLE_BYTES -- component 0's DC, its AC, component
+ *             1's DC, ... as the scan header's td / ta select them (a shared table is stored twice; grayscale leaves four zero) -- then
+ *             qt uint16 [3][64] as above.  A table: uint16 look[512] ((length << 8) | symbol of every code of up to 9 bits by its
+ *             first 9 bits, 0 for a longer one), int32 maxcode[18] (largest code of length l, -1 if none; [17] above every code), int32
+ *             valoff[18] (index of the first symbol of length l minus its code), uint8 vals[256].
+ *   state     (p, b, k): bit position, block within the MCU (0 .. hmax vmax + 1; selects the component and so the tables), zigzag
+ *             position (0: the next symbol is a DC category).  One step decodes one symbol and its magnitude bits, and it is a total
+ *             function of the state and the bits: what mvldm_jpeg_entropy refuses is a FAULT, after which the decode goes on by a
+ *             fixed rule -- a code that does not exist skips one bit, a DC category above 15 counts as 0, a coefficient index above
+ *             63 consumes its bits and ends the block -- and a symbol whose bits run past bit_len gives DEAD (p = bit_len and a
+ *             flag), which passes through everything after it.  No read leaves the padded scan, whatever the bits are.  Faults are
+ *             not absorbing because a decoder started at a wrong bit faults constantly and would then never meet the true sequence
+ *             of states; they count only where the entry state is known to be true (the write pass, below).
+ *   decoder   one workgroup per frame.  The scan is cut into subsequences of subseq_bits (0: the default, 512; else a multiple of 32 in
+ *             32 .. 65536), one per thread; a chunk is mvldm_jpeg_entropy_chunk_subseqs() = 1024 of them, and the workgroup walks the
+ *             chunks in order.  Cold pass: every thread decodes its subsequence from (its first bit, 0, 0) -- thread 0 from the true
+ *             state -- and leaves its exit state.  Rounds: thread i takes thread i - 1's exit as its entry and decodes again if that
+ *             changed, until no entry changed or as many rounds ran as the chunk has subsequences: after r rounds the first r + 1
+ *             subsequences are right whatever the stream is, so the bound is also the proof.  Write pass: a scan of the blocks each
+ *             thread completed gives its first block; it decodes once more and stores every coefficient at mvldm_jpeg_entropy's
+ *             address (the DC DIFFERENCE in [0]), each store guarded by block < blocks of the frame.  The slots are zeroed by a memset
+ *             in front of the kernel on the same stream.  A second kernel sums the DC differences per component in scan order (64-bit),
+ *             and computes the guard's S of every block.
+ *   accepted  when the write pass meets no fault in front of the frame's last block, that block completes with fewer than 8 bits left
+ *             (where mvldm_jpeg_entropy stops reading; what the remaining bits would decode to is not looked at), and every DC prefix
+ *             fits int16 -- else MVLDM_JPEG_CORRUPT -- and no S exceeds the guard, else MVLDM_JPEG_RANGE.
+ *   status    int32 [4] per frame: reason, largest S (0 unless the reason is OK or RANGE: mvldm_jpeg_entropy's max_s), the largest number
+ *             of rounds a chunk took, 0.
+ * mvldm_jpeg_scan_prepare (host; no state, any number of threads) reads data[0 .. len) and writes scan[scan_off .. scan_off + desc[2]),
+ * desc and tables; info (may be NULL) is mvldm_jpeg_probe's.  Returns the reason: what mvldm_jpeg_probe returns, MVLDM_JPEG_RESTART,
+ * CORRUPT / TRUNCATED for the scan's end; MVLDM_ERR_ARG for a null pointer, an offset that is no multiple of 16, a scan_room below
+ * scan_off + mvldm_jpeg_scan_room(len) or above 2^31 - 1.  After a refusal nothing outside those ranges was written.
+ * mvldm_jpeg_entropy_device (device) decodes n_img prepared frames of ONE (h, w, sampling): a memset and two launches, no allocation,
+ * nothing read back; may be captured.  scan, desc, tables, coef [n_img][coef_count], qt [n_img][3][64], status: device pointers, 16-byte
+ * aligned (status, desc: 4); a null or misaligned pointer, a refused shape or subseq_bits is MVLDM_ERR_ARG.  After a refusal a frame's
+ * coef slot is unspecified; nothing outside coef, qt and status is written.
+ * mvldm_jpeg_entropy_emul_host (host) is the same algorithm with loops for threads and the same step function (csrc/jpeg_huff_common.h),
+ * chunk_subseqs subsequences to a chunk (0: the device's): the same coef, qt and status, rounds included when the chunk sizes agree. */
+#define MVLDM_JPEG_HUFF_TABLE_BYTES 1424
+#define MVLDM_JPEG_TABLE_BYTES 8928
+enum { MVLDM_JPEG_RESTART = 13 }; /* restart intervals: not on the device entropy path */
+size_t mvldm_jpeg_scan_room(size_t len);
+int mvldm_jpeg_scan_prepare(const uint8_t* data /* host */, size_t len, uint8_t* scan /* host */, size_t scan_off, size_t scan_room,
+                            int32_t* desc /* host [4] */, uint8_t* tables /* host [MVLDM_JPEG_TABLE_BYTES] */, int32_t* info /* host [8], may be NULL */);
+int mvldm_jpeg_entropy_chunk_subseqs(void);
+int mvldm_jpeg_entropy_device(const uint8_t* scan, size_t scan_bytes, const int32_t* desc, const uint8_t* tables, int n_img, int h, int w,
+                              int sampling, int16_t* coef, uint16_t* qt, int32_t* status, int subseq_bits, mvldm_stream_t stream);
+int mvldm_jpeg_entropy_emul_host(const uint8_t* scan /* host */, size_t scan_bytes, const int32_t* desc /* host */, const uint8_t* tables /* host */,
+                                 int n_img, int h, int w, int sampling, int16_t* coef /* host */, uint16_t* qt /* host */, int32_t* status /* host */,
+                                 int subseq_bits, int chunk_subseqs);
 
 /* ------------------------------------------------------------------------------------------------
  * Plans: a whole forward (UNet walk, VAE decoder, DDIM step) as a flat list of the ops above with

@@ -20,8 +20,10 @@ NORM_BWD_STORE = 0x100          # include/mvldm.h MVLDM_NORM_BWD_STORE: norm bac
 GN_MAX_CHUNKS = 32
 JPEG_GRAY, JPEG_444, JPEG_422, JPEG_420 = 0, 1, 2, 3            # include/mvldm.h MVLDM_JPEG_*: sampling layouts
 JPEG_REASONS = ("ok", "not a JPEG", "truncated", "corrupt", "progressive", "frame type", "precision", "components", "sampling", "colour space",
-                "scans", "size", "range guard")                 # MVLDM_JPEG_OK .. MVLDM_JPEG_RANGE, by value
+                "scans", "size", "range guard", "restart intervals")        # MVLDM_JPEG_OK .. MVLDM_JPEG_RESTART, by value
 JPEG_RANGE = 12
+JPEG_RESTART = 13                                               # mvldm_jpeg_scan_prepare only: the frame's scan is decoded by the host
+JPEG_HUFF_TABLE_BYTES, JPEG_TABLE_BYTES = 1424, 8928            # MVLDM_JPEG_HUFF_TABLE_BYTES, MVLDM_JPEG_TABLE_BYTES
 
 (OP_IGEMM, OP_GROUPNORM, OP_LAYERNORM, OP_ATTENTION, OP_TIMESTEP_EMBED, OP_ELTWISE, OP_DDIM_STEP, OP_DDIM_ADVANCE,
  OP_NCHW_TO_NHWC, OP_NHWC_TO_NCHW, OP_MEMCPY, OP_RAY_ENCODE, OP_POSTERIOR_SAMPLE,
@@ -271,6 +273,11 @@ SIGNATURES = {
     "mvldm_jpeg_workspace_bytes": (sz, [C.c_int] * 4),
     "mvldm_jpeg_decode": (C.c_int, [vp, vp, vp] + [C.c_int] * 4 + [vp, sz, vp]),
     "mvldm_jpeg_idct_host": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int]),
+    "mvldm_jpeg_scan_room": (sz, [sz]),
+    "mvldm_jpeg_scan_prepare": (C.c_int, [vp, sz, vp, sz, sz, vp, vp, vp]),
+    "mvldm_jpeg_entropy_chunk_subseqs": (C.c_int, []),
+    "mvldm_jpeg_entropy_device": (C.c_int, [vp, sz, vp, vp] + [C.c_int] * 4 + [vp, vp, vp, C.c_int, vp]),
+    "mvldm_jpeg_entropy_emul_host": (C.c_int, [vp, sz, vp, vp] + [C.c_int] * 4 + [vp, vp, vp, C.c_int, C.c_int]),
     "mvldm_nchw_to_nhwc": (C.c_int, [vp, vp] + [C.c_int] * 6 + [f32, f32, vp, vp]),
     "mvldm_ray_channels": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "mvldm_ray_encode": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp] + [C.c_int] * 4 + [vp]),

@@ -4,6 +4,7 @@
 #include <string.h>
 
 #include "jpeg_common.h"
+#include "jpeg_huff_common.h"
 
 namespace mvldm {
 
@@ -27,6 +28,7 @@ struct Huff {                   // one DHT table: canonical codes by length, and
 // DHT payload at p[0 .. n): counts[16], symbols.  false: the counts do not describe a prefix code
 bool huff_build(Huff* t, const uint8_t* counts, const uint8_t* syms, int nsyms) {
     memset(t->look, 0, sizeof(t->look));
+    memset(t->vals, 0, sizeof(t->vals));        // the table blob of the device path copies all 256
     memcpy(t->vals, syms, (size_t)nsyms);
     int32_t code = 0;
     int k = 0;
@@ -323,6 +325,36 @@ int decode_scan(const uint8_t* d, size_t len, const Header& hd, const JpegLayout
     return worst > kJpegGuard ? MVLDM_JPEG_RANGE : MVLDM_JPEG_OK;
 }
 
+// info[0..7] of mvldm_jpeg_probe
+void fill_info(const Header& hd, int reason, int32_t* info) {
+    for (int i = 0; i < 8; ++i) info[i] = 0;
+    info[0] = hd.h;
+    info[1] = hd.w;
+    info[2] = -1;
+    info[3] = reason;
+    JpegLayout L;
+    if (reason == MVLDM_JPEG_OK && jpeg_layout(hd.h, hd.w, hd.sampling, &L)) {
+        info[2] = hd.sampling;
+        info[4] = L.bw[0] * L.bh[0];
+        info[5] = L.bw[1] * L.bh[1];
+        info[6] = L.mcux;
+        info[7] = L.mcuy;
+    }
+}
+
+// one table of the device path's blob (include/mvldm.h): look | maxcode[18] | valoff[18] | vals
+void huff_blob(const Huff& t, uint8_t* out) {
+    int32_t words[36];
+    for (int l = 0; l < 18; ++l) {
+        words[l] = l >= 1 ? t.maxcode[l] : -1;
+        words[18 + l] = l >= 1 && l <= 16 ? t.valoff[l] : 0;
+    }
+    memcpy(out + kHuffLookOff, t.look, sizeof(t.look));
+    memcpy(out + kHuffMaxOff, words, sizeof(words));
+    memcpy(out + kHuffValsOff, t.vals, sizeof(t.vals));
+}
+static_assert(sizeof(Huff::look) == 1024 && sizeof(Huff::vals) == 256, "table blob layout");
+
 }  // namespace
 
 size_t jpeg_coef_count(int h, int w, int sampling) {
@@ -338,19 +370,7 @@ extern "C" int mvldm_jpeg_probe(const uint8_t* data, size_t len, int32_t* info) 
     if (data == nullptr || info == nullptr) return set_error(MVLDM_ERR_ARG, "jpeg_probe: null pointer");
     Header hd;
     const int reason = parse_header(data, len, &hd);
-    for (int i = 0; i < 8; ++i) info[i] = 0;
-    info[0] = hd.h;
-    info[1] = hd.w;
-    info[2] = -1;
-    info[3] = reason;
-    JpegLayout L;
-    if (reason == MVLDM_JPEG_OK && jpeg_layout(hd.h, hd.w, hd.sampling, &L)) {
-        info[2] = hd.sampling;
-        info[4] = L.bw[0] * L.bh[0];
-        info[5] = L.bw[1] * L.bh[1];
-        info[6] = L.mcux;
-        info[7] = L.mcuy;
-    }
+    fill_info(hd, reason, info);
     return reason;
 }
 
@@ -403,5 +423,170 @@ extern "C" int mvldm_jpeg_idct_host(const int16_t* coef, const uint16_t* qt, uin
             o[2] = (uint8_t)(px >> 16);
         }
     delete[] planes;
+    return MVLDM_OK;
+}
+
+// ---- the scan on the device: what the host still does, and the decoder's emulation ---------------------------------------------------
+extern "C" size_t mvldm_jpeg_scan_room(size_t len) { return huff_scan_room(len); }
+
+extern "C" int mvldm_jpeg_scan_prepare(const uint8_t* data, size_t len, uint8_t* scan, size_t scan_off, size_t scan_room, int32_t* desc, uint8_t* tables,
+                                       int32_t* info) {
+    if (data == nullptr || scan == nullptr || desc == nullptr || tables == nullptr) return set_error(MVLDM_ERR_ARG, "jpeg_scan_prepare: null pointer");
+    if ((scan_off & 15) || len >= ((size_t)1 << 28) || scan_room > 0x7FFFFFFFu || scan_room < scan_off || scan_room - scan_off < huff_scan_room(len))
+        return set_error(MVLDM_ERR_ARG, "jpeg_scan_prepare: offset %zu of %zu bytes for a frame of %zu (a multiple of 16, room for %zu, below 2^31)", scan_off,
+                         scan_room, len, huff_scan_room(len));
+    Header hd;
+    const int reason = parse_header(data, len, &hd);
+    if (info) fill_info(hd, reason, info);
+    desc[0] = (int32_t)scan_off;
+    desc[1] = desc[2] = desc[3] = 0;
+    if (reason != MVLDM_JPEG_OK) return reason;
+    JpegLayout L;
+    if (!jpeg_layout(hd.h, hd.w, hd.sampling, &L)) return MVLDM_JPEG_SIZE;
+    if (hd.restart != 0) return MVLDM_JPEG_RESTART;
+    // the entropy-coded bytes up to the first marker, FF 00 -> FF
+    uint8_t* out = scan + scan_off;
+    size_t n = 0, i = hd.scan;
+    while (true) {
+        if (i >= len) return MVLDM_JPEG_TRUNCATED;
+        const uint8_t b = data[i];
+        if (b == 0xFF) {
+            if (i + 1 >= len) return MVLDM_JPEG_TRUNCATED;
+            if (data[i + 1] != 0x00) break;
+            i += 2;
+        } else {
+            ++i;
+        }
+        out[n++] = b;                           // n <= i - hd.scan < len
+    }
+    while (i < len && data[i] == 0xFF) ++i;     // the marker: fill bytes, then EOI (decode_scan's tail)
+    if (i >= len) return MVLDM_JPEG_TRUNCATED;
+    if (data[i] != 0xD9) return MVLDM_JPEG_CORRUPT;
+    const size_t room = huff_scan_room(n);      // <= huff_scan_room(len)
+    memset(out + n, 0, room - n);
+    desc[1] = (int32_t)(n * 8);
+    desc[2] = (int32_t)room;
+    memset(tables, 0, (size_t)kHuffBlobBytes);
+    uint16_t qt[192];
+    for (int c = 0; c < 3; ++c) {
+        if (c < L.ncomp) {
+            huff_blob(hd.dc[hd.comp[c].td], tables + (size_t)(2 * c) * kHuffTabBytes);
+            huff_blob(hd.ac[hd.comp[c].ta], tables + (size_t)(2 * c + 1) * kHuffTabBytes);
+        }
+        for (int k = 0; k < 64; ++k) qt[c * 64 + k] = c < L.ncomp ? hd.qt[hd.comp[c].tq][k] : 0;
+    }
+    memcpy(tables + kHuffTabsBytes, qt, sizeof(qt));
+    return MVLDM_JPEG_OK;
+}
+
+extern "C" int mvldm_jpeg_entropy_chunk_subseqs(void) { return kHuffChunk; }
+
+extern "C" int mvldm_jpeg_entropy_emul_host(const uint8_t* scan, size_t scan_bytes, const int32_t* desc, const uint8_t* tables, int n_img, int h, int w,
+                                            int sampling, int16_t* coef, uint16_t* qt, int32_t* status, int subseq_bits, int chunk_subseqs) {
+    if (scan == nullptr || desc == nullptr || tables == nullptr || coef == nullptr || qt == nullptr || status == nullptr)
+        return set_error(MVLDM_ERR_ARG, "jpeg_entropy_emul_host: null pointer");
+    JpegLayout L;
+    if (n_img < 0 || !jpeg_layout(h, w, sampling, &L)) return set_error(MVLDM_ERR_ARG, "jpeg_entropy_emul_host: %d frames of %d x %d, sampling %d", n_img, h, w, sampling);
+    if (!huff_bits_ok(subseq_bits) || chunk_subseqs < 0 || chunk_subseqs > (1 << 20))
+        return set_error(MVLDM_ERR_ARG, "jpeg_entropy_emul_host: subseq_bits %d (0, or a multiple of 32 in 32 .. %d), chunk of %d", subseq_bits, kHuffMaxBits, chunk_subseqs);
+    const uint32_t sb = subseq_bits ? (uint32_t)subseq_bits : (uint32_t)kHuffDefaultBits;
+    const uint32_t T = chunk_subseqs ? (uint32_t)chunk_subseqs : (uint32_t)kHuffChunk;
+    const HuffGeom G = huff_geom(L);
+    const size_t count = (size_t)L.blocks * 64;
+    HuffState* buf[2] = {new HuffState[T], new HuffState[T]};      // the exit states: the barrier of a round is the swap of the two
+    HuffState* entry = new HuffState[T];
+    uint32_t* done = new uint32_t[T];
+    uint8_t zigzag[64];
+    for (uint32_t i = 0; i < 64; ++i) zigzag[i] = huff_zigzag(i);
+    for (int img = 0; img < n_img; ++img) {
+        int16_t* cf = coef + (size_t)img * count;
+        uint16_t* q = qt + (size_t)img * 192;
+        const int32_t* d = desc + (size_t)img * 4;
+        const uint8_t* tab = tables + (size_t)img * kHuffBlobBytes;
+        memset(cf, 0, count * sizeof(int16_t));
+        memcpy(q, tab + kHuffTabsBytes, 192 * sizeof(uint16_t));
+        int reason = MVLDM_JPEG_CORRUPT;
+        uint32_t rounds_max = 0;
+        if (huff_desc_ok(d, scan_bytes)) {
+            const uint8_t* sc = scan + d[0];
+            const uint32_t bit_len = (uint32_t)d[1];
+            const uint32_t nsub = (uint32_t)(((uint64_t)bit_len + sb - 1) / sb);
+            HuffState carry = {0u, 0u};
+            uint32_t base = 0, end_p = 0xFFFFFFFFu, bad = 0;
+            for (uint32_t ch0 = 0; ch0 < nsub; ch0 += T) {
+                const uint32_t n_act = nsub - ch0 < T ? nsub - ch0 : T;
+                auto end_of = [&](uint32_t i) {
+                    const uint64_t e = ((uint64_t)(ch0 + i) + 1) * sb;
+                    return e < bit_len ? (uint32_t)e : bit_len;
+                };
+                HuffNoSink none;
+                for (uint32_t i = 0; i < n_act; ++i) {          // cold pass
+                    entry[i] = i == 0 ? carry : HuffState{(ch0 + i) * sb, 0u};
+                    HuffState st = entry[i];
+                    huff_run(sc, bit_len, tab, G.nl, G.nb, end_of(i), sb, &st, &done[i], &none);
+                    buf[0][i] = st;
+                }
+                int cur = 0;
+                uint32_t rounds = 0;
+                for (uint32_t r = 0; r < n_act; ++r) {
+                    bool any = false;
+                    for (uint32_t i = 0; i < n_act; ++i) {
+                        HuffState st = buf[cur][i];
+                        if (i >= 1 && !huff_same(buf[cur][i - 1], entry[i])) {
+                            entry[i] = st = buf[cur][i - 1];
+                            huff_run(sc, bit_len, tab, G.nl, G.nb, end_of(i), sb, &st, &done[i], &none);
+                            any = true;
+                        }
+                        buf[cur ^ 1][i] = st;
+                    }
+                    cur ^= 1;
+                    ++rounds;
+                    if (!any) break;
+                }
+                if (rounds > rounds_max) rounds_max = rounds;
+                for (uint32_t i = 0; i < n_act; ++i) {          // write pass
+                    HuffCoefSink sink{cf, zigzag, G, base, &end_p, &bad, nullptr};
+                    sink.open();
+                    HuffState st = entry[i];
+                    uint32_t nb = 0;
+                    huff_run(sc, bit_len, tab, G.nl, G.nb, end_of(i), sb, &st, &nb, &sink);
+                    base += nb;
+                }
+                carry = buf[cur][n_act - 1];
+            }
+            if (!bad && end_p != 0xFFFFFFFFu && bit_len - end_p < 8u) reason = MVLDM_JPEG_OK;
+        }
+        int32_t worst = 0;
+        if (reason == MVLDM_JPEG_OK) {          // the second launch: DC prefixes in scan order, S of every block
+            bool bad = false;
+            for (uint32_t c = 0; c < G.ncomp; ++c) {
+                const uint32_t nc = c == 0 ? G.mcus * G.nl : G.mcus;
+                int64_t pred = 0;
+                for (uint32_t j = 0; j < nc; ++j) {
+                    const uint32_t m = c == 0 ? j / G.nl : j, b = c == 0 ? j - m * G.nl : G.nl + c - 1;
+                    int16_t* blk = cf + (size_t)huff_block_index(G, m, b) * 64;
+                    pred += blk[0];
+                    if (pred < -32768 || pred > 32767) {
+                        bad = true;
+                        continue;
+                    }
+                    blk[0] = (int16_t)pred;
+                    int32_t sum = 0;
+                    for (int k = 0; k < 64; ++k) sum += (blk[k] < 0 ? -(int32_t)blk[k] : (int32_t)blk[k]) * (int32_t)q[c * 64 + k];
+                    if (sum > worst) worst = sum;
+                }
+            }
+            reason = bad ? MVLDM_JPEG_CORRUPT : worst > kJpegGuard ? MVLDM_JPEG_RANGE : MVLDM_JPEG_OK;
+            if (bad) worst = 0;
+        }
+        status[img * 4 + 0] = reason;
+        status[img * 4 + 1] = worst;
+        status[img * 4 + 2] = (int32_t)rounds_max;
+        status[img * 4 + 3] = 0;
+    }
+    delete[] buf[0];
+    delete[] buf[1];
+    delete[] entry;
+    delete[] done;
     return MVLDM_OK;
 }

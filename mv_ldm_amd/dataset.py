@@ -147,13 +147,14 @@ class RE10KScenes:
     that scale.  A view group's frames are decoded on the host, stacked, uploaded as uint8 and go through `ops.crop_shim` in one call;
     with `device_decode` (and `crop`) they go through `ops.jpeg_decode` instead -- the scan decoded by the library on the host, the rest
     on the device, PNG frames and frames the library refuses through `decode_image` into their slots -- and its device tensor feeds
-    the crop shim: the same bytes.
+    the crop shim: the same bytes.  `device_entropy` (implies `device_decode`): the host only removes the scan's byte stuffing and the
+    Huffman decoding runs on the device as well (`ops.jpeg_decode(entropy="device")`): a twelfth of the upload, the same bytes.
     `crop=False` leaves out the device: the groups then carry the decoded uint8 frames `[1, v, h, w, 3]` and the unscaled intrinsics
     (inspection, CPU tests)."""
 
     def __init__(self, root, stage: str = "test", index=None, image_shape: Tuple[int, int] = (256, 256), make_baseline_1: bool = True,
                  baseline_epsilon: float = 1e-3, max_fov: float = 100.0, scenes: Optional[Sequence[str]] = None, crop: bool = True,
-                 device_decode: bool = False):
+                 device_decode: bool = False, device_entropy: bool = False):
         if index is None:
             raise ValueError("RE10KScenes needs an evaluation index (load_index(path), or the path)")
         self.root = Path(root) / stage
@@ -162,7 +163,8 @@ class RE10KScenes:
         self.make_baseline_1, self.baseline_epsilon, self.max_fov = bool(make_baseline_1), float(baseline_epsilon), float(max_fov)
         self.scenes = None if scenes is None else list(scenes)
         self.crop = bool(crop)
-        self.device_decode = bool(device_decode) and self.crop
+        self.device_entropy = bool(device_entropy) and self.crop           # implies device_decode: the Huffman scan is decoded on the device too
+        self.device_decode = (bool(device_decode) or self.device_entropy) and self.crop
         if self.scenes is None:
             self.chunks = sorted(p for p in self.root.iterdir() if p.suffix == ".torch")
         else:
@@ -183,7 +185,7 @@ class RE10KScenes:
         if len(sizes) != 1 or h < h_out or w < w_out:
             print(f"Skipped bad example {example['key']}. Frame shapes were {sorted(sizes)}.")
             return None
-        images = ops.jpeg_decode(data) if self.device_decode else torch.from_numpy(np.stack(frames))
+        images = ops.jpeg_decode(data, entropy="device" if self.device_entropy else "host") if self.device_decode else torch.from_numpy(np.stack(frames))
         idx = torch.tensor(list(indices), dtype=torch.int64)
         bound = lambda v: (torch.full((len(indices),), v, dtype=torch.float32) / scale)[None]
         views = {"extrinsics": extrinsics[idx][None], "intrinsics": intrinsics[idx][None], "image": images[None],
@@ -475,6 +477,8 @@ class RE10KTrainLoader:
     code on the `decode_workers` threads (no GIL) into one pinned tensor of coefficients, the inverse DCT, upsampling and colour on the
     device -- and its uint8 device tensor feeds the crop shim, so no decoded frame exists on the host; PNG frames and JPEG frames the
     library refuses are decoded as before and uploaded into their slots, so a batch may mix them.  The bytes, and the draws, are the same.
+    `device_entropy` (implies `device_decode`): the workers only parse the markers and remove the byte stuffing; the Huffman scans are
+    decoded on the device too (`ops.jpeg_decode(entropy="device")`), at the price of one small status read-back per frame size.
 
     No rank sharding: like the reference's iterable dataset, every rank walks all chunks, under its own torch seed."""
 
@@ -483,7 +487,7 @@ class RE10KTrainLoader:
     def __init__(self, root, stage: str = "train", view_sampler: Optional[ViewSampler] = None, image_shape: Tuple[int, int] = (256, 256),
                  batch_size: int = 6, drop_last: bool = True, augment: bool = False, make_baseline_1: bool = True, baseline_epsilon: float = 1e-3,
                  max_fov: float = 100.0, scenes: Optional[Sequence[str]] = None, decode_workers: int = 0, crop: bool = True,
-                 random_transform_extrinsics: bool = False, device_decode: bool = False):
+                 random_transform_extrinsics: bool = False, device_decode: bool = False, device_entropy: bool = False):
         if stage not in ("train", "val"):
             raise ValueError(f"RE10KTrainLoader reads stage train or val, got {stage!r} (RE10KScenes reads test)")
         if random_transform_extrinsics:
@@ -499,7 +503,8 @@ class RE10KTrainLoader:
         self.make_baseline_1, self.baseline_epsilon, self.max_fov = bool(make_baseline_1), float(baseline_epsilon), float(max_fov)
         self.decode_workers = max(0, min(int(decode_workers), self.MAX_DECODE_WORKERS))
         self.crop = bool(crop)
-        self.device_decode = bool(device_decode) and self.crop
+        self.device_entropy = bool(device_entropy) and self.crop           # implies device_decode
+        self.device_decode = (bool(device_decode) or self.device_entropy) and self.crop
         self._pool = None
         if self.scenes is None:
             self.chunks = sorted(p for p in self.root.iterdir() if p.suffix == ".torch")
@@ -599,7 +604,8 @@ class RE10KTrainLoader:
             dev = torch.device("cuda", torch.cuda.current_device())
             for (h, w), members in by_size.items():
                 if self.device_decode:      # coefficients up, frames decoded on the device
-                    source = ops.jpeg_decode([blobs[i * v + t] for i in members for t in range(v)], pool=self._workers())
+                    source = ops.jpeg_decode([blobs[i * v + t] for i in members for t in range(v)], pool=self._workers(),
+                                             entropy="device" if self.device_entropy else "host")
                 else:
                     staged = torch.empty(len(members) * v, h, w, 3, dtype=torch.uint8, pin_memory=True)      # one upload per frame size
                     host = staged.numpy()

@@ -1150,18 +1150,195 @@ def jpeg_decode_coefs(coef: torch.Tensor, qt: torch.Tensor, h: int, w: int, samp
     return dst
 
 
-def jpeg_decode(blobs: Sequence[bytes], pool=None, device=None) -> torch.Tensor:
+class JpegScan(NamedTuple):
+    """`jpeg_scan_prepare` of one frame: `reason` 0 and the frame's part of `scan`, its `desc` and `tables` are what `jpeg_entropy_device`
+    takes; `_lib.JPEG_RESTART`: the frame has restart intervals and its scan is `jpeg_entropy`'s; any other reason as `jpeg_probe`."""
+    reason: int
+    info: JpegInfo
+    scan: np.ndarray
+    desc: np.ndarray
+    tables: np.ndarray
+
+
+def jpeg_scan_room(n: int) -> int:
+    """bytes of the packed scan buffer a frame of n encoded bytes (or a destuffed scan of n bytes) can take: padding included, a multiple of 16"""
+    return int(L.load().mvldm_jpeg_scan_room(n))
+
+
+def jpeg_entropy_chunk_subseqs() -> int:
+    """subsequences (one per thread) of a chunk of the device entropy decoder"""
+    return int(L.load().mvldm_jpeg_entropy_chunk_subseqs())
+
+
+def jpeg_scan_prepare(blob: bytes, scan: Optional[np.ndarray] = None, scan_off: int = 0, desc: Optional[np.ndarray] = None,
+                      tables: Optional[np.ndarray] = None) -> JpegScan:
+    """what the host still does for the device entropy decoder (`mvldm_jpeg_scan_prepare`): the markers, the destuffed scan into
+    `scan[scan_off:]` (uint8, room for `jpeg_scan_room(len(blob))` bytes behind the offset, a multiple of 16), the descriptor into `desc`
+    (int32 `[4]`) and the Huffman and quantisation tables into `tables` (uint8 `[_lib.JPEG_TABLE_BYTES]`).  Buffers left out are made.
+    Releases the GIL; keeps no state."""
+    if scan is None:
+        scan = np.zeros(scan_off + jpeg_scan_room(len(blob)), dtype=np.uint8)
+    if desc is None:
+        desc = np.zeros(4, dtype=np.int32)
+    if tables is None:
+        tables = np.zeros(L.JPEG_TABLE_BYTES, dtype=np.uint8)
+    assert scan.dtype == np.uint8 and scan.flags.c_contiguous and scan.ndim == 1
+    assert desc.dtype == np.int32 and desc.flags.c_contiguous and desc.size == 4
+    assert tables.dtype == np.uint8 and tables.flags.c_contiguous and tables.size == L.JPEG_TABLE_BYTES
+    info = (C.c_int32 * 8)()
+    rc = L.load().mvldm_jpeg_scan_prepare(blob, len(blob), scan.ctypes.data, scan_off, scan.size, desc.ctypes.data, tables.ctypes.data, info)
+    if rc < 0:
+        L.check(rc)
+    return JpegScan(rc, JpegInfo(*info), scan, desc, tables)
+
+
+def jpeg_entropy_emul(scan: np.ndarray, desc: np.ndarray, tables: np.ndarray, h: int, w: int, sampling: int, coef: Optional[np.ndarray] = None,
+                      qt: Optional[np.ndarray] = None, status: Optional[np.ndarray] = None, subseq_bits: int = 0, chunk_subseqs: int = 0):
+    """the device entropy decoder on the host (`mvldm_jpeg_entropy_emul_host`: the same step function, loops for threads) over the
+    frames of `desc` int32 `[n, 4]` -> (coef int16 `[n, jpeg_coef_count]`, qt uint16 `[n, 192]`, status int32 `[n, 4]`): tests and tools"""
+    desc, tables = desc.reshape(-1, 4), tables.reshape(-1, L.JPEG_TABLE_BYTES)
+    n, count = desc.shape[0], jpeg_coef_count(h, w, sampling)
+    assert scan.dtype == np.uint8 and scan.flags.c_contiguous and desc.dtype == np.int32 and desc.flags.c_contiguous
+    assert tables.dtype == np.uint8 and tables.flags.c_contiguous and tables.shape[0] == n and count > 0
+    coef = np.empty((n, count), dtype=np.int16) if coef is None else coef
+    qt = np.empty((n, 192), dtype=np.uint16) if qt is None else qt
+    status = np.empty((n, 4), dtype=np.int32) if status is None else status
+    assert coef.dtype == np.int16 and coef.flags.c_contiguous and coef.size == n * count and qt.dtype.itemsize == 2 and qt.flags.c_contiguous and qt.size == n * 192
+    assert status.dtype == np.int32 and status.flags.c_contiguous and status.size == n * 4
+    L.check(L.load().mvldm_jpeg_entropy_emul_host(scan.ctypes.data, scan.size, desc.ctypes.data, tables.ctypes.data, n, h, w, sampling, coef.ctypes.data,
+                                                  qt.ctypes.data, status.ctypes.data, subseq_bits, chunk_subseqs))
+    return coef, qt, status
+
+
+def jpeg_entropy_device(scan: torch.Tensor, desc: torch.Tensor, tables: torch.Tensor, h: int, w: int, sampling: int, coef: Optional[torch.Tensor] = None,
+                        qt: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None, subseq_bits: int = 0):
+    """`mvldm_jpeg_entropy_device`: the prepared frames of `desc` int32 `[n, 4]` (packed scans uint8, tables uint8 `[n, JPEG_TABLE_BYTES]`, all
+    on the device) -> (coef int16 `[n, jpeg_coef_count]`, qt int16 `[n, 192]`, status int32 `[n, 4]` = reason, largest S, rounds, 0): what
+    `jpeg_decode_coefs` takes.  A memset and two launches; nothing is allocated when the three outputs are given, and nothing is read
+    back, so the call can be captured."""
+    n, count = desc.shape[0], jpeg_coef_count(h, w, sampling)
+    assert scan.is_cuda and scan.is_contiguous() and scan.dtype == torch.uint8 and scan.dim() == 1
+    assert desc.is_cuda and desc.is_contiguous() and desc.dtype == torch.int32 and tuple(desc.shape) == (n, 4)
+    assert tables.is_cuda and tables.is_contiguous() and tables.dtype == torch.uint8 and tuple(tables.shape) == (n, L.JPEG_TABLE_BYTES) and count > 0
+    coef = torch.empty(n, count, dtype=torch.int16, device=scan.device) if coef is None else coef
+    qt = torch.empty(n, 192, dtype=torch.int16, device=scan.device) if qt is None else qt
+    status = torch.empty(n, 4, dtype=torch.int32, device=scan.device) if status is None else status
+    assert coef.is_cuda and coef.is_contiguous() and coef.dtype == torch.int16 and tuple(coef.shape) == (n, count)
+    assert qt.is_cuda and qt.is_contiguous() and qt.dtype == torch.int16 and tuple(qt.shape) == (n, 192)
+    assert status.is_cuda and status.is_contiguous() and status.dtype == torch.int32 and tuple(status.shape) == (n, 4)
+    L.check(L.load().mvldm_jpeg_entropy_device(scan.data_ptr(), scan.numel(), desc.data_ptr(), tables.data_ptr(), n, h, w, sampling, coef.data_ptr(),
+                                               qt.data_ptr(), status.data_ptr(), subseq_bits, stream()))
+    return coef, qt, status
+
+
+def jpeg_status_download(status: torch.Tensor) -> np.ndarray:
+    """the status words of a `jpeg_entropy_device` call on the host: the one read-back (and synchronisation) of `jpeg_decode(entropy="device")`"""
+    return status.cpu().numpy()
+
+
+def _jpeg_decode_device_entropy(blobs: Sequence[bytes], pool, dev) -> torch.Tensor:
+    from .dataset import decode_image
+    n = len(blobs)
+    infos = [jpeg_probe(b) for b in blobs]
+    groups: dict = {}
+    for i, info in enumerate(infos):
+        if info.supported:
+            groups.setdefault(info.sampling, []).append(i)
+    sizes = {(info.h, info.w) for info in infos if info.supported}
+    if len(sizes) > 1:
+        raise ValueError(f"jpeg_decode: frames of one size, got {sorted(sizes)}")
+    refused = [i for i, info in enumerate(infos) if not info.supported]
+    tb = L.JPEG_TABLE_BYTES
+    staged, jobs = {}, []
+    for sampling, members in groups.items():
+        m = len(members)
+        offs = [0]
+        for i in members:
+            offs.append(offs[-1] + jpeg_scan_room(len(blobs[i])))
+        buf = torch.empty(offs[-1] + m * (tb + 16), dtype=torch.uint8, pin_memory=True)         # [scans | tables | descriptors]: one upload
+        host = buf.numpy()
+        tables, desc = host[offs[-1]:offs[-1] + m * tb].reshape(m, tb), host[offs[-1] + m * tb:].view(np.int32).reshape(m, 4)
+        staged[sampling] = (buf, offs[-1])
+        jobs += [(i, host[:offs[-1]], offs[j], desc[j], tables[j]) for j, i in enumerate(members)]
+    run = lambda job: jpeg_scan_prepare(blobs[job[0]], *job[1:]).reason
+    reasons = dict(zip((job[0] for job in jobs), pool.map(run, jobs) if pool is not None and len(jobs) > 1 else [run(j) for j in jobs]))
+    refused += [i for i, reason in reasons.items() if reason not in (0, L.JPEG_RESTART)]
+    restart = {}                                # frames with restart intervals: the host's entropy pass, into the same device call
+    for sampling, members in groups.items():
+        mine = [i for i in members if reasons[i] == L.JPEG_RESTART]
+        if mine:
+            count = jpeg_coef_count(infos[mine[0]].h, infos[mine[0]].w, sampling)
+            rbuf = torch.empty(len(mine) * (count + 192), dtype=torch.int16, pin_memory=True)
+            rhost = rbuf.numpy()
+            rjobs = [(i, rhost[j * count:(j + 1) * count], rhost[len(mine) * count + j * 192:len(mine) * count + (j + 1) * 192]) for j, i in enumerate(mine)]
+            rrun = lambda job: jpeg_entropy(blobs[job[0]], job[1], job[2])[0]
+            rreasons = list(pool.map(rrun, rjobs)) if pool is not None and len(rjobs) > 1 else [rrun(j) for j in rjobs]
+            refused += [i for i, reason in zip(mine, rreasons) if reason != 0]
+            restart[sampling] = (mine, rbuf, count)
+    pending = []
+    dst = None
+    with torch.cuda.device(dev):
+        for sampling, members in groups.items():
+            h, w = infos[members[0]].h, infos[members[0]].w
+            buf, scan_bytes = staged[sampling]
+            m = len(members)
+            on_dev = buf.to(dev, non_blocking=True)
+            coef, qt, status = jpeg_entropy_device(on_dev[:scan_bytes], on_dev[scan_bytes + m * tb:].view(torch.int32).view(m, 4),
+                                                   on_dev[scan_bytes:scan_bytes + m * tb].view(m, tb), h, w, sampling)
+            if sampling in restart:             # after the kernels: their slots hold a refused frame's leftovers
+                mine, rbuf, count = restart[sampling]
+                at = torch.tensor([members.index(i) for i in mine], device=dev)
+                up = rbuf.to(dev, non_blocking=True)
+                coef[at] = up[:len(mine) * count].view(len(mine), count)
+                qt[at] = up[len(mine) * count:].view(len(mine), 192)
+            if dst is None:
+                dst = torch.empty(n, h, w, 3, dtype=torch.uint8, device=dev)
+            whole = m == n
+            out = jpeg_decode_coefs(coef, qt, h, w, sampling, dst if whole else None)
+            if not whole:
+                dst[torch.tensor(members, device=dev)] = out
+            pending.append((members, status))
+        for members, status in pending:         # one small read-back per layout; the host path has none
+            st = jpeg_status_download(status)
+            refused += [i for j, i in enumerate(members) if reasons[i] == 0 and st[j, 0] != 0]
+        late = [blobs[i] for i in sorted(refused)]
+        late = list(pool.map(decode_image, late)) if pool is not None and len(late) > 1 else [decode_image(b) for b in late]
+        sizes |= {f.shape[:2] for f in late}
+        if len(sizes) != 1:
+            raise ValueError(f"jpeg_decode: frames of one size, got {sorted(sizes)}")
+        (h, w), = sizes
+        if dst is None:
+            dst = torch.empty(n, h, w, 3, dtype=torch.uint8, device=dev)
+        if late:
+            host = torch.empty(len(late), h, w, 3, dtype=torch.uint8, pin_memory=True)
+            for j, f in enumerate(late):
+                host.numpy()[j] = f
+            dst[torch.tensor(sorted(refused), device=dev)] = host.to(dev, non_blocking=True)
+    return dst
+
+
+def jpeg_decode(blobs: Sequence[bytes], pool=None, device=None, entropy: str = "host") -> torch.Tensor:
     """encoded frames of ONE size -> uint8 `[n, h, w, 3]` on the current device, the bytes `Image.open(...).convert("RGB")` gives.
 
     Per frame the host parses the markers and decodes the Huffman scan (`mvldm_jpeg_entropy`: no Pillow, no GIL; on `pool`, a
     `concurrent.futures` executor, when one is given) straight into one pinned staging tensor per sampling layout; each layout is one
     upload and one `mvldm_jpeg_decode` call.  A frame the library refuses -- progressive, CMYK, outside the range guard, PNG, ... -- is
-    decoded by `dataset.decode_image` (Pillow) on the host and uploaded into its slot: the result never depends on which path ran."""
+    decoded by `dataset.decode_image` (Pillow) on the host and uploaded into its slot: the result never depends on which path ran.
+
+    `entropy="device"`: the host only parses the markers and removes the byte stuffing (`mvldm_jpeg_scan_prepare`, on `pool`) into one
+    pinned tensor per layout -- scans, tables, descriptors: about a twelfth of the coefficients -- and each layout is one upload, one
+    `mvldm_jpeg_entropy_device`, one `mvldm_jpeg_decode` and then ONE small download of the frames' status words: a synchronisation
+    with the device that the host path does not have.  A frame with restart intervals takes the host's entropy pass into the same device
+    call; a frame whose status is not 0, or that prepare refused, goes through `decode_image` as above.  The same bytes either way."""
     from .dataset import decode_image
     n = len(blobs)
     if n == 0:
         raise ValueError("jpeg_decode: no frames")
+    if entropy not in ("host", "device"):
+        raise ValueError(f"jpeg_decode: entropy {entropy!r} (host or device)")
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if entropy == "device":
+        return _jpeg_decode_device_entropy(blobs, pool, dev)
     infos = [jpeg_probe(b) for b in blobs]
     groups: dict = {}
     for i, info in enumerate(infos):

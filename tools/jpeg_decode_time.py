@@ -1,5 +1,5 @@
 """time the JPEG decoder (mv_ldm_amd/ops.py jpeg_decode: csrc/jpeg_host.cpp on the host, csrc/jpeg.hip on the device) next to Pillow:
-    python tools/jpeg_decode_time.py [--json OUT]
+    python tools/jpeg_decode_time.py [--entropy] [--json OUT]
 Two 360 x 640 4:2:0 quality-90 frames built here: "fixture" (tests/train_fixture.py's kind: 45 x 80 noise repeated 8 x each way, so every
 luma block is flat) and "photo" (smooth ramps plus +-12 of noise: every block has AC coefficients).  Per frame:
   * host: `mvldm_jpeg_entropy` (markers + Huffman scan into a reused buffer) on ONE thread, best of 5 passes of 20 calls, ms a frame; and
@@ -7,6 +7,11 @@ luma block is flat) and "photo" (smooth ramps plus +-12 of noise: every block ha
   * device: `mvldm_jpeg_decode` of n = 5 and n = 30 copies, coefficients already on the device, microseconds per frame.  "hot": the median
     of 5 windows of back-to-back calls between device events; "cold": one call per window behind a 640 MB fill that evicts the 256 MiB
     last-level cache, median of 7.
+  * `--entropy`: the Huffman scan on the device (`mvldm_jpeg_entropy_device`, csrc/jpeg_huff.hip), prepared scans already on the device: per
+    subseq_bits in 128, 256, 512, 1024 and n = 5, 30 the same hot / cold microseconds per frame, the rounds the worst chunk took and the
+    bytes uploaded per frame (scan with padding + tables + descriptor); next to it, IN THE SAME RUN, the host's entropy pass spread over a
+    pool of 16 threads (wall time of 30 frames / 30) and `mvldm_jpeg_scan_prepare` on one thread.  Coefficients are checked against the
+    host's before anything is timed.
 The device result is checked against Pillow's before anything is timed.  No threshold: the figures go to DESIGN.md and profiles/."""
 import json, os, sys, time
 from io import BytesIO
@@ -82,6 +87,42 @@ for name, pixels in FRAMES.items():
         cold = sorted(cold)[3]
         r[f"device_n{n}"] = {"hot_us_per_frame": round(hot / n, 3), "cold_us_per_frame": round(cold / n, 3), "hot_us_per_call": round(hot, 2),
                              "cold_us_per_call": round(cold, 2), "coefficient_bytes_per_frame": count * 2}
+    if "--entropy" in sys.argv:
+        from concurrent.futures import ThreadPoolExecutor
+        from mv_ldm_amd import _lib
+        e = r["device_entropy"] = {}
+        p = ops.jpeg_scan_prepare(blob)
+        assert p.reason == 0
+        room = int(p.desc[2])
+        e["scan_bytes"] = int(p.desc[1]) // 8
+        e["upload_bytes_per_frame"] = room + _lib.JPEG_TABLE_BYTES + 16
+        e["prepare_ms_per_frame"] = round(best_ms(lambda: ops.jpeg_scan_prepare(blob, p.scan, 0, p.desc, p.tables)), 4)
+        with ThreadPoolExecutor(16) as pool:
+            bufs = [(np.zeros(count, dtype=np.int16), np.zeros(192, dtype=np.int16)) for _ in range(30)]
+            spread = lambda: list(pool.map(lambda b: ops.jpeg_entropy(blob, b[0], b[1]), bufs))
+            e["host_entropy_16_workers_ms_per_frame"] = round(best_ms(spread) / 30, 4)
+        for n in (5, 30):
+            scan = torch.from_numpy(p.scan[:room]).cuda().repeat(n)
+            desc = torch.from_numpy(p.desc).cuda().repeat(n, 1)
+            desc[:, 0] = torch.arange(n, device="cuda", dtype=torch.int32) * room
+            tables = torch.from_numpy(p.tables).cuda().repeat(n, 1)
+            dc, dq = torch.empty(n, count, dtype=torch.int16, device="cuda"), torch.empty(n, 192, dtype=torch.int16, device="cuda")
+            st = torch.empty(n, 4, dtype=torch.int32, device="cuda")
+            for sb in (128, 256, 512, 1024):
+                call = lambda: ops.jpeg_entropy_device(scan, desc, tables, H, W, 3, dc, dq, st, subseq_bits=sb)
+                call()
+                torch.cuda.synchronize()
+                status = st.cpu().numpy()
+                assert (status[:, 0] == 0).all() and (status[:, 1] == max_s).all(), status
+                assert all(np.array_equal(dc[i].cpu().numpy(), coef) and np.array_equal(dq[i].cpu().numpy(), qt) for i in (0, n - 1)), "not the host's coefficients"
+                hot = sorted(event_us(call, 20) for _ in range(5))[2]
+                cold = []
+                for _ in range(7):
+                    flush.fill_(1)
+                    cold.append(event_us(call, 1))
+                cold = sorted(cold)[3]
+                e[f"n{n}_bits{sb}"] = {"hot_us_per_frame": round(hot / n, 3), "cold_us_per_frame": round(cold / n, 3), "hot_us_per_call": round(hot, 2),
+                                       "cold_us_per_call": round(cold, 2), "rounds": int(status[:, 2].max())}
     print(name, json.dumps(r), flush=True)
 if "--json" in sys.argv:
     with open(sys.argv[sys.argv.index("--json") + 1], "w") as f:
