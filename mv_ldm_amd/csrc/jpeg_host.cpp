@@ -248,6 +248,21 @@ inline bool receive_extend(Bits* b, int s, int* out) {
     return true;
 }
 
+// What follows the entropy-coded bytes, at d[p]: fill bytes (FF), then EOI.  Returns a reason: running off the end is TRUNCATED; no
+// marker at all at p, or another marker (more scans, tables or restart markers than the frame has MCUs for), is CORRUPT.
+int expect_eoi(const uint8_t* d, size_t len, size_t p) {
+    const size_t at = p;
+    while (p < len && d[p] == 0xFF) ++p;
+    if (p >= len) return MVLDM_JPEG_TRUNCATED;
+    return p == at || d[p] != 0xD9 ? MVLDM_JPEG_CORRUPT : MVLDM_JPEG_OK;
+}
+
+// The three components' quantisation rows (natural order, zeros for a component the frame does not have) as the device half takes them
+void quant_rows(const Header& hd, const JpegLayout& L, uint16_t* qt) {
+    for (int c = 0; c < 3; ++c)
+        for (int k = 0; k < 64; ++k) qt[c * 64 + k] = c < L.ncomp ? hd.qt[hd.comp[c].tq][k] : 0;
+}
+
 // The scan.  coef: room for L.blocks * 64 values (checked by the caller).  Returns a reason.
 int decode_scan(const uint8_t* d, size_t len, const Header& hd, const JpegLayout& L, int16_t* coef, int32_t* max_s) {
     Bits b{d, hd.scan, len};
@@ -317,10 +332,8 @@ int decode_scan(const uint8_t* d, size_t len, const Header& hd, const JpegLayout
     // what follows the last MCU: padding bits, then EOI
     b.fill();
     if (!b.stop || b.n >= 8) return MVLDM_JPEG_CORRUPT;
-    size_t p = b.pos;
-    while (p < len && d[p] == 0xFF) ++p;
-    if (p >= len) return MVLDM_JPEG_TRUNCATED;
-    if (p == b.pos || d[p] != 0xD9) return MVLDM_JPEG_CORRUPT;      // more scans, tables or restart markers than the frame has MCUs for
+    const int tail = expect_eoi(d, len, b.pos);
+    if (tail != MVLDM_JPEG_OK) return tail;
     if (max_s) *max_s = worst;
     return worst > kJpegGuard ? MVLDM_JPEG_RANGE : MVLDM_JPEG_OK;
 }
@@ -386,8 +399,7 @@ extern "C" int mvldm_jpeg_entropy(const uint8_t* data, size_t len, int16_t* coef
     if (!jpeg_layout(hd.h, hd.w, hd.sampling, &L)) return MVLDM_JPEG_SIZE;
     if (coef_len < (size_t)L.blocks * 64)
         return set_error(MVLDM_ERR_ARG, "jpeg_entropy: room for %zu coefficients, the %d x %d frame has %zu", coef_len, hd.h, hd.w, (size_t)L.blocks * 64);
-    for (int c = 0; c < 3; ++c)
-        for (int k = 0; k < 64; ++k) qt[c * 64 + k] = c < L.ncomp ? hd.qt[hd.comp[c].tq][k] : 0;
+    quant_rows(hd, L, qt);
     return decode_scan(data, len, hd, L, coef, max_s);
 }
 
@@ -459,22 +471,19 @@ extern "C" int mvldm_jpeg_scan_prepare(const uint8_t* data, size_t len, uint8_t*
         }
         out[n++] = b;                           // n <= i - hd.scan < len
     }
-    while (i < len && data[i] == 0xFF) ++i;     // the marker: fill bytes, then EOI (decode_scan's tail)
-    if (i >= len) return MVLDM_JPEG_TRUNCATED;
-    if (data[i] != 0xD9) return MVLDM_JPEG_CORRUPT;
+    const int tail = expect_eoi(data, len, i);  // i sits on the marker's FF
+    if (tail != MVLDM_JPEG_OK) return tail;
     const size_t room = huff_scan_room(n);      // <= huff_scan_room(len)
     memset(out + n, 0, room - n);
     desc[1] = (int32_t)(n * 8);
     desc[2] = (int32_t)room;
     memset(tables, 0, (size_t)kHuffBlobBytes);
-    uint16_t qt[192];
-    for (int c = 0; c < 3; ++c) {
-        if (c < L.ncomp) {
-            huff_blob(hd.dc[hd.comp[c].td], tables + (size_t)(2 * c) * kHuffTabBytes);
-            huff_blob(hd.ac[hd.comp[c].ta], tables + (size_t)(2 * c + 1) * kHuffTabBytes);
-        }
-        for (int k = 0; k < 64; ++k) qt[c * 64 + k] = c < L.ncomp ? hd.qt[hd.comp[c].tq][k] : 0;
+    for (int c = 0; c < L.ncomp; ++c) {
+        huff_blob(hd.dc[hd.comp[c].td], tables + (size_t)(2 * c) * kHuffTabBytes);
+        huff_blob(hd.ac[hd.comp[c].ta], tables + (size_t)(2 * c + 1) * kHuffTabBytes);
     }
+    uint16_t qt[192];
+    quant_rows(hd, L, qt);
     memcpy(tables + kHuffTabsBytes, qt, sizeof(qt));
     return MVLDM_JPEG_OK;
 }

@@ -8,7 +8,8 @@ The images take the reference's path bit for bit -- 8-bit decode, PIL's LANCZOS 
 resize, crop and division run on the device (`ops.crop_shim`, csrc/cropshim.hip).  The container decode (JPEG through Pillow, PNG
 through `image_io`) runs on the host by default; with `device_decode=True` a JPEG frame's Huffman scan is decoded by the library's own
 host code and everything after it -- dequantisation, inverse DCT, upsampling, colour -- on the device (`ops.jpeg_decode`, csrc/jpeg.hip),
-bit for bit with Pillow, so no decoded frame exists on the host.  Cameras follow the reference's host arithmetic.  `rescale_and_crop`, `apply_crop_shim_to_views`
+bit for bit with Pillow, so no decoded frame exists on the host; with `device_entropy=True` the Huffman scan is decoded on the device
+too (csrc/jpeg_huff.hip).  Cameras follow the reference's host arithmetic.  `rescale_and_crop`, `apply_crop_shim_to_views`
 and `apply_crop_shim` are drop-ins for a loader that already produces the reference's `BatchedExample` dicts.
 
 Training reads the same chunks through `RE10KTrainLoader`, `DatasetRE10k.__iter__` for `stage = "train" | "val"`: shuffled chunks and
@@ -24,7 +25,7 @@ reversed (`ops.crop_shim(flip=)`), so a whole micro-batch of mirrored and unmirr
 `apply_augmentation_and_crop_shim` is the drop-in for the reference's `apply_augmentation_shim` followed by `apply_crop_shim`.
 
 Out of scope: the `all` / `random` view samplers, the random-transform shim (`random_transform_extrinsics`, off in the released config: it
-needs an SO(3) sampler), the re10kv2 / CO3D / Objaverse readers, entropy decoding of JPEG on the device, Lightning's DataModule."""
+needs an SO(3) sampler), the re10kv2 / CO3D / Objaverse readers, Lightning's DataModule."""
 from __future__ import annotations
 
 import json
@@ -40,10 +41,10 @@ _PNG = b"\x89PNG\r\n\x1a\n"
 
 
 # ------------------------------------------------------------------------------------------ the crop shim
-def rescale_and_crop(images: torch.Tensor, intrinsics: torch.Tensor, shape: Tuple[int, int]):
+def rescale_and_crop(images: torch.Tensor, intrinsics: torch.Tensor, shape: Tuple[int, int], flip: bool = False):
     """crop_shim.py:51-75 + `center_crop`: images `[*batch, 3, h, w]` (fp32 in [0, 1]; or decoded uint8 `[*batch, h, w, 3]`), intrinsics
     `[*batch, 3, 3]` -> (fp32 `[*batch, 3, h_out, w_out]` on the device, intrinsics with fx, fy rescaled).  A CPU tensor is moved to the
-    current device; the intrinsics stay where they are and are changed on a clone."""
+    current device; the intrinsics stay where they are and are changed on a clone.  `flip`: the shim reads every image mirrored."""
     from . import ops
     dev = images.device if images.is_cuda else torch.device("cuda", torch.cuda.current_device())
     if images.dtype == torch.uint8:
@@ -53,8 +54,9 @@ def rescale_and_crop(images: torch.Tensor, intrinsics: torch.Tensor, shape: Tupl
         *batch, c, h, w = images.shape
         flat = images.reshape(-1, c, h, w).float()
     assert c == 3, f"the crop shim takes RGB images, got {c} channels"
-    out, (h_scaled, w_scaled) = ops.crop_shim(flat.to(dev).contiguous(), shape)
-    return out.reshape(*batch, 3, *out.shape[-2:]), crop_intrinsics(intrinsics, (h_scaled, w_scaled), shape)
+    flags = torch.full((flat.shape[0],), int(flip), dtype=torch.uint8, device=dev) if flip else None
+    out, scaled = ops.crop_shim(flat.to(dev).contiguous(), shape, flip=flags)
+    return out.reshape(*batch, 3, *out.shape[-2:]), crop_intrinsics(intrinsics, scaled, shape)
 
 
 def crop_intrinsics(intrinsics: torch.Tensor, scaled: Tuple[int, int], shape: Tuple[int, int]) -> torch.Tensor:
@@ -133,7 +135,63 @@ def _frame_bytes(frame) -> bytes:
 
 
 # ------------------------------------------------------------------------------------------ the reader
-class RE10KScenes:
+class _RE10KReader:
+    """what `RE10KScenes` and `RE10KTrainLoader` share: which chunks are read (`root/*.torch` sorted, or those `root/index.json` names
+    for `scenes`), how their frames are decoded, and the per-scene steps of `DatasetRE10k.__iter__`.  Nothing here draws a random number."""
+
+    def __init__(self, root, scenes, image_shape, make_baseline_1, baseline_epsilon, max_fov, crop, device_decode, device_entropy):
+        self.root = Path(root)
+        self.scenes = None if scenes is None else list(scenes)
+        self.image_shape = (int(image_shape[0]), int(image_shape[1]))
+        self.make_baseline_1, self.baseline_epsilon, self.max_fov = bool(make_baseline_1), float(baseline_epsilon), float(max_fov)
+        self.crop = bool(crop)
+        self.device_entropy = bool(device_entropy) and self.crop           # implies device_decode: the Huffman scan is decoded on the device too
+        self.device_decode = (bool(device_decode) or self.device_entropy) and self.crop
+        self.entropy = "device" if self.device_entropy else "host"         # `ops.jpeg_decode`'s mode
+        if self.scenes is None:
+            self.chunks = sorted(p for p in self.root.iterdir() if p.suffix == ".torch")
+        else:
+            with open(self.root / "index.json") as f:
+                where = json.load(f)
+            self.chunks = [self.root / where[name] for name in self.scenes]
+
+    def _scenes(self, chunk_path, order=iter) -> Iterator[tuple]:
+        """(example, extrinsics, intrinsics) of the chunk's scenes (those of `scenes`) in `order`, without a field of view above `max_fov`"""
+        chunk = torch.load(chunk_path, weights_only=True)
+        for example in order(chunk if self.scenes is None else [x for x in chunk if x["key"] in self.scenes]):
+            extrinsics, intrinsics = convert_poses(example["cameras"])
+            if not (get_fov(intrinsics).rad2deg() > self.max_fov).any():
+                yield example, extrinsics, intrinsics
+
+    def _baseline(self, scene: str, extrinsics: torch.Tensor, context):
+        """near / far's scale: 1, or with two context views (rows `context`) and `make_baseline_1` their distance, the scene's
+        translations divided by it IN PLACE; None (with the message) when it is below `baseline_epsilon`"""
+        context_extrinsics = extrinsics[context]
+        if context_extrinsics.shape[0] != 2 or not self.make_baseline_1:
+            return 1
+        a, b = context_extrinsics[:, :3, 3]
+        scale = (a - b).norm()
+        if scale < self.baseline_epsilon:
+            print(f"Skipped {scene} because of insufficient baseline {scale:.6f}")
+            return None
+        extrinsics[:, :3, 3] /= scale
+        return scale
+
+    def _frame_hw(self, scene: str, sizes: set):
+        """(h, w) of frames whose shape tuples are `sizes`, or None (with the message): they disagree, or are smaller than `image_shape`"""
+        h, w = next(iter(sizes))[:2]
+        if len(sizes) != 1 or h < self.image_shape[0] or w < self.image_shape[1]:
+            print(f"Skipped bad example {scene}. Frame shapes were {sorted(sizes)}.")
+            return None
+        return h, w
+
+
+def _bound(value: float, count: int, scale) -> torch.Tensor:
+    """near or far (`NEAR`, `FAR`) of `count` views over the baseline's scale"""
+    return torch.full((count,), value, dtype=torch.float32) / scale
+
+
+class RE10KScenes(_RE10KReader):
     """Iterable over `BatchedExample`-shaped dicts with b = 1 (the schema of `generate.synthetic_example`, plus `target["image"]`) read
     from `root/<stage>/*.torch` in sorted order: `DatasetRE10k.__iter__` (dataset_re10k.py:79-171) with the `evaluation` view sampler.
 
@@ -157,62 +215,33 @@ class RE10KScenes:
                  device_decode: bool = False, device_entropy: bool = False):
         if index is None:
             raise ValueError("RE10KScenes needs an evaluation index (load_index(path), or the path)")
-        self.root = Path(root) / stage
+        super().__init__(Path(root) / stage, scenes, image_shape, make_baseline_1, baseline_epsilon, max_fov, crop, device_decode, device_entropy)
         self.index = load_index(index) if isinstance(index, (str, Path)) else {k: v for k, v in index.items() if v}
-        self.image_shape = (int(image_shape[0]), int(image_shape[1]))
-        self.make_baseline_1, self.baseline_epsilon, self.max_fov = bool(make_baseline_1), float(baseline_epsilon), float(max_fov)
-        self.scenes = None if scenes is None else list(scenes)
-        self.crop = bool(crop)
-        self.device_entropy = bool(device_entropy) and self.crop           # implies device_decode: the Huffman scan is decoded on the device too
-        self.device_decode = (bool(device_decode) or self.device_entropy) and self.crop
-        if self.scenes is None:
-            self.chunks = sorted(p for p in self.root.iterdir() if p.suffix == ".torch")
-        else:
-            with open(self.root / "index.json") as f:
-                where = json.load(f)
-            self.chunks = [self.root / where[name] for name in self.scenes]
 
     def _views(self, example: dict, indices: Sequence[int], extrinsics, intrinsics, scale) -> Optional[dict]:
-        h_out, w_out = self.image_shape
-        if self.device_decode:
-            from . import ops
-            data = [_frame_bytes(example["images"][i]) for i in indices]
-            sizes = {(*_frame_size(d, probe=True), 3) for d in data}
-        else:
-            frames = [decode_image(_frame_bytes(example["images"][i])) for i in indices]
-            sizes = {f.shape for f in frames}
-        h, w, _ = next(iter(sizes))
-        if len(sizes) != 1 or h < h_out or w < w_out:
-            print(f"Skipped bad example {example['key']}. Frame shapes were {sorted(sizes)}.")
+        data = [_frame_bytes(example["images"][i]) for i in indices]
+        frames = None if self.device_decode else [decode_image(d) for d in data]
+        sizes = {(*_frame_size(d, probe=True), 3) for d in data} if frames is None else {f.shape for f in frames}
+        if self._frame_hw(example["key"], sizes) is None:
             return None
-        images = ops.jpeg_decode(data, entropy="device" if self.device_entropy else "host") if self.device_decode else torch.from_numpy(np.stack(frames))
+        if frames is None:
+            from . import ops
+            images = ops.jpeg_decode(data, entropy=self.entropy)
+        else:
+            images = torch.from_numpy(np.stack(frames))
         idx = torch.tensor(list(indices), dtype=torch.int64)
-        bound = lambda v: (torch.full((len(indices),), v, dtype=torch.float32) / scale)[None]
         views = {"extrinsics": extrinsics[idx][None], "intrinsics": intrinsics[idx][None], "image": images[None],
-                 "near": bound(NEAR), "far": bound(FAR), "index": idx[None]}
+                 "near": _bound(NEAR, len(indices), scale)[None], "far": _bound(FAR, len(indices), scale)[None], "index": idx[None]}
         return apply_crop_shim_to_views(views, self.image_shape) if self.crop else views
 
     def __iter__(self) -> Iterator[dict]:
         for chunk_path in self.chunks:
-            chunk = torch.load(chunk_path, weights_only=True)
-            if self.scenes is not None:
-                chunk = [x for x in chunk if x["key"] in self.scenes]
-            for example in chunk:
-                extrinsics, intrinsics = convert_poses(example["cameras"])
+            for example, extrinsics, intrinsics in self._scenes(chunk_path):
                 scene = example["key"]
-                if (get_fov(intrinsics).rad2deg() > self.max_fov).any():
-                    continue
                 for entry in self.index.get(scene) or ():
-                    context_extrinsics = extrinsics[list(entry["context"])]
-                    if context_extrinsics.shape[0] == 2 and self.make_baseline_1:
-                        a, b = context_extrinsics[:, :3, 3]
-                        scale = (a - b).norm()
-                        if scale < self.baseline_epsilon:
-                            print(f"Skipped {scene} because of insufficient baseline {scale:.6f}")
-                            continue
-                        extrinsics[:, :3, 3] /= scale
-                    else:
-                        scale = 1
+                    scale = self._baseline(scene, extrinsics, list(entry["context"]))
+                    if scale is None:
+                        continue
                     sample = {"scene": [scene]}
                     for view_type in ("context", "target"):
                         sample[view_type] = self._views(example, entry[view_type], extrinsics, intrinsics, scale)
@@ -401,21 +430,9 @@ def reflect_extrinsics(extrinsics: torch.Tensor) -> torch.Tensor:
 def _crop_views_flagged(views: dict, shape: Tuple[int, int], flip: bool) -> dict:
     """`apply_crop_shim_to_views` of a view group whose images are mirrored first when `flip`: the flag goes to the device shim, the
     extrinsics are reflected here"""
-    from . import ops
-    images = views["image"]
-    dev = images.device if images.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    if images.dtype == torch.uint8:
-        *batch, h, w, c = images.shape
-        flat = images.reshape(-1, h, w, c)
-    else:
-        *batch, c, h, w = images.shape
-        flat = images.reshape(-1, c, h, w).float()
-    assert c == 3, f"the crop shim takes RGB images, got {c} channels"
-    flags = torch.full((flat.shape[0],), int(flip), dtype=torch.uint8, device=dev) if flip else None
-    out, scaled = ops.crop_shim(flat.to(dev).contiguous(), shape, flip=flags)
+    images, intrinsics = rescale_and_crop(views["image"], views["intrinsics"], shape, flip)
     extrinsics = reflect_extrinsics(views["extrinsics"]) if flip else views["extrinsics"]
-    return {**views, "image": out.reshape(*batch, 3, *out.shape[-2:]), "extrinsics": extrinsics,
-            "intrinsics": crop_intrinsics(views["intrinsics"], scaled, shape)}
+    return {**views, "image": images, "extrinsics": extrinsics, "intrinsics": intrinsics}
 
 
 def apply_augmentation_and_crop_shim(example: dict, shape: Tuple[int, int], generator: Optional[torch.Generator] = None) -> dict:
@@ -452,7 +469,7 @@ def _shuffle(items: list) -> list:
     return [items[i] for i in torch.randperm(len(items))]
 
 
-class RE10KTrainLoader:
+class RE10KTrainLoader(_RE10KReader):
     """`DatasetRE10k.__iter__` (dataset_re10k.py:79-171) for `stage = "train" | "val"` behind the reference's train `DataLoader`
     (data_module.py:87-100: batches of `batch_size`, `drop_last`), one pass over the chunks per `iter()`.
 
@@ -495,75 +512,50 @@ class RE10KTrainLoader:
         if view_sampler is None:            # config/experiment/baseline.yaml:16-20
             view_sampler = ViewSamplerBounded(num_context_views=2, num_target_views=3, min_distance_between_context_views=50,
                                               max_distance_between_context_views=180, stage=stage)
+        super().__init__(Path(root) / ("test" if stage == "val" or scenes is not None else stage),     # `data_stage`
+                         scenes, image_shape, make_baseline_1, baseline_epsilon, max_fov, crop, device_decode, device_entropy)
         self.stage, self.view_sampler = stage, view_sampler
-        self.scenes = None if scenes is None else list(scenes)
-        self.root = Path(root) / ("test" if stage == "val" or self.scenes is not None else stage)     # `data_stage`
-        self.image_shape = (int(image_shape[0]), int(image_shape[1]))
         self.batch_size, self.drop_last, self.augment = int(batch_size), bool(drop_last), bool(augment)
-        self.make_baseline_1, self.baseline_epsilon, self.max_fov = bool(make_baseline_1), float(baseline_epsilon), float(max_fov)
         self.decode_workers = max(0, min(int(decode_workers), self.MAX_DECODE_WORKERS))
-        self.crop = bool(crop)
-        self.device_entropy = bool(device_entropy) and self.crop           # implies device_decode
-        self.device_decode = (bool(device_decode) or self.device_entropy) and self.crop
         self._pool = None
-        if self.scenes is None:
-            self.chunks = sorted(p for p in self.root.iterdir() if p.suffix == ".torch")
-        else:
-            with open(self.root / "index.json") as f:
-                where = json.load(f)
-            self.chunks = [self.root / where[name] for name in self.scenes]
 
     # ---- the host-only pass
     def _records(self, decode: bool) -> Iterator[dict]:
         from .ops import crop_geometry
         self.chunks = _shuffle(self.chunks)
         for chunk_path in self.chunks:
-            chunk = torch.load(chunk_path, weights_only=True)
-            if self.scenes is not None:
-                chunk = [x for x in chunk if x["key"] in self.scenes]
-            for example in _shuffle(chunk):
-                extrinsics, intrinsics = convert_poses(example["cameras"])
+            for example, extrinsics, intrinsics in self._scenes(chunk_path, _shuffle):
                 scene = example["key"]
-                if (get_fov(intrinsics).rad2deg() > self.max_fov).any():
-                    continue
                 try:
                     view_indices = self.view_sampler.sample(scene, extrinsics.shape[0])
                 except ValueError:          # not enough frames
                     continue
                 for view_index in view_indices:
-                    context_extrinsics = extrinsics[view_index.context]
-                    if context_extrinsics.shape[0] == 2 and self.make_baseline_1:
-                        a, b = context_extrinsics[:, :3, 3]
-                        scale = (a - b).norm()
-                        if scale < self.baseline_epsilon:
-                            print(f"Skipped {scene} because of insufficient baseline {scale:.6f}")
-                            continue
-                        extrinsics[:, :3, 3] /= scale
-                    else:
-                        scale = 1
+                    scale = self._baseline(scene, extrinsics, view_index.context)
+                    if scale is None:
+                        continue
                     groups = {k: v for k, v in view_index._asdict().items() if v is not None}
                     data = {k: [_frame_bytes(example["images"][i.item()]) for i in v] for k, v in groups.items()}
-                    sizes = {_frame_size(d, probe=self.device_decode and not decode) for ds in data.values() for d in ds}
-                    h, w = next(iter(sizes))
-                    if len(sizes) != 1 or h < self.image_shape[0] or w < self.image_shape[1]:
-                        print(f"Skipped bad example {scene}. Frame shapes were {sorted(sizes)}.")
+                    size = self._frame_hw(scene, {_frame_size(d, probe=self.device_decode and not decode) for ds in data.values() for d in ds})
+                    if size is None:
                         continue
+                    h, w = size
                     flip = False
                     if self.stage == "train" and self.augment:
                         flip = not bool(torch.rand(tuple()) < 0.5)
                     h_s, w_s, _, _ = crop_geometry(h, w, self.image_shape)
                     record = {"scene": scene, "flip": flip}
                     for k, idx in groups.items():
-                        bound = lambda v: torch.full((len(idx),), v, dtype=torch.float32) / scale
                         ext = extrinsics[idx]
                         record[k] = {"extrinsics": reflect_extrinsics(ext) if flip else ext,
                                      "intrinsics": crop_intrinsics(intrinsics[idx], (h_s, w_s), self.image_shape),
-                                     "near": bound(NEAR), "far": bound(FAR), "index": idx, "size": (h, w)}
+                                     "near": _bound(NEAR, len(idx), scale), "far": _bound(FAR, len(idx), scale), "index": idx, "size": (h, w)}
                         if decode:
                             record[k]["frames"] = np.stack([decode_image(d) for d in data[k]])
                         else:
                             record[k]["data"] = data[k]
                     yield record
+
 
     def examples(self) -> Iterator[dict]:
         return self._records(decode=True)
@@ -604,8 +596,7 @@ class RE10KTrainLoader:
             dev = torch.device("cuda", torch.cuda.current_device())
             for (h, w), members in by_size.items():
                 if self.device_decode:      # coefficients up, frames decoded on the device
-                    source = ops.jpeg_decode([blobs[i * v + t] for i in members for t in range(v)], pool=self._workers(),
-                                             entropy="device" if self.device_entropy else "host")
+                    source = ops.jpeg_decode([blobs[i * v + t] for i in members for t in range(v)], pool=self._workers(), entropy=self.entropy)
                 else:
                     staged = torch.empty(len(members) * v, h, w, 3, dtype=torch.uint8, pin_memory=True)      # one upload per frame size
                     host = staged.numpy()

@@ -1236,85 +1236,36 @@ def jpeg_status_download(status: torch.Tensor) -> np.ndarray:
     return status.cpu().numpy()
 
 
-def _jpeg_decode_device_entropy(blobs: Sequence[bytes], pool, dev) -> torch.Tensor:
-    from .dataset import decode_image
-    n = len(blobs)
-    infos = [jpeg_probe(b) for b in blobs]
-    groups: dict = {}
-    for i, info in enumerate(infos):
-        if info.supported:
-            groups.setdefault(info.sampling, []).append(i)
-    sizes = {(info.h, info.w) for info in infos if info.supported}
-    if len(sizes) > 1:
-        raise ValueError(f"jpeg_decode: frames of one size, got {sorted(sizes)}")
-    refused = [i for i, info in enumerate(infos) if not info.supported]
-    tb = L.JPEG_TABLE_BYTES
-    staged, jobs = {}, []
-    for sampling, members in groups.items():
-        m = len(members)
-        offs = [0]
-        for i in members:
-            offs.append(offs[-1] + jpeg_scan_room(len(blobs[i])))
-        buf = torch.empty(offs[-1] + m * (tb + 16), dtype=torch.uint8, pin_memory=True)         # [scans | tables | descriptors]: one upload
-        host = buf.numpy()
-        tables, desc = host[offs[-1]:offs[-1] + m * tb].reshape(m, tb), host[offs[-1] + m * tb:].view(np.int32).reshape(m, 4)
-        staged[sampling] = (buf, offs[-1])
-        jobs += [(i, host[:offs[-1]], offs[j], desc[j], tables[j]) for j, i in enumerate(members)]
-    run = lambda job: jpeg_scan_prepare(blobs[job[0]], *job[1:]).reason
-    reasons = dict(zip((job[0] for job in jobs), pool.map(run, jobs) if pool is not None and len(jobs) > 1 else [run(j) for j in jobs]))
-    refused += [i for i, reason in reasons.items() if reason not in (0, L.JPEG_RESTART)]
-    restart = {}                                # frames with restart intervals: the host's entropy pass, into the same device call
-    for sampling, members in groups.items():
-        mine = [i for i in members if reasons[i] == L.JPEG_RESTART]
-        if mine:
-            count = jpeg_coef_count(infos[mine[0]].h, infos[mine[0]].w, sampling)
-            rbuf = torch.empty(len(mine) * (count + 192), dtype=torch.int16, pin_memory=True)
-            rhost = rbuf.numpy()
-            rjobs = [(i, rhost[j * count:(j + 1) * count], rhost[len(mine) * count + j * 192:len(mine) * count + (j + 1) * 192]) for j, i in enumerate(mine)]
-            rrun = lambda job: jpeg_entropy(blobs[job[0]], job[1], job[2])[0]
-            rreasons = list(pool.map(rrun, rjobs)) if pool is not None and len(rjobs) > 1 else [rrun(j) for j in rjobs]
-            refused += [i for i, reason in zip(mine, rreasons) if reason != 0]
-            restart[sampling] = (mine, rbuf, count)
-    pending = []
-    dst = None
-    with torch.cuda.device(dev):
-        for sampling, members in groups.items():
-            h, w = infos[members[0]].h, infos[members[0]].w
-            buf, scan_bytes = staged[sampling]
-            m = len(members)
-            on_dev = buf.to(dev, non_blocking=True)
-            coef, qt, status = jpeg_entropy_device(on_dev[:scan_bytes], on_dev[scan_bytes + m * tb:].view(torch.int32).view(m, 4),
-                                                   on_dev[scan_bytes:scan_bytes + m * tb].view(m, tb), h, w, sampling)
-            if sampling in restart:             # after the kernels: their slots hold a refused frame's leftovers
-                mine, rbuf, count = restart[sampling]
-                at = torch.tensor([members.index(i) for i in mine], device=dev)
-                up = rbuf.to(dev, non_blocking=True)
-                coef[at] = up[:len(mine) * count].view(len(mine), count)
-                qt[at] = up[len(mine) * count:].view(len(mine), 192)
-            if dst is None:
-                dst = torch.empty(n, h, w, 3, dtype=torch.uint8, device=dev)
-            whole = m == n
-            out = jpeg_decode_coefs(coef, qt, h, w, sampling, dst if whole else None)
-            if not whole:
-                dst[torch.tensor(members, device=dev)] = out
-            pending.append((members, status))
-        for members, status in pending:         # one small read-back per layout; the host path has none
-            st = jpeg_status_download(status)
-            refused += [i for j, i in enumerate(members) if reasons[i] == 0 and st[j, 0] != 0]
-        late = [blobs[i] for i in sorted(refused)]
-        late = list(pool.map(decode_image, late)) if pool is not None and len(late) > 1 else [decode_image(b) for b in late]
-        sizes |= {f.shape[:2] for f in late}
-        if len(sizes) != 1:
-            raise ValueError(f"jpeg_decode: frames of one size, got {sorted(sizes)}")
-        (h, w), = sizes
-        if dst is None:
-            dst = torch.empty(n, h, w, 3, dtype=torch.uint8, device=dev)
-        if late:
-            host = torch.empty(len(late), h, w, 3, dtype=torch.uint8, pin_memory=True)
-            for j, f in enumerate(late):
-                host.numpy()[j] = f
-            dst[torch.tensor(sorted(refused), device=dev)] = host.to(dev, non_blocking=True)
-    return dst
+def _map(pool, f, xs) -> list:
+    """`[f(x) for x in xs]`, on `pool` when one is given and there is more than one job (results in the order of `xs`)"""
+    return list(pool.map(f, xs)) if pool is not None and len(xs) > 1 else [f(x) for x in xs]
+
+
+# What `jpeg_decode` stages for the `members` (frame numbers) of one sampling layout, `info` the probe of one of them -> (the pinned buffer
+# that goes up in one copy, one host job `(function, *arguments)` per member that fills its part and returns its reason first, a function
+# from the uploaded buffer to (coef, qt, status or None): what `jpeg_decode_coefs` takes)
+def _jpeg_stage_host(blobs, members, info):
+    """[coefficients | tables], filled by `jpeg_entropy`"""
+    m, count = len(members), jpeg_coef_count(info.h, info.w, info.sampling)
+    buf = torch.empty(m * (count + 192), dtype=torch.int16, pin_memory=True)
+    host = buf.numpy()
+    jobs = [(jpeg_entropy, blobs[i], host[j * count:(j + 1) * count], host[m * count + j * 192:m * count + (j + 1) * 192]) for j, i in enumerate(members)]
+    return buf, jobs, lambda on_dev: (on_dev[:m * count].view(m, count), on_dev[m * count:].view(m, 192), None)
+
+
+def _jpeg_stage_device(blobs, members, info):
+    """[scans | tables | descriptors], filled by `jpeg_scan_prepare`; the coefficients are `jpeg_entropy_device`'s"""
+    m, tb = len(members), L.JPEG_TABLE_BYTES
+    offs = [0]
+    for i in members:
+        offs.append(offs[-1] + jpeg_scan_room(len(blobs[i])))
+    end = offs[-1]
+    buf = torch.empty(end + m * (tb + 16), dtype=torch.uint8, pin_memory=True)
+    host = buf.numpy()
+    tables, desc = host[end:end + m * tb].reshape(m, tb), host[end + m * tb:].view(np.int32).reshape(m, 4)
+    jobs = [(jpeg_scan_prepare, blobs[i], host[:end], offs[j], desc[j], tables[j]) for j, i in enumerate(members)]
+    return buf, jobs, lambda on_dev: jpeg_entropy_device(on_dev[:end], on_dev[end + m * tb:].view(torch.int32).view(m, 4),
+                                                         on_dev[end:end + m * tb].view(m, tb), info.h, info.w, info.sampling)
 
 
 def jpeg_decode(blobs: Sequence[bytes], pool=None, device=None, entropy: str = "host") -> torch.Tensor:
@@ -1336,46 +1287,53 @@ def jpeg_decode(blobs: Sequence[bytes], pool=None, device=None, entropy: str = "
         raise ValueError("jpeg_decode: no frames")
     if entropy not in ("host", "device"):
         raise ValueError(f"jpeg_decode: entropy {entropy!r} (host or device)")
+    stage = _jpeg_stage_device if entropy == "device" else _jpeg_stage_host
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    if entropy == "device":
-        return _jpeg_decode_device_entropy(blobs, pool, dev)
     infos = [jpeg_probe(b) for b in blobs]
     groups: dict = {}
     for i, info in enumerate(infos):
         if info.supported:
             groups.setdefault(info.sampling, []).append(i)
     sizes = {(info.h, info.w) for info in infos if info.supported}
-    if len(sizes) > 1:
-        raise ValueError(f"jpeg_decode: frames of one size, got {sorted(sizes)}")
+
+    def one_size():
+        if len(sizes) > 1:
+            raise ValueError(f"jpeg_decode: frames of one size, got {sorted(sizes)}")
+    one_size()
     refused = [i for i, info in enumerate(infos) if not info.supported]
-    staged, jobs = {}, []
-    for sampling, members in groups.items():
-        h, w = infos[members[0]].h, infos[members[0]].w
-        count = jpeg_coef_count(h, w, sampling)
-        buf = torch.empty(len(members) * (count + 192), dtype=torch.int16, pin_memory=True)         # [coefficients | tables]: one upload
-        host = buf.numpy()
-        staged[sampling] = (buf, count)
-        for j, i in enumerate(members):
-            jobs.append((i, host[j * count:(j + 1) * count], host[len(members) * count + j * 192:len(members) * count + (j + 1) * 192]))
-    run = lambda job: jpeg_entropy(blobs[job[0]], job[1], job[2])[0]
-    reasons = list(pool.map(run, jobs)) if pool is not None and len(jobs) > 1 else [run(j) for j in jobs]
-    refused += [job[0] for job, reason in zip(jobs, reasons) if reason != 0]      # the scan itself: corrupt, or outside the guard
-    late = [blobs[i] for i in sorted(refused)]
-    late = list(pool.map(decode_image, late)) if pool is not None and len(late) > 1 else [decode_image(b) for b in late]
-    sizes |= {f.shape[:2] for f in late}
-    if len(sizes) != 1:
-        raise ValueError(f"jpeg_decode: frames of one size, got {sorted(sizes)}")
-    (h, w), = sizes
-    dst = torch.empty(n, h, w, 3, dtype=torch.uint8, device=dev)
+    run = lambda job: job[0](*job[1:])[0]       # the reason: first in `jpeg_entropy`'s pair and in `JpegScan`
+    staged = [(members, *stage(blobs, members, infos[members[0]])) for members in groups.values()]
+    order = [i for members, *_ in staged for i in members]
+    reasons = dict(zip(order, _map(pool, run, [job for _, _, jobs, _ in staged for job in jobs])))
+    refused += [i for i in order if reasons[i] not in (0, L.JPEG_RESTART)]      # the scan itself: corrupt, or outside the guard
+    dst, pending = None, []
     with torch.cuda.device(dev):
-        for sampling, members in groups.items():
-            buf, count = staged[sampling]
-            m = len(members)
-            on_dev = buf.to(dev, non_blocking=True)
+        for members, buf, _, coefs in staged:
+            info, m = infos[members[0]], len(members)
+            coef, qt, status = coefs(buf.to(dev, non_blocking=True))
+            at = [j for j, i in enumerate(members) if reasons[i] == L.JPEG_RESTART]
+            if at:      # restart intervals (prepare's answer: device entropy only): the host's entropy pass, into the same device call
+                rbuf, rjobs, rcoefs = _jpeg_stage_host(blobs, [members[j] for j in at], info)
+                refused += [members[j] for j, reason in zip(at, _map(pool, run, rjobs)) if reason != 0]
+                at = torch.tensor(at, device=dev)
+                coef[at], qt[at], _ = rcoefs(rbuf.to(dev, non_blocking=True))     # after the kernels: their slots hold a refused frame's leftovers
+            if dst is None:
+                dst = torch.empty(n, info.h, info.w, 3, dtype=torch.uint8, device=dev)
             whole = m == n                      # the common case: every frame in one layout, decoded in place
-            out = jpeg_decode_coefs(on_dev[:m * count].view(m, count), on_dev[m * count:].view(m, 192), h, w, sampling, dst if whole else None)
+            out = jpeg_decode_coefs(coef, qt, info.h, info.w, info.sampling, dst if whole else None)
             if not whole:
                 dst[torch.tensor(members, device=dev)] = out
+            if status is not None:
+                pending.append((members, status))
+        for members, status in pending:         # one small read-back per layout, after every launch; the host path has none
+            st = jpeg_status_download(status)
+            refused += [i for j, i in enumerate(members) if reasons[i] == 0 and st[j, 0] != 0]
+        late = _map(pool, decode_image, [blobs[i] for i in sorted(refused)])
+        sizes |= {f.shape[:2] for f in late}
+        one_size()
+        (h, w), = sizes
+        if dst is None:
+            dst = torch.empty(n, h, w, 3, dtype=torch.uint8, device=dev)
         if late:
             host = torch.empty(len(late), h, w, 3, dtype=torch.uint8, pin_memory=True)
             for j, f in enumerate(late):

@@ -179,6 +179,40 @@ def test_decode_fallbacks_inside_a_batch(ops, monkeypatch):
     assert torch.equal(out.cpu(), want)
 
 
+@pytest.mark.parametrize("entropy", ["host", "device"])
+def test_decode_every_frame_refused(ops, entropy, monkeypatch):
+    """two PNGs and a progressive frame: no layout, so nothing is launched or read back; all three come from `decode_image`"""
+    from mv_ldm_amd import dataset as D
+    from mv_ldm_amd.image_io import encode_png
+    blobs = [encode_png(J.pixels(45, 81, "smooth")), encode_png(J.pixels(45, 81, "noise")), J.encode(J.pixels(45, 81, "photo"), quality=90, progressive=True)]
+    fell = []
+    real = D.decode_image
+    monkeypatch.setattr(D, "decode_image", lambda b: (fell.append(blobs.index(b)), real(b))[1])
+    calls = _counted(ops, monkeypatch)
+    out = ops.jpeg_decode(blobs, entropy=entropy)
+    assert sorted(fell) == [0, 1, 2] and calls == {"status": 0, "entropy": [], "decode": []}
+    want = torch.from_numpy(np.stack([J.pixels(45, 81, "smooth"), J.pixels(45, 81, "noise"), J.pillow(blobs[2])]))
+    assert out.is_cuda and torch.equal(out.cpu(), want)
+
+
+@pytest.mark.parametrize("entropy", ["host", "device"])
+def test_decode_layout_of_restart_frames(ops, entropy, monkeypatch):
+    """a layout made only of restart frames: the host's entropy pass for both, one decode call, never Pillow; with device entropy the
+    layout still makes its one (empty) entropy call and its one status download"""
+    from mv_ldm_amd import dataset as D
+    blobs = [J.restart_case(), J.restart_case()]
+    info = ops.jpeg_probe(blobs[0])
+    assert info.supported and (info.h, info.w) == (45, 81)
+    fell = []
+    real = D.decode_image
+    monkeypatch.setattr(D, "decode_image", lambda b: (fell.append(1), real(b))[1])
+    calls = _counted(ops, monkeypatch)
+    out = ops.jpeg_decode(blobs, entropy=entropy)
+    assert not fell and calls["decode"] == [(info.sampling, 2)]
+    assert (calls["entropy"], calls["status"]) == (([(info.sampling, 2)], 1) if entropy == "device" else ([], 0))
+    assert torch.equal(out.cpu(), _expect(blobs))
+
+
 def test_decode_big_case(ops, monkeypatch):
     blob = J.big_case()
     calls = _counted(ops, monkeypatch)

@@ -196,6 +196,19 @@ def test_every_truncation(ops):
         assert prepare(ops, blob[:cut]).reason == ops.jpeg_probe(blob[:cut]).reason != 0
 
 
+def test_tail_reasons_are_the_host_decoders(ops):
+    """what follows the scan -- fill bytes, then EOI: prepare and the host decoder refuse a bad tail with the same code, TRUNCATED where
+    the data runs off the end and CORRUPT where another marker stands"""
+    from mv_ldm_amd import _lib as L
+    truncated, corrupt = L.JPEG_REASONS.index("truncated"), L.JPEG_REASONS.index("corrupt")
+    blob, _ = damaged_stream()
+    body = blob[:-2]
+    assert blob[-2:] == b"\xff\xd9"
+    for tail, want in ((b"", truncated), (b"\xff", truncated), (b"\xff\xff", truncated), (b"\xff\xff\xff", truncated), (b"\xff\xd9", 0),
+                       (b"\xff\xff\xd9", 0), (b"\xff\xff\xff\xd9\x00", 0), (b"\xff\xc4", corrupt), (b"\xff\xff\xd8", corrupt), (b"\xff\xda\xff\xd9", corrupt)):
+        assert prepare(ops, body + tail).reason == host(ops, body + tail)[0] == want, tail
+
+
 def test_flipped_bytes(ops):
     blob, start = damaged_stream()
     outcomes = set()
