@@ -48,7 +48,9 @@ extern "C" {
  *    + mvldm_jpeg_probe / _entropy / _coef_count / _workspace_bytes / _decode / _idct_host (baseline JPEG frames: entropy decoding on the
  *    host, dequantisation, inverse DCT, upsampling and colour on the device): new symbols and enums only, the number stays 7.
  *    + mvldm_jpeg_scan_room / _scan_prepare / _entropy_chunk_subseqs / _entropy_device / _entropy_emul_host and the reason
- *    MVLDM_JPEG_RESTART (the Huffman scan decoded on the device): new symbols and one new enum value only, the number stays 7. */
+ *    MVLDM_JPEG_RESTART (the Huffman scan decoded on the device): new symbols and one new enum value only, the number stays 7.
+ *    + mvldm_png_unfilter / _unfilter_host and the MVLDM_PNG_* enums (PNG frames: inflate on the host, row unfiltering and colour expansion
+ *    on the device): new symbols and enums only, the number stays 7. */
 #define MVLDM_ABI_VERSION 7
 
 typedef void* mvldm_stream_t; /* hipStream_t */
@@ -884,6 +886,55 @@ int mvldm_jpeg_entropy_device(const uint8_t* scan, size_t scan_bytes, const int3
 int mvldm_jpeg_entropy_emul_host(const uint8_t* scan /* host */, size_t scan_bytes, const int32_t* desc /* host */, const uint8_t* tables /* host */,
                                  int n_img, int h, int w, int sampling, int16_t* coef /* host */, uint16_t* qt /* host */, int32_t* status /* host */,
                                  int subseq_bits, int chunk_subseqs);
+
+/* ------------------------------------------------------------------------------------------------
+ * PNG frames: row unfiltering and colour expansion on the device.  What `Image.open(BytesIO(frame)).convert("RGB")` gives for a PNG
+ * (the reference writes its frames and ground-truth trees through Pillow, which picks a filter per row), bit for bit: alpha dropped,
+ * grey replicated, palette entries looked up; tRNS, gAMA and iCCP play no part.  The caller (mv_ldm_amd/ops.py png_decode) parses the
+ * chunks, checks their CRCs and inflates IDAT on the host; the device does the rest.
+ *   streams   one buffer of inflated streams.  Frame i is h rows of 1 + stride bytes (filter byte, then the filtered row), stride =
+ *             ceil(w * channels * depth / 8), at byte desc[i][0]: no row is aligned, none is assumed to be.  h, w: 1 .. 16384, common to
+ *             the call.  Non-interlaced only.
+ *   desc      int32 [MVLDM_PNG_DESC_INTS] per frame: stream offset, colour type, bit depth, offset of the frame's palette in `palettes`
+ *             (bytes), palette entries (1 .. 256), 0, 0, 0.  Colour type 2, 6, 0 or 4 at depth 8; colour type 3 at depth 1, 2, 4 or 8.
+ *             A descriptor of another format, or one whose stream (h * (1 + stride) bytes) or palette (3 bytes per entry) does not fit
+ *             its buffer, is refused: status MVLDM_PNG_DESC, nothing of the frame is read and nothing is written for it.
+ *   filters   None / Sub / Up / Average / Paeth per row, modulo 256; bytes left of the first pixel and the row above the first are 0;
+ *             Average floors the 9-bit sum; Paeth is p = a + b - c in integers, ties in the order a, b, c.  A filter byte above 4 is
+ *             treated as None (the caller refuses such a frame before any launch).
+ *   dst       MVLDM_PNG_DST_U8: uint8 [n_img][h][w][3] (what mvldm_jpeg_decode writes and mvldm_crop_shim takes); MVLDM_PNG_DST_F32:
+ *             fp32 [n_img][3][h][w] holding k / 255 correctly rounded (the bits of torch's `k.float() / 255`).
+ *   status    int32 per frame: MVLDM_PNG_OK, MVLDM_PNG_DESC, or MVLDM_PNG_PALETTE_INDEX -- a pixel's palette index lies beyond the PLTE
+ *             entries: it is written as black and the caller decodes that frame elsewhere.
+ * mvldm_png_unfilter (device): one launch, one wave per frame.  Average and Paeth are serial along a row and need the row above, so the
+ * wave walks bands of 64 rows as a skewed wavefront: lane r reconstructs unit t - r (a pixel, or a byte of pixels below 8 bits) at step
+ * t and takes the two units it needs from the row above out of lane r - 1's registers; a band's last row waits in LDS for lane 0 of the
+ * next band.  Nothing is allocated and nothing is read back, so the call can be captured.
+ * mvldm_png_unfilter_host (host; no state, any number of threads) is the same arithmetic (csrc/png_common.h) row by row in plain C++ on
+ * host pointers: what the CPU tests pin to Pillow.  It takes sizes from untrusted files and applies the same descriptor check. */
+enum { MVLDM_PNG_DST_U8 = 0, MVLDM_PNG_DST_F32 = 1 };
+#define MVLDM_PNG_DESC_INTS 8
+enum {
+    MVLDM_PNG_OK = 0,
+    MVLDM_PNG_NOT_PNG = 1,       /* no PNG signature, or no IHDR first */
+    MVLDM_PNG_TRUNCATED = 2,     /* the file ends inside a chunk, or has no IDAT / IEND */
+    MVLDM_PNG_CRC = 3,           /* a chunk whose CRC does not match (critical or not: Pillow raises on either) */
+    MVLDM_PNG_INTERLACE = 4,     /* Adam7 */
+    MVLDM_PNG_DEPTH16 = 5,       /* 16-bit samples */
+    MVLDM_PNG_GREY_BITS = 6,     /* grey below 8 bits */
+    MVLDM_PNG_FORMAT = 7,        /* a colour type / bit depth / compression / filter method outside the PNG specification */
+    MVLDM_PNG_SIZE = 8,          /* an edge of 0 or above 16384 */
+    MVLDM_PNG_NO_PLTE = 9,       /* colour type 3 without a palette (or one of no entries, more than 256, or a length no multiple of 3) */
+    MVLDM_PNG_FILTER = 10,       /* a filter byte above 4 */
+    MVLDM_PNG_LENGTH = 11,       /* an inflated length other than h * (1 + stride) */
+    MVLDM_PNG_INFLATE = 12,      /* zlib refuses the IDAT stream */
+    MVLDM_PNG_PALETTE_INDEX = 13,/* status only: a palette index beyond the PLTE entries */
+    MVLDM_PNG_DESC = 14          /* status only: a descriptor that does not fit its buffers */
+};
+int mvldm_png_unfilter(const uint8_t* streams, size_t stream_bytes, const int32_t* desc, const uint8_t* palettes, size_t palette_bytes, void* dst,
+                       int dst_kind, int n_img, int h, int w, int32_t* status, mvldm_stream_t stream);
+int mvldm_png_unfilter_host(const uint8_t* streams /* host */, size_t stream_bytes, const int32_t* desc /* host */, const uint8_t* palettes /* host */,
+                            size_t palette_bytes, void* dst /* host */, int dst_kind, int n_img, int h, int w, int32_t* status /* host */);
 
 /* ------------------------------------------------------------------------------------------------
  * Plans: a whole forward (UNet walk, VAE decoder, DDIM step) as a flat list of the ops above with

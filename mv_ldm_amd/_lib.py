@@ -24,6 +24,13 @@ JPEG_REASONS = ("ok", "not a JPEG", "truncated", "corrupt", "progressive", "fram
 JPEG_RANGE = 12
 JPEG_RESTART = 13                                               # mvldm_jpeg_scan_prepare only: the frame's scan is decoded by the host
 JPEG_HUFF_TABLE_BYTES, JPEG_TABLE_BYTES = 1424, 8928            # MVLDM_JPEG_HUFF_TABLE_BYTES, MVLDM_JPEG_TABLE_BYTES
+PNG_DST_U8, PNG_DST_F32 = 0, 1                                  # include/mvldm.h MVLDM_PNG_DST_*: what mvldm_png_unfilter writes
+PNG_DESC_INTS = 8                                               # MVLDM_PNG_DESC_INTS
+PNG_REASONS = ("ok", "not a PNG", "truncated", "bad CRC", "interlaced", "16-bit samples", "grey below 8 bits", "format", "size", "no palette",
+               "filter byte", "inflated length", "inflate", "palette index", "descriptor")      # MVLDM_PNG_OK .. MVLDM_PNG_DESC, by value
+(PNG_NOT_PNG, PNG_TRUNCATED, PNG_CRC, PNG_INTERLACE, PNG_DEPTH16, PNG_GREY_BITS, PNG_FORMAT, PNG_SIZE, PNG_NO_PLTE, PNG_FILTER, PNG_LENGTH, PNG_INFLATE,
+ PNG_PALETTE_INDEX, PNG_DESC) = range(1, 15)
+PNG_MAX_DIM = 16384
 
 (OP_IGEMM, OP_GROUPNORM, OP_LAYERNORM, OP_ATTENTION, OP_TIMESTEP_EMBED, OP_ELTWISE, OP_DDIM_STEP, OP_DDIM_ADVANCE,
  OP_NCHW_TO_NHWC, OP_NHWC_TO_NCHW, OP_MEMCPY, OP_RAY_ENCODE, OP_POSTERIOR_SAMPLE,
@@ -278,6 +285,8 @@ SIGNATURES = {
     "mvldm_jpeg_entropy_chunk_subseqs": (C.c_int, []),
     "mvldm_jpeg_entropy_device": (C.c_int, [vp, sz, vp, vp] + [C.c_int] * 4 + [vp, vp, vp, C.c_int, vp]),
     "mvldm_jpeg_entropy_emul_host": (C.c_int, [vp, sz, vp, vp] + [C.c_int] * 4 + [vp, vp, vp, C.c_int, C.c_int]),
+    "mvldm_png_unfilter": (C.c_int, [vp, sz, vp, vp, sz, vp] + [C.c_int] * 4 + [vp, vp]),
+    "mvldm_png_unfilter_host": (C.c_int, [vp, sz, vp, vp, sz, vp] + [C.c_int] * 4 + [vp]),
     "mvldm_nchw_to_nhwc": (C.c_int, [vp, vp] + [C.c_int] * 6 + [f32, f32, vp, vp]),
     "mvldm_ray_channels": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "mvldm_ray_encode": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp] + [C.c_int] * 4 + [vp]),

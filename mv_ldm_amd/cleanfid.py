@@ -4,7 +4,8 @@ the `fidclean_*` and `kidclean_*` columns of the reference's evaluation.
 
     python -m mv_ldm_amd.cleanfid DIR1 DIR2 --weights INCEPTION.pth [--json OUT] [--kid [--kid-seed N] [--kid-subsets S] [--kid-subset-size M]]
 
-Every `*.png` under a folder (recursively, sorted) goes through the package's "clean" resize -- PIL's antialiased bicubic on float32
+Every `*.png` under a folder (recursively, sorted; any PNG Pillow reads -- filtered rows, RGB, RGBA, grey, palette: `ops.png_decode`
+unfilters and expands on the device, and what it refuses is decoded by Pillow) goes through the package's "clean" resize -- PIL's antialiased bicubic on float32
 planes, no re-quantisation --, `(x - 128) / 128`, the FID variant of Inception-v3 up to its 2048-wide pool, and the fp64 statistics; the
 score is the Frechet distance of the two sets.  The resize, the pools, the unfold that turns the 1 x 7 / 7 x 1 / 1 x 3 / 3 x 1 / 5 x 5
 convolutions into 1 x 1 ones, the running statistics and the 2048-wide eigen-solves are `csrc/inception.hip`; the 94 convolutions run
@@ -29,6 +30,7 @@ the subsets the package would draw), as noise is everywhere else at this boundar
 from __future__ import annotations
 
 import json
+import os
 import sys
 from pathlib import Path
 from typing import Optional
@@ -369,17 +371,15 @@ def list_images(folder) -> list:
     return sorted(p for p in folder.rglob("*.png") if p.is_file())
 
 
-def iter_batches(folder, batch: int = 32):
-    """uint8 `[m, 3, h, w]` host tensors of the folder's images: sorted order, split by image size (sizes in order of first appearance),
-    at most `batch` images each"""
-    from .image_io import load_image
-    groups: dict = {}
-    for p in list_images(folder):
-        img = (load_image(p) * 255).round().to(torch.uint8)       # k / 255 back to the decoded byte k, exactly
-        groups.setdefault(tuple(img.shape[1:]), []).append(img)
-    for imgs in groups.values():
-        for i in range(0, len(imgs), batch):
-            yield torch.stack(imgs[i:i + batch]).contiguous()
+def iter_batches(folder, batch: int = 32, device="cpu", pool=None):
+    """uint8 `[m, 3, h, w]` tensors on `device` (the host unless one is named) of the folder's images: sorted order, split by image size (sizes in order of first
+    appearance), at most `batch` images each.  Any PNG Pillow reads: the host inflates (on `pool`), the device unfilters the rows and
+    expands grey, alpha and palette files to RGB (`ops.png_decode`); what that refuses goes through Pillow."""
+    from .image_io import group_by_size, load_images
+    paths = list_images(folder)
+    for members in group_by_size(paths).values():
+        for i in range(0, len(members), batch):
+            yield load_images([paths[j] for j in members[i:i + batch]], device, pool, out="uint8").permute(0, 3, 1, 2).contiguous()
 
 
 def score_folders(dir1, dir2, metric: CleanFID, batch: int = 32, dtype: Optional[torch.dtype] = None, kid: Optional[dict] = None) -> dict:
@@ -388,17 +388,22 @@ def score_folders(dir1, dir2, metric: CleanFID, batch: int = 32, dtype: Optional
     "seed", "fp64", "scale"}."""
     if kid is not None and not metric.keep_features:
         raise RuntimeError("score_folders(kid=...): KID needs the features themselves; construct the CleanFID with keep_features=True")
+    from concurrent.futures import ThreadPoolExecutor
     dev = metric.real_state.device
     metric.reset()
     counts = []
-    for folder, real in ((dir1, False), (dir2, True)):
-        n = 0
-        for imgs in iter_batches(folder, batch):
-            metric.update(imgs.to(dev), real=real, dtype=dtype)
-            n += imgs.shape[0]
-        if n == 0:
-            raise ValueError(f"cleanfid: no *.png under {folder}")
-        counts.append(n)
+    pool = ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1))      # the files' inflate; unfiltering and expansion are the device's
+    try:
+        for folder, real in ((dir1, False), (dir2, True)):
+            n = 0
+            for imgs in iter_batches(folder, batch, dev, pool):
+                metric.update(imgs, real=real, dtype=dtype)
+                n += imgs.shape[0]
+            if n == 0:
+                raise ValueError(f"cleanfid: no *.png under {folder}")
+            counts.append(n)
+    finally:
+        pool.shutdown()
     score = float(metric.compute())
     info = metric.info.tolist()
     rec = {"fidclean": score, "n1": counts[0], "n2": counts[1],

@@ -1,7 +1,9 @@
 """Image output for the generation harness: the counterpart of `src/misc/image_io.py:42-73`
 (`prep_image`: clip to [0,1], x255, truncate to uint8, HWC; `save_image`: create the parent directory, write).
 The reference writes through PIL; here the PNG container is produced directly (zlib + CRC from the standard
-library: an 8-bit RGB / RGBA / grey image is a filter byte + raw row per scanline, deflated)."""
+library: an 8-bit RGB / RGBA / grey image is a filter byte + raw row per scanline, deflated).
+Reading: `load_image` / `decode_png` read this writer's own files (filter 0 on every row); `load_images` reads a batch of ANY PNG files --
+what Pillow writes, filtered rows, grey, palette -- through `ops.png_decode`: inflate on the host, unfiltering and expansion on the device."""
 from __future__ import annotations
 
 import struct
@@ -69,3 +71,40 @@ def load_image(path: Union[Path, str]) -> torch.Tensor:
     tool scores PNG trees with (src/evaluation/metric_computer.py reads the same files through torchvision)"""
     pixels = decode_png(Path(path).read_bytes())
     return torch.from_numpy(pixels[..., :3]).permute(2, 0, 1).float() / 255
+
+
+def image_size(path: Union[Path, str]) -> tuple:
+    """(h, w) of an image file without decoding it: a PNG's IHDR, anything else through Pillow's lazy open"""
+    from .ops import png_probe
+    with open(path, "rb") as f:
+        info = png_probe(f.read(33))
+    if info.h and info.w:
+        return info.h, info.w
+    from PIL import Image
+    with Image.open(path) as im:
+        return im.height, im.width
+
+
+def group_by_size(paths) -> dict:
+    """{(h, w): [positions in `paths`]}, sizes in order of first appearance, positions ascending"""
+    groups: dict = {}
+    for i, p in enumerate(paths):
+        groups.setdefault(image_size(p), []).append(i)
+    return groups
+
+
+def load_images(paths, device="cuda", pool=None, out: str = "float", info=None) -> torch.Tensor:
+    """any PNG files of ONE size -> float32 `[n, 3, h, w]` in [0, 1] on `device`, in the order of `paths`: `Image.open(p).convert("RGB")`
+    as k / 255 (for RGB and RGBA files the reference's `ToTensor()(Image.open(p))[:3]`), whichever filter the writer chose per row and
+    whether the file is RGB, RGBA, grey, grey + alpha or palette.  The host inflates (on `pool`, a `concurrent.futures` executor, when
+    one is given), one upload, and the device unfilters, expands and writes the layout (`ops.png_decode`); what that refuses goes through
+    Pillow into the same slot.  `out="uint8"`: the decoded bytes, uint8 `[n, h, w, 3]`.  Files of several sizes: `group_by_size` first.
+    `info`: see `ops.png_decode`."""
+    from .ops import _map, png_decode
+    paths = list(paths)
+    if not paths:
+        raise ValueError("load_images: no files")
+    sizes = group_by_size(paths)
+    if len(sizes) > 1:
+        raise ValueError(f"load_images: files of one size, got {sorted(sizes)} (group_by_size splits a list)")
+    return png_decode(_map(pool, lambda p: Path(p).read_bytes(), paths), pool=pool, device=device, out=out, info=info)

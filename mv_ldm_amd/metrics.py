@@ -21,6 +21,7 @@ from __future__ import annotations
 
 import argparse
 import json
+import os
 from pathlib import Path
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -186,29 +187,34 @@ def score_trees(pred_dir, gt_dir, device="cuda", batch: int = 64, lpips=None, di
     `FrechetInceptionDistance` on `device`; FID is one value per scene, so the per-frame rows do not change: every scene entry gains
     "fid" (None for a scene of fewer than 2 paired frames) and "overall" the mean over the scored scenes, as the reference's running
     table averages its per-scene values."""
-    from .image_io import load_image
+    from concurrent.futures import ThreadPoolExecutor
+    from .image_io import load_images
     pairs, missing = pair_trees(scan_tree(pred_dir), scan_tree(gt_dir))
+    pool = ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1))      # the frames' inflate (zlib releases the GIL); the rest is the device's
     per_frame: Dict[str, Dict[int, List[float]]] = {}
     scene_fid: Dict[str, Optional[torch.Tensor]] = {}
-    for scene, items in pairs.items():
-        per_frame[scene] = {}
-        if fid is not None:
-            fid.reset()
-        for i0 in range(0, len(items), batch):
-            chunk = items[i0:i0 + batch]
-            p = torch.stack([load_image(a) for _, a, _ in chunk]).to(device)
-            g = torch.stack([load_image(b) for _, _, b in chunk]).to(device)
-            psnr, ssim = image_metrics(g, p)
-            rows = [psnr.tolist(), ssim.tolist()] + ([] if lpips is None else [compute_lpips(g, p, lpips).tolist()]) \
-                + ([] if dists is None else [compute_dists(g, p, dists).tolist()])
-            for (i, _, _), *row in zip(chunk, *rows):
-                per_frame[scene][i] = row
-            if fid is not None and len(items) >= 2:
-                fid.update(g, real=True)
-                fid.update(p, real=False)
-        if fid is not None:
-            scene_fid[scene] = fid.compute() if len(items) >= 2 else None
-            fid.reset()
+    try:
+        for scene, items in pairs.items():
+            per_frame[scene] = {}
+            if fid is not None:
+                fid.reset()
+            for i0 in range(0, len(items), batch):
+                chunk = items[i0:i0 + batch]
+                p = load_images([a for _, a, _ in chunk], device, pool)     # any PNG: Pillow's filtered rows, RGBA, grey, palette (ops.png_decode)
+                g = load_images([b for _, _, b in chunk], device, pool)
+                psnr, ssim = image_metrics(g, p)
+                rows = [psnr.tolist(), ssim.tolist()] + ([] if lpips is None else [compute_lpips(g, p, lpips).tolist()]) \
+                    + ([] if dists is None else [compute_dists(g, p, dists).tolist()])
+                for (i, _, _), *row in zip(chunk, *rows):
+                    per_frame[scene][i] = row
+                if fid is not None and len(items) >= 2:
+                    fid.update(g, real=True)
+                    fid.update(p, real=False)
+            if fid is not None:
+                scene_fid[scene] = fid.compute() if len(items) >= 2 else None
+                fid.reset()
+    finally:
+        pool.shutdown()
     if dists is None:
         rep = summarize(per_frame)
     else:

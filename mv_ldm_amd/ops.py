@@ -7,8 +7,11 @@ activation dtype; biases / norm parameters / statistics are fp32.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
+import struct
+import zlib
 from dataclasses import dataclass
 from typing import NamedTuple, Optional, Sequence
 
@@ -1339,4 +1342,256 @@ def jpeg_decode(blobs: Sequence[bytes], pool=None, device=None, entropy: str = "
             for j, f in enumerate(late):
                 host.numpy()[j] = f
             dst[torch.tensor(sorted(refused), device=dev)] = host.to(dev, non_blocking=True)         # after the kernels: a refused scan's slot is overwritten
+    return dst
+
+
+# ------------------------------------------------------------------------------------------ PNG frames (csrc/png.hip, csrc/png_host.cpp)
+_PNG_SIG = b"\x89PNG\r\n\x1a\n"
+_PNG_DEPTHS = {0: (1, 2, 4, 8, 16), 2: (8, 16), 3: (1, 2, 4, 8), 4: (8, 16), 6: (8, 16)}        # the PNG specification's colour type -> bit depths
+_PNG_CHANNELS = {0: 1, 2: 3, 3: 1, 4: 2, 6: 4}
+_PNG_NO_FRAME = (0, -1, 0, 0, 0, 0, 0, 0)       # the descriptor of a frame the host refused: no format, so the kernel reads and writes nothing for it
+
+
+class PngInfo(NamedTuple):
+    """`png_probe` of an encoded frame.  `reason` 0: the library unfilters it on the device; otherwise an index into `_lib.PNG_REASONS`.
+    h, w, color_type, depth and interlace are IHDR's where one was read (else 0)."""
+    h: int
+    w: int
+    color_type: int
+    depth: int
+    interlace: int
+    reason: int
+
+    @property
+    def supported(self) -> bool:
+        return self.reason == 0
+
+    @property
+    def stride(self) -> int:
+        """bytes of a row behind its filter byte"""
+        return (self.w * _PNG_CHANNELS[self.color_type] * self.depth + 7) // 8
+
+    @property
+    def stream_bytes(self) -> int:
+        """what IDAT has to inflate to"""
+        return self.h * (1 + self.stride)
+
+
+def png_probe(blob: bytes) -> PngInfo:
+    """size, colour type, bit depth, interlace flag and reason of an encoded frame from its IHDR: nothing is inflated (host only, no library call)"""
+    if len(blob) < 8 or bytes(blob[:8]) != _PNG_SIG:
+        return PngInfo(0, 0, 0, 0, 0, L.PNG_NOT_PNG)
+    if len(blob) < 33:
+        return PngInfo(0, 0, 0, 0, 0, L.PNG_TRUNCATED)
+    if bytes(blob[8:16]) != b"\x00\x00\x00\rIHDR":
+        return PngInfo(0, 0, 0, 0, 0, L.PNG_NOT_PNG)
+    w, h, depth, ctype, comp, filt, lace = struct.unpack(">IIBBBBB", blob[16:29])
+    why = lambda reason: PngInfo(h, w, ctype, depth, lace, reason)
+    if struct.unpack(">I", blob[29:33])[0] != (zlib.crc32(blob[12:29]) & 0xFFFFFFFF):
+        return why(L.PNG_CRC)
+    if depth not in _PNG_DEPTHS.get(ctype, ()) or comp != 0 or filt != 0 or lace > 1:
+        return why(L.PNG_FORMAT)
+    if not (1 <= h <= L.PNG_MAX_DIM and 1 <= w <= L.PNG_MAX_DIM):
+        return why(L.PNG_SIZE)
+    if lace:
+        return why(L.PNG_INTERLACE)
+    if depth == 16:
+        return why(L.PNG_DEPTH16)
+    if ctype == 0 and depth < 8:
+        return why(L.PNG_GREY_BITS)
+    return why(0)
+
+
+def _png_chunks(blob: bytes):
+    """(reason, IDAT bodies, PLTE body or None) of a frame whose IHDR `png_probe` accepted: every chunk's CRC is checked (Pillow raises on
+    a bad one, so such a frame is Pillow's to judge), the walk ends at IEND"""
+    pos, idat, plte, n = 33, [], None, len(blob)
+    view = memoryview(blob)
+    while True:
+        if pos + 12 > n:
+            return L.PNG_TRUNCATED, idat, plte
+        size, tag = struct.unpack(">I", view[pos:pos + 4])[0], bytes(view[pos + 4:pos + 8])
+        if pos + 12 + size > n:
+            return L.PNG_TRUNCATED, idat, plte
+        body = view[pos + 8:pos + 8 + size]
+        if struct.unpack(">I", view[pos + 8 + size:pos + 12 + size])[0] != (zlib.crc32(body, zlib.crc32(tag)) & 0xFFFFFFFF):
+            return L.PNG_CRC, idat, plte
+        if tag == b"IDAT":
+            idat.append(body)
+        elif tag == b"PLTE":
+            if plte is not None or idat:
+                return L.PNG_FORMAT, idat, plte
+            plte = body
+        elif tag == b"IEND":
+            return (0 if idat else L.PNG_TRUNCATED), idat, plte
+        elif tag == b"IHDR" or not (tag[0] & 0x20):     # a second header, or a critical chunk this reader does not know
+            return L.PNG_FORMAT, idat, plte
+        pos += 12 + size
+
+
+def _png_stage(blob: bytes, info: PngInfo, host: np.ndarray, off: int, pal0: int, pal_off: int, desc: np.ndarray) -> int:
+    """what the host does for one frame `png_probe` accepted: the chunks and their CRCs, IDAT inflated (`zlib`, which releases the GIL) into
+    `host[off : off + info.stream_bytes]`, the palette to byte `pal_off` of the palettes, which start at `host[pal0]`, the descriptor into `desc` (int32 `[8]`).
+    Returns the reason; after a refusal the descriptor is the no-frame one, and nothing reaches the kernel."""
+    desc[:] = _PNG_NO_FRAME
+    reason, idat, plte = _png_chunks(blob)
+    if reason:
+        return reason
+    count = 0
+    if info.color_type == 3:
+        if plte is None or len(plte) == 0 or len(plte) % 3 or len(plte) > 768:
+            return L.PNG_NO_PLTE
+        count = len(plte) // 3
+    need = info.stream_bytes
+    inflater = zlib.decompressobj()
+    try:
+        raw = inflater.decompress(idat[0] if len(idat) == 1 else b"".join(idat), need + 1)
+    except zlib.error:
+        return L.PNG_INFLATE
+    if len(raw) != need:
+        return L.PNG_LENGTH                             # short, or bytes behind the last row
+    if not inflater.eof or inflater.unused_data:
+        return L.PNG_INFLATE                            # a stream without its end or with bytes behind it: Pillow's to judge
+    rows = np.frombuffer(raw, dtype=np.uint8)
+    if int(rows[::1 + info.stride].max()) > 4:
+        return L.PNG_FILTER
+    host[off:off + need] = rows
+    if count:
+        host[pal0 + pal_off:pal0 + pal_off + 3 * count] = np.frombuffer(plte, dtype=np.uint8)
+    desc[:] = (off, info.color_type, info.depth, pal_off, count, 0, 0, 0)
+    return 0
+
+
+def _png_layout(infos) -> tuple:
+    """(stream offsets of the supported frames {i: offset}, end of the streams = start of the palettes, start of the descriptors, bytes):
+    one staging buffer [streams | 768 bytes of palette per frame | int32 [n, 8] descriptors]"""
+    offs, end = {}, 0
+    for i, info in enumerate(infos):
+        if info.supported:
+            offs[i] = end
+            end += info.stream_bytes
+    desc0 = (end + 768 * len(infos) + 3) & ~3
+    return offs, end, desc0, desc0 + 4 * L.PNG_DESC_INTS * len(infos)
+
+
+def png_unfilter_host(streams: np.ndarray, desc: np.ndarray, palettes: np.ndarray, h: int, w: int, dst: np.ndarray) -> np.ndarray:
+    """`mvldm_png_unfilter_host`: the kernel's arithmetic in plain C++ over the frames of `desc` int32 `[n, 8]` into `dst` -- uint8
+    `[n, h, w, 3]` or float32 `[n, 3, h, w]` -> status int32 `[n]`: tests and tools"""
+    desc = desc.reshape(-1, L.PNG_DESC_INTS)
+    n = desc.shape[0]
+    assert streams.dtype == np.uint8 and streams.flags.c_contiguous and palettes.dtype == np.uint8 and palettes.flags.c_contiguous
+    assert desc.dtype == np.int32 and desc.flags.c_contiguous and dst.flags.c_contiguous
+    assert (dst.dtype == np.uint8 and dst.shape == (n, h, w, 3)) or (dst.dtype == np.float32 and dst.shape == (n, 3, h, w)), (dst.dtype, dst.shape)
+    status = np.full(n, -1, dtype=np.int32)
+    L.check(L.load().mvldm_png_unfilter_host(streams.ctypes.data, streams.size, desc.ctypes.data, palettes.ctypes.data if palettes.size else None, palettes.size,
+                                             dst.ctypes.data, L.PNG_DST_U8 if dst.dtype == np.uint8 else L.PNG_DST_F32, n, h, w, status.ctypes.data))
+    return status
+
+
+def png_decode_host(blob: bytes, dst: Optional[np.ndarray] = None, out: str = "uint8"):
+    """one encoded frame through the host twin -> (reason, pixels): uint8 `[h, w, 3]` or float32 `[3, h, w]` (`dst`, when given, is that
+    array and is written in place).  A refused frame comes back with its reason and `None`, and `dst` is not touched; reason
+    `_lib.PNG_PALETTE_INDEX` comes with the pixels the kernel would write (black where the index has no entry).  Tests and tools."""
+    info = png_probe(blob)
+    if not info.supported:
+        return info.reason, None
+    (offs, end, desc0, total), (h, w) = _png_layout([info]), (info.h, info.w)
+    host = np.zeros(total, dtype=np.uint8)
+    desc = host[desc0:].view(np.int32)
+    reason = _png_stage(blob, info, host, 0, end, 0, desc)
+    if reason:
+        return reason, None
+    shape = (h, w, 3) if out == "uint8" else (3, h, w)
+    if dst is None:
+        dst = np.empty(shape, dtype=np.uint8 if out == "uint8" else np.float32)
+    assert dst.shape == shape and dst.flags.c_contiguous, (dst.shape, shape)
+    status = png_unfilter_host(host[:end], desc, host[end:desc0], h, w, dst.reshape(1, *shape))
+    return int(status[0]), dst
+
+
+def png_unfilter(staged: torch.Tensor, stream_bytes: int, desc0: int, n: int, h: int, w: int, dst: torch.Tensor, status: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`mvldm_png_unfilter` over one uploaded staging buffer of `_png_layout` -> status int32 `[n]` on the device.  One launch; nothing is
+    allocated when `status` is given, and nothing is read back, so the call can be captured."""
+    assert staged.is_cuda and staged.is_contiguous() and staged.dtype == torch.uint8 and staged.dim() == 1 and desc0 % 4 == 0
+    assert staged.numel() >= desc0 + 4 * L.PNG_DESC_INTS * n and stream_bytes + 768 * n <= desc0
+    assert dst.is_cuda and dst.is_contiguous() and dst.device == staged.device
+    assert (dst.dtype == torch.uint8 and tuple(dst.shape) == (n, h, w, 3)) or (dst.dtype == torch.float32 and tuple(dst.shape) == (n, 3, h, w)), (dst.dtype, tuple(dst.shape))
+    status = torch.empty(n, dtype=torch.int32, device=staged.device) if status is None else status
+    assert status.is_cuda and status.is_contiguous() and status.dtype == torch.int32 and tuple(status.shape) == (n,)
+    base = staged.data_ptr()
+    L.check(L.load().mvldm_png_unfilter(base, stream_bytes, base + desc0, base + stream_bytes, 768 * n, dst.data_ptr(),
+                                        L.PNG_DST_U8 if dst.dtype == torch.uint8 else L.PNG_DST_F32, n, h, w, status.data_ptr(), stream()))
+    return status
+
+
+def _pillow_rgb(blob: bytes) -> np.ndarray:
+    """the expression the PNG path has to reproduce, and its fallback: an error Pillow raises for a broken file is the caller's"""
+    from io import BytesIO
+    from PIL import Image
+    return np.ascontiguousarray(np.asarray(Image.open(BytesIO(blob)).convert("RGB")))
+
+
+def png_decode(blobs: Sequence[bytes], pool=None, device=None, out: str = "uint8", info: Optional[dict] = None) -> torch.Tensor:
+    """encoded PNG frames of ONE size -> uint8 `[n, h, w, 3]` (`out="uint8"`: what `jpeg_decode` returns and `crop_shim` takes) or fp32
+    `[n, 3, h, w]` holding k / 255 (`out="float"`: what the metrics consume), the pixels `Image.open(...).convert("RGB")` gives.
+
+    Per frame the host parses the chunks, checks their CRCs and inflates IDAT (`zlib`, no GIL; on `pool`, a `concurrent.futures`
+    executor, when one is given) into one pinned staging tensor; then one upload, one `mvldm_png_unfilter` launch -- the five row filters,
+    the expansion of grey, grey + alpha, RGBA and palette frames to RGB, the write into the layout asked for -- and ONE small download of
+    the frames' status words.  A frame the library refuses (16-bit, grey below 8 bits, interlaced, a filter byte above 4, an inflated
+    length other than h * (1 + stride), a bad CRC, no PLTE, not a PNG at all, ...) or that the kernel flags (a palette index beyond the PLTE
+    entries) is decoded by Pillow on the host and uploaded into its slot: the result never depends on which path ran.
+    `info`: a dict that receives `"fallback"`, the list of (frame number, reason) that took Pillow.
+    `device="cpu"` (tests and tools on a machine without a device): the same staging, then the kernel's host twin
+    (`mvldm_png_unfilter_host`: the same arithmetic in C++) into a host tensor."""
+    n = len(blobs)
+    if n == 0:
+        raise ValueError("png_decode: no frames")
+    if out not in ("uint8", "float"):
+        raise ValueError(f"png_decode: out {out!r} (uint8 or float)")
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    on_host = dev.type == "cpu"
+    infos = [png_probe(b) for b in blobs]
+    sizes = {(p.h, p.w) for p in infos if p.supported}
+
+    def one_size():
+        if len(sizes) > 1:
+            raise ValueError(f"png_decode: frames of one size, got {sorted(sizes)}")
+    one_size()
+    refused = {i: p.reason for i, p in enumerate(infos) if not p.supported}
+    dst = None
+    with (contextlib.nullcontext() if on_host else torch.cuda.device(dev)):
+        if len(refused) < n:
+            (h, w), = sizes
+            offs, end, desc0, total = _png_layout(infos)
+            buf = torch.empty(total, dtype=torch.uint8, pin_memory=not on_host)
+            host = buf.numpy()
+            desc = host[desc0:].view(np.int32).reshape(n, L.PNG_DESC_INTS)
+            desc[:] = _PNG_NO_FRAME
+            order = sorted(offs)
+            reasons = _map(pool, lambda i: _png_stage(blobs[i], infos[i], host, offs[i], end, 768 * i, desc[i]), order)
+            refused.update({i: r for i, r in zip(order, reasons) if r})
+            dst = torch.empty((n, h, w, 3) if out == "uint8" else (n, 3, h, w), dtype=torch.uint8 if out == "uint8" else torch.float32, device=dev)
+            if len(refused) < n and on_host:
+                status = png_unfilter_host(host[:end], desc, host[end:end + 768 * n], h, w, dst.numpy())
+            elif len(refused) < n:
+                status = png_unfilter(buf.to(dev, non_blocking=True), end, desc0, n, h, w, dst).cpu().numpy()       # the one read-back
+                refused.update({i: int(status[i]) for i in order if i not in refused and status[i] != 0})
+        at = sorted(refused)
+        late = _map(pool, _pillow_rgb, [blobs[i] for i in at])
+        sizes |= {f.shape[:2] for f in late}
+        one_size()
+        (h, w), = sizes
+        if dst is None:
+            dst = torch.empty((n, h, w, 3) if out == "uint8" else (n, 3, h, w), dtype=torch.uint8 if out == "uint8" else torch.float32, device=dev)
+        if late:
+            host = torch.empty(len(late), h, w, 3, dtype=torch.uint8, pin_memory=not on_host)
+            for j, f in enumerate(late):
+                host.numpy()[j] = f
+            if out == "float":      # k / 255 divided on the host, where torch divides (the device multiplies by a reciprocal: other bits)
+                host = (host.permute(0, 3, 1, 2).float() / 255).contiguous()
+                host = host if on_host else host.pin_memory()
+            dst[torch.tensor(at, device=dev)] = host.to(dev, non_blocking=True)       # after the kernel: a flagged frame's slot is overwritten
+    if info is not None:
+        info["fallback"] = [(i, L.PNG_REASONS[refused[i]]) for i in at]
     return dst
