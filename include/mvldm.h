@@ -50,7 +50,9 @@ extern "C" {
  *    + mvldm_jpeg_scan_room / _scan_prepare / _entropy_chunk_subseqs / _entropy_device / _entropy_emul_host and the reason
  *    MVLDM_JPEG_RESTART (the Huffman scan decoded on the device): new symbols and one new enum value only, the number stays 7.
  *    + mvldm_png_unfilter / _unfilter_host and the MVLDM_PNG_* enums (PNG frames: inflate on the host, row unfiltering and colour expansion
- *    on the device): new symbols and enums only, the number stays 7. */
+ *    on the device): new symbols and enums only, the number stays 7.
+ *    + mvldm_png_inflate / _inflate_host / _inflate_room (PNG frames: IDAT inflated on the device, opt-in): new symbols only, the number
+ *    stays 7. */
 #define MVLDM_ABI_VERSION 7
 
 typedef void* mvldm_stream_t; /* hipStream_t */
@@ -935,6 +937,40 @@ int mvldm_png_unfilter(const uint8_t* streams, size_t stream_bytes, const int32_
                        int dst_kind, int n_img, int h, int w, int32_t* status, mvldm_stream_t stream);
 int mvldm_png_unfilter_host(const uint8_t* streams /* host */, size_t stream_bytes, const int32_t* desc /* host */, const uint8_t* palettes /* host */,
                             size_t palette_bytes, void* dst /* host */, int dst_kind, int n_img, int h, int w, int32_t* status /* host */);
+
+/* ------------------------------------------------------------------------------------------------
+ * PNG frames: IDAT inflated on the device (opt-in: mv_ldm_amd/ops.py png_decode(inflate="device")).  n zlib streams (RFC 1950 around
+ * RFC 1951), one per frame, are inflated into the slots mvldm_png_unfilter reads, so that the upload is the file's IDAT bytes and not the
+ * inflated stream.  The caller still walks the chunks and checks their CRCs, and copies a frame's IDAT bodies back to back.
+ *   z         one buffer of zlib streams, 16-byte aligned.  Frame i's stream is zdesc[i][1] bytes at byte zdesc[i][0] (a multiple of 16)
+ *             followed by zeros up to mvldm_png_inflate_room(bytes) = round_up(bytes, 16) + 16: the decoder reads aligned dwords.
+ *   zdesc     int32 [MVLDM_PNG_ZDESC_INTS] per frame: offset, bytes, 0, 0.
+ *   streams, desc   the output buffer and mvldm_png_unfilter's descriptors: frame i is written at byte desc[i][0] and has to be exactly
+ *             need = h * (1 + stride) bytes.  A descriptor png_unfilter would refuse (the no-frame descriptor of a frame the host
+ *             refused among them), or a zdesc that does not fit `z`, gives MVLDM_PNG_DESC: nothing of the frame is read or written.
+ *   zstatus   int32 per frame, apart from mvldm_png_unfilter's status.  MVLDM_PNG_OK: the slot holds the inflated stream.
+ *             MVLDM_PNG_LENGTH: the stream inflates to more or fewer than `need` bytes.  MVLDM_PNG_FILTER: a row's filter byte is
+ *             above 4.  MVLDM_PNG_INFLATE: anything else -- a header other than CM = 8, CINFO <= 7, a multiple of 31, FDICT = 0; a
+ *             reserved block type; a stored block whose length and complement disagree; a code set zlib refuses (over-subscribed, or
+ *             incomplete other than a single one-bit code or a distance code of no codes; no end-of-block code; more than 286 / 30
+ *             codes; a repeat with nothing before it or past the end); bits that match no code; length codes 286 / 287, distance
+ *             codes 30 / 31; a distance beyond the bytes written so far; a stream that ends before its final block or its trailer
+ *             does; an Adler-32 (computed on the device) other than the trailer's; a byte behind the trailer.
+ *             After a refusal the slot's contents are unspecified; nothing outside the slot and the status word is written.
+ * Stored, fixed and dynamic blocks in any sequence, empty stored blocks (Z_SYNC_FLUSH, Z_FULL_FLUSH), matches of 3 .. 258 bytes at
+ * distances 1 .. 32768, overlapping ones included.
+ * mvldm_png_inflate (device): one launch, one wave per frame, 37 KiB of LDS (a 32 KiB sliding window, two decode tables, a queue of 64
+ * symbols).  One lane decodes symbols; the wave builds a dynamic block's tables, copies stored blocks and matches, writes runs of
+ * literals, and sums the Adler-32.  Every loop is bounded by 8 * bytes + 16 steps, every read stays inside the padded stream, every
+ * write is guarded by its position in the slot.  Nothing is allocated and nothing is read back, so the call can be captured.
+ * mvldm_png_inflate_host (host; no state, any number of threads) runs the same step functions (csrc/inflate_common.h) with loops in
+ * place of lanes: the same bytes and the same status. */
+#define MVLDM_PNG_ZDESC_INTS 4
+size_t mvldm_png_inflate_room(size_t bytes);
+int mvldm_png_inflate(const uint8_t* z, size_t z_bytes, const int32_t* zdesc, uint8_t* streams, size_t stream_bytes, const int32_t* desc, int n_img, int h,
+                      int w, int32_t* zstatus, mvldm_stream_t stream);
+int mvldm_png_inflate_host(const uint8_t* z /* host */, size_t z_bytes, const int32_t* zdesc /* host */, uint8_t* streams /* host */, size_t stream_bytes,
+                           const int32_t* desc /* host */, int n_img, int h, int w, int32_t* zstatus /* host */);
 
 /* ------------------------------------------------------------------------------------------------
  * Plans: a whole forward (UNet walk, VAE decoder, DDIM step) as a flat list of the ops above with

@@ -26,6 +26,7 @@ JPEG_RESTART = 13                                               # mvldm_jpeg_sca
 JPEG_HUFF_TABLE_BYTES, JPEG_TABLE_BYTES = 1424, 8928            # MVLDM_JPEG_HUFF_TABLE_BYTES, MVLDM_JPEG_TABLE_BYTES
 PNG_DST_U8, PNG_DST_F32 = 0, 1                                  # include/mvldm.h MVLDM_PNG_DST_*: what mvldm_png_unfilter writes
 PNG_DESC_INTS = 8                                               # MVLDM_PNG_DESC_INTS
+PNG_ZDESC_INTS = 4                                              # MVLDM_PNG_ZDESC_INTS
 PNG_REASONS = ("ok", "not a PNG", "truncated", "bad CRC", "interlaced", "16-bit samples", "grey below 8 bits", "format", "size", "no palette",
                "filter byte", "inflated length", "inflate", "palette index", "descriptor")      # MVLDM_PNG_OK .. MVLDM_PNG_DESC, by value
 (PNG_NOT_PNG, PNG_TRUNCATED, PNG_CRC, PNG_INTERLACE, PNG_DEPTH16, PNG_GREY_BITS, PNG_FORMAT, PNG_SIZE, PNG_NO_PLTE, PNG_FILTER, PNG_LENGTH, PNG_INFLATE,
@@ -287,6 +288,9 @@ SIGNATURES = {
     "mvldm_jpeg_entropy_emul_host": (C.c_int, [vp, sz, vp, vp] + [C.c_int] * 4 + [vp, vp, vp, C.c_int, C.c_int]),
     "mvldm_png_unfilter": (C.c_int, [vp, sz, vp, vp, sz, vp] + [C.c_int] * 4 + [vp, vp]),
     "mvldm_png_unfilter_host": (C.c_int, [vp, sz, vp, vp, sz, vp] + [C.c_int] * 4 + [vp]),
+    "mvldm_png_inflate_room": (sz, [sz]),
+    "mvldm_png_inflate": (C.c_int, [vp, sz, vp, vp, sz, vp] + [C.c_int] * 3 + [vp, vp]),
+    "mvldm_png_inflate_host": (C.c_int, [vp, sz, vp, vp, sz, vp] + [C.c_int] * 3 + [vp]),
     "mvldm_nchw_to_nhwc": (C.c_int, [vp, vp] + [C.c_int] * 6 + [f32, f32, vp, vp]),
     "mvldm_ray_channels": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "mvldm_ray_encode": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp] + [C.c_int] * 4 + [vp]),

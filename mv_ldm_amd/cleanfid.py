@@ -371,21 +371,22 @@ def list_images(folder) -> list:
     return sorted(p for p in folder.rglob("*.png") if p.is_file())
 
 
-def iter_batches(folder, batch: int = 32, device="cpu", pool=None):
+def iter_batches(folder, batch: int = 32, device="cpu", pool=None, inflate: str = "host"):
     """uint8 `[m, 3, h, w]` tensors on `device` (the host unless one is named) of the folder's images: sorted order, split by image size (sizes in order of first
     appearance), at most `batch` images each.  Any PNG Pillow reads: the host inflates (on `pool`), the device unfilters the rows and
-    expands grey, alpha and palette files to RGB (`ops.png_decode`); what that refuses goes through Pillow."""
+    expands grey, alpha and palette files to RGB (`ops.png_decode`); what that refuses goes through Pillow.  `inflate="device"`: the
+    device inflates too (opt-in, the same bytes)."""
     from .image_io import group_by_size, load_images
     paths = list_images(folder)
     for members in group_by_size(paths).values():
         for i in range(0, len(members), batch):
-            yield load_images([paths[j] for j in members[i:i + batch]], device, pool, out="uint8").permute(0, 3, 1, 2).contiguous()
+            yield load_images([paths[j] for j in members[i:i + batch]], device, pool, out="uint8", inflate=inflate).permute(0, 3, 1, 2).contiguous()
 
 
-def score_folders(dir1, dir2, metric: CleanFID, batch: int = 32, dtype: Optional[torch.dtype] = None, kid: Optional[dict] = None) -> dict:
+def score_folders(dir1, dir2, metric: CleanFID, batch: int = 32, dtype: Optional[torch.dtype] = None, kid: Optional[dict] = None, inflate: str = "host") -> dict:
     """{"fidclean", "n1", "n2", "solve": {...}} of two folders, which need not pair up: a distance of two distributions.
     `kid=dict(num_subsets=, max_subset_size=, seed=)` (a `CleanFID(keep_features=True)`) adds "kidclean" and "kid": {"m", "subsets",
-    "seed", "fp64", "scale"}."""
+    "seed", "fp64", "scale"}.  `inflate`: see `iter_batches`."""
     if kid is not None and not metric.keep_features:
         raise RuntimeError("score_folders(kid=...): KID needs the features themselves; construct the CleanFID with keep_features=True")
     from concurrent.futures import ThreadPoolExecutor
@@ -396,7 +397,7 @@ def score_folders(dir1, dir2, metric: CleanFID, batch: int = 32, dtype: Optional
     try:
         for folder, real in ((dir1, False), (dir2, True)):
             n = 0
-            for imgs in iter_batches(folder, batch, dev, pool):
+            for imgs in iter_batches(folder, batch, dev, pool, inflate):
                 metric.update(imgs, real=real, dtype=dtype)
                 n += imgs.shape[0]
             if n == 0:
@@ -457,12 +458,13 @@ def main(argv=None) -> int:
     ap.add_argument("--kid-seed", type=int, default=None, help="seed of a private numpy RandomState for the subsets (default: numpy's global stream)")
     ap.add_argument("--kid-subsets", type=int, default=100)
     ap.add_argument("--kid-subset-size", type=int, default=1000)
+    ap.add_argument("--device-inflate", action="store_true", help="inflate the files' IDAT on the device as well (the default inflates on the host); the same bytes")
     a = ap.parse_args(argv)
     dtype = getattr(torch, a.dtype)
     _not_empty(a.dir1, a.dir2)
     model = InceptionPool3(weights=a.weights, dtype=dtype).to("cuda")
     kid = dict(num_subsets=a.kid_subsets, max_subset_size=a.kid_subset_size, seed=a.kid_seed) if a.kid else None
-    rec = score_folders(a.dir1, a.dir2, CleanFID(model, keep_features=a.kid), a.batch, dtype, kid=kid)
+    rec = score_folders(a.dir1, a.dir2, CleanFID(model, keep_features=a.kid), a.batch, dtype, kid=kid, inflate="device" if a.device_inflate else "host")
     s = rec["solve"]
     line = (f"fidclean {rec['fidclean']:.6f}  ({rec['n1']} vs {rec['n2']} images; solves: {s['sweeps'][0]} + {s['sweeps'][1]} sweeps, "
             f"residual {s['residual'][0]:.1e}, {s['residual'][1]:.1e}, capped {s['capped']})")

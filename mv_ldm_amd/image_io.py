@@ -93,13 +93,13 @@ def group_by_size(paths) -> dict:
     return groups
 
 
-def load_images(paths, device="cuda", pool=None, out: str = "float", info=None) -> torch.Tensor:
+def load_images(paths, device="cuda", pool=None, out: str = "float", info=None, inflate: str = "host") -> torch.Tensor:
     """any PNG files of ONE size -> float32 `[n, 3, h, w]` in [0, 1] on `device`, in the order of `paths`: `Image.open(p).convert("RGB")`
     as k / 255 (for RGB and RGBA files the reference's `ToTensor()(Image.open(p))[:3]`), whichever filter the writer chose per row and
     whether the file is RGB, RGBA, grey, grey + alpha or palette.  The host inflates (on `pool`, a `concurrent.futures` executor, when
     one is given), one upload, and the device unfilters, expands and writes the layout (`ops.png_decode`); what that refuses goes through
     Pillow into the same slot.  `out="uint8"`: the decoded bytes, uint8 `[n, h, w, 3]`.  Files of several sizes: `group_by_size` first.
-    `info`: see `ops.png_decode`."""
+    `info`: see `ops.png_decode`.  `inflate="device"`: IDAT is inflated on the device too (`ops.png_decode`; opt-in, the same pixels)."""
     from .ops import _map, png_decode
     paths = list(paths)
     if not paths:
@@ -107,4 +107,4 @@ def load_images(paths, device="cuda", pool=None, out: str = "float", info=None) 
     sizes = group_by_size(paths)
     if len(sizes) > 1:
         raise ValueError(f"load_images: files of one size, got {sorted(sizes)} (group_by_size splits a list)")
-    return png_decode(_map(pool, lambda p: Path(p).read_bytes(), paths), pool=pool, device=device, out=out, info=info)
+    return png_decode(_map(pool, lambda p: Path(p).read_bytes(), paths), pool=pool, device=device, out=out, info=info, inflate=inflate)

@@ -180,13 +180,14 @@ def summarize(per_frame: Dict[str, Dict[int, List[float]]], names: Optional[Sequ
     return {"scenes": scenes, "overall": {**means(every), "frames": len(every)}}
 
 
-def score_trees(pred_dir, gt_dir, device="cuda", batch: int = 64, lpips=None, dists=None, fid=None) -> dict:
+def score_trees(pred_dir, gt_dir, device="cuda", batch: int = 64, lpips=None, dists=None, fid=None, inflate: str = "host") -> dict:
     """`metric_computer.test_step` over two PNG trees: every paired frame scored on the device, `batch` frames per launch.
     `lpips`: an `LPIPS` network on `device`; the per-frame rows then grow from [psnr, ssim] to [psnr, ssim, lpips].  `dists`: a `DISTS`
     network on `device` appends a dists column after that, and the report names its columns under "columns".  `fid`: a
     `FrechetInceptionDistance` on `device`; FID is one value per scene, so the per-frame rows do not change: every scene entry gains
     "fid" (None for a scene of fewer than 2 paired frames) and "overall" the mean over the scored scenes, as the reference's running
-    table averages its per-scene values."""
+    table averages its per-scene values.  `inflate="device"`: the files' IDAT is inflated on the device too (`ops.png_decode`; opt-in,
+    the same pixels)."""
     from concurrent.futures import ThreadPoolExecutor
     from .image_io import load_images
     pairs, missing = pair_trees(scan_tree(pred_dir), scan_tree(gt_dir))
@@ -200,8 +201,8 @@ def score_trees(pred_dir, gt_dir, device="cuda", batch: int = 64, lpips=None, di
                 fid.reset()
             for i0 in range(0, len(items), batch):
                 chunk = items[i0:i0 + batch]
-                p = load_images([a for _, a, _ in chunk], device, pool)     # any PNG: Pillow's filtered rows, RGBA, grey, palette (ops.png_decode)
-                g = load_images([b for _, _, b in chunk], device, pool)
+                p = load_images([a for _, a, _ in chunk], device, pool, inflate=inflate)     # any PNG: Pillow's filtered rows, RGBA, grey, palette (ops.png_decode)
+                g = load_images([b for _, _, b in chunk], device, pool, inflate=inflate)
                 psnr, ssim = image_metrics(g, p)
                 rows = [psnr.tolist(), ssim.tolist()] + ([] if lpips is None else [compute_lpips(g, p, lpips).tolist()]) \
                     + ([] if dists is None else [compute_dists(g, p, dists).tolist()])
@@ -240,6 +241,7 @@ def main(argv=None):
     ap.add_argument("--dists-weights", default=None, help="the DISTS_pytorch package's weights.pt (alpha, beta), with a torchvision VGG-16 as --dists")
     ap.add_argument("--fid", default=None, help="Inception-v3 weights (torch-fidelity's pt_inception state dict or a torchmetrics FID state dict); "
                                                 "adds fid (feature=64), one value per scene")
+    ap.add_argument("--device-inflate", action="store_true", help="inflate the frames' IDAT on the device as well (the default inflates on the host); the same pixels")
     args = ap.parse_args(argv)
     if args.lpips_lin and not args.lpips:
         ap.error("--lpips-lin goes with --lpips")
@@ -248,7 +250,8 @@ def main(argv=None):
     if not torch.cuda.is_available():
         raise SystemExit("metrics needs a GPU (the HIP path has no CPU fallback)")
     rep = score_trees(args.pred, args.gt, lpips=load_lpips(args.lpips, args.lpips_lin) if args.lpips else None,
-                      dists=load_dists(args.dists, args.dists_weights) if args.dists else None, fid=load_fid(args.fid) if args.fid else None)
+                      dists=load_dists(args.dists, args.dists_weights) if args.dists else None, fid=load_fid(args.fid) if args.fid else None,
+                      inflate="device" if args.device_inflate else "host")
     for kind, scene, index, side in rep["missing"]:
         print(f"skipped {kind} {scene}" + ("" if index is None else f"/{index}") + f": missing in --{side}")
     extra = lambda r: (f" lpips {r['lpips']:.6f}" if "lpips" in r else "") + (f" dists {r['dists']:.6f}" if "dists" in r else "") \

@@ -1524,6 +1524,105 @@ def png_unfilter(staged: torch.Tensor, stream_bytes: int, desc0: int, n: int, h:
     return status
 
 
+def png_inflate_host(z: np.ndarray, zdesc: np.ndarray, streams: np.ndarray, desc: np.ndarray, h: int, w: int) -> np.ndarray:
+    """`mvldm_png_inflate_host`: the zlib streams of `zdesc` int32 `[n, 4]` (offset in `z`, a multiple of 16; bytes; zeros behind each up
+    to `mvldm_png_inflate_room`) inflated into the slots of `desc` int32 `[n, 8]` in `streams`, by the kernel's step functions in plain C++
+    -> status int32 `[n]`: tests, tools and `png_decode(device="cpu", inflate="device")`"""
+    zdesc, desc = zdesc.reshape(-1, L.PNG_ZDESC_INTS), desc.reshape(-1, L.PNG_DESC_INTS)
+    n = desc.shape[0]
+    assert zdesc.shape[0] == n and zdesc.dtype == np.int32 and zdesc.flags.c_contiguous and desc.dtype == np.int32 and desc.flags.c_contiguous
+    assert z.dtype == np.uint8 and z.flags.c_contiguous and streams.dtype == np.uint8 and streams.flags.c_contiguous and streams.flags.writeable
+    status = np.full(n, -1, dtype=np.int32)
+    L.check(L.load().mvldm_png_inflate_host(z.ctypes.data, z.size, zdesc.ctypes.data, streams.ctypes.data, streams.size, desc.ctypes.data, n, h, w, status.ctypes.data))
+    return status
+
+
+def png_inflate(z: torch.Tensor, zdesc: torch.Tensor, streams: torch.Tensor, desc: torch.Tensor, h: int, w: int, status: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`mvldm_png_inflate`: as `png_inflate_host` on device tensors (`z`, `streams` uint8, 1-D; `zdesc` int32 `[n, 4]`, `desc` int32
+    `[n, 8]`) -> status int32 `[n]` on the device.  One launch; nothing is allocated when `status` is given, and nothing is read back, so
+    the call can be captured."""
+    n = desc.shape[0]
+    assert z.is_cuda and z.is_contiguous() and z.dtype == torch.uint8 and z.dim() == 1 and z.data_ptr() % 16 == 0
+    assert streams.is_cuda and streams.is_contiguous() and streams.dtype == torch.uint8 and streams.dim() == 1 and streams.device == z.device
+    assert zdesc.is_cuda and zdesc.is_contiguous() and zdesc.dtype == torch.int32 and tuple(zdesc.shape) == (n, L.PNG_ZDESC_INTS)
+    assert desc.is_cuda and desc.is_contiguous() and desc.dtype == torch.int32 and tuple(desc.shape) == (n, L.PNG_DESC_INTS)
+    status = torch.empty(n, dtype=torch.int32, device=z.device) if status is None else status
+    assert status.is_cuda and status.is_contiguous() and status.dtype == torch.int32 and tuple(status.shape) == (n,)
+    L.check(L.load().mvldm_png_inflate(z.data_ptr(), z.numel(), zdesc.data_ptr(), streams.data_ptr(), streams.numel(), desc.data_ptr(), n, h, w, status.data_ptr(), stream()))
+    return status
+
+
+def _png_zstage(blobs, infos, pool, refused: dict, pin: bool):
+    """the host's share of `png_decode(inflate="device")` for the frames `png_probe` accepted: the chunk walk with every CRC (on `pool`),
+    then each frame's IDAT bodies copied back to back into ONE staging tensor [z streams, each at a multiple of 16 with zeros up to
+    `mvldm_png_inflate_room` | 768 bytes of palette per frame | int32 [n, 8] descriptors | int32 [n, 4] z descriptors].  Adds what it
+    refuses to `refused`; returns None when nothing is left, else (staging tensor, frames kept, end of the z streams = start of the
+    palettes, bytes of the inflated streams, start of the descriptors, start of the z descriptors)."""
+    n, lib = len(blobs), L.load()
+    order = [i for i, p in enumerate(infos) if p.supported]
+    keep, zend, send = [], 0, 0
+    for i, (reason, idat, plte) in zip(order, _map(pool, lambda i: _png_chunks(blobs[i]), order)):
+        if not reason and infos[i].color_type == 3 and (plte is None or len(plte) == 0 or len(plte) % 3 or len(plte) > 768):
+            reason = L.PNG_NO_PLTE
+        if reason:
+            refused[i] = reason
+            continue
+        zbytes = sum(len(b) for b in idat)
+        keep.append((i, idat, plte, zend, zbytes, send))
+        zend += lib.mvldm_png_inflate_room(zbytes)
+        send += infos[i].stream_bytes
+    if not keep:
+        return None
+    desc0 = (zend + 768 * n + 3) & ~3
+    zdesc0 = desc0 + 4 * L.PNG_DESC_INTS * n
+    buf = torch.empty(zdesc0 + 4 * L.PNG_ZDESC_INTS * n, dtype=torch.uint8, pin_memory=pin)
+    host = buf.numpy()
+    desc = host[desc0:zdesc0].view(np.int32).reshape(n, L.PNG_DESC_INTS)
+    zdesc = host[zdesc0:].view(np.int32).reshape(n, L.PNG_ZDESC_INTS)
+    desc[:] = _PNG_NO_FRAME
+    zdesc[:] = 0
+    for i, idat, plte, zoff, zbytes, soff in keep:
+        host[zoff:zoff + zbytes] = np.frombuffer(idat[0] if len(idat) == 1 else b"".join(idat), dtype=np.uint8)
+        host[zoff + zbytes:zoff + lib.mvldm_png_inflate_room(zbytes)] = 0
+        count = 0
+        if infos[i].color_type == 3:
+            count = len(plte) // 3
+            host[zend + 768 * i:zend + 768 * i + 3 * count] = np.frombuffer(plte, dtype=np.uint8)
+        desc[i] = (soff, infos[i].color_type, infos[i].depth, 768 * i, count, 0, 0, 0)
+        zdesc[i] = (zoff, zbytes, 0, 0)
+    return buf, [k[0] for k in keep], zend, send, desc0, zdesc0
+
+
+def _png_decode_zdevice(blobs, infos, pool, dev, dst: torch.Tensor, h: int, w: int, refused: dict, info: Optional[dict]) -> None:
+    """`png_decode(inflate="device")` behind `png_probe`: `_png_zstage` on the host, ONE upload, `mvldm_png_inflate` into a device tensor
+    that is never uploaded, `mvldm_png_unfilter` out of it, and ONE download that carries both status vectors.  `dev` cpu: the two host
+    twins.  Adds the frames either status refuses to `refused`, the inflate's reason first."""
+    n, lib, on_host = len(blobs), L.load(), dev.type == "cpu"
+    staged = _png_zstage(blobs, infos, pool, refused, pin=not on_host)
+    if staged is None:
+        return
+    buf, keep, zend, send, desc0, zdesc0 = staged
+    if on_host:
+        host = buf.numpy()
+        desc, zdesc = host[desc0:zdesc0].view(np.int32), host[zdesc0:].view(np.int32)
+        streams = np.empty(send, dtype=np.uint8)
+        status = np.stack([png_inflate_host(host[:zend], zdesc, streams, desc, h, w), png_unfilter_host(streams, desc, host[zend:zend + 768 * n], h, w, dst.numpy())])
+    else:
+        on_dev = buf.to(dev, non_blocking=True)
+        streams = torch.empty(send, dtype=torch.uint8, device=dev)
+        both = torch.empty(2, n, dtype=torch.int32, device=dev)
+        base = on_dev.data_ptr()
+        L.check(lib.mvldm_png_inflate(base, zend, base + zdesc0, streams.data_ptr(), send, base + desc0, n, h, w, both[0].data_ptr(), stream()))
+        L.check(lib.mvldm_png_unfilter(streams.data_ptr(), send, base + desc0, base + zend, 768 * n, dst.data_ptr(),
+                                       L.PNG_DST_U8 if dst.dtype == torch.uint8 else L.PNG_DST_F32, n, h, w, both[1].data_ptr(), stream()))
+        status = both.cpu().numpy()                        # the one read-back: both status vectors
+    for i in keep:
+        if status[0][i] != 0 or status[1][i] != 0:         # a frame the inflate refused names that reason: its slot held nothing to unfilter
+            refused[i] = int(status[0][i]) or int(status[1][i])
+    if info is not None:
+        info["upload_bytes"] = buf.numel()
+
+
 def _pillow_rgb(blob: bytes) -> np.ndarray:
     """the expression the PNG path has to reproduce, and its fallback: an error Pillow raises for a broken file is the caller's"""
     from io import BytesIO
@@ -1531,7 +1630,7 @@ def _pillow_rgb(blob: bytes) -> np.ndarray:
     return np.ascontiguousarray(np.asarray(Image.open(BytesIO(blob)).convert("RGB")))
 
 
-def png_decode(blobs: Sequence[bytes], pool=None, device=None, out: str = "uint8", info: Optional[dict] = None) -> torch.Tensor:
+def png_decode(blobs: Sequence[bytes], pool=None, device=None, out: str = "uint8", info: Optional[dict] = None, inflate: str = "host") -> torch.Tensor:
     """encoded PNG frames of ONE size -> uint8 `[n, h, w, 3]` (`out="uint8"`: what `jpeg_decode` returns and `crop_shim` takes) or fp32
     `[n, 3, h, w]` holding k / 255 (`out="float"`: what the metrics consume), the pixels `Image.open(...).convert("RGB")` gives.
 
@@ -1543,10 +1642,15 @@ def png_decode(blobs: Sequence[bytes], pool=None, device=None, out: str = "uint8
     entries) is decoded by Pillow on the host and uploaded into its slot: the result never depends on which path ran.
     `info`: a dict that receives `"fallback"`, the list of (frame number, reason) that took Pillow.
     `device="cpu"` (tests and tools on a machine without a device): the same staging, then the kernel's host twin
-    (`mvldm_png_unfilter_host`: the same arithmetic in C++) into a host tensor."""
+    (`mvldm_png_unfilter_host`: the same arithmetic in C++) into a host tensor.
+    `inflate="device"` (opt-in; the default `"host"` is the path above): the host still walks the chunks and checks every CRC, but uploads
+    the IDAT bytes as they are, and `mvldm_png_inflate` inflates them on the device in front of the unfilter launch (`_png_decode_zdevice`):
+    the same pixels, the same fallbacks with the same reasons, and `info["upload_bytes"]`."""
     n = len(blobs)
     if n == 0:
         raise ValueError("png_decode: no frames")
+    if inflate not in ("host", "device"):
+        raise ValueError(f"png_decode: inflate {inflate!r} (host or device)")
     if out not in ("uint8", "float"):
         raise ValueError(f"png_decode: out {out!r} (uint8 or float)")
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
@@ -1561,7 +1665,11 @@ def png_decode(blobs: Sequence[bytes], pool=None, device=None, out: str = "uint8
     refused = {i: p.reason for i, p in enumerate(infos) if not p.supported}
     dst = None
     with (contextlib.nullcontext() if on_host else torch.cuda.device(dev)):
-        if len(refused) < n:
+        if len(refused) < n and inflate == "device":
+            (h, w), = sizes
+            dst = torch.empty((n, h, w, 3) if out == "uint8" else (n, 3, h, w), dtype=torch.uint8 if out == "uint8" else torch.float32, device=dev)
+            _png_decode_zdevice(blobs, infos, pool, dev, dst, h, w, refused, info)
+        elif len(refused) < n:
             (h, w), = sizes
             offs, end, desc0, total = _png_layout(infos)
             buf = torch.empty(total, dtype=torch.uint8, pin_memory=not on_host)
