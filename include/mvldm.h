@@ -432,7 +432,8 @@ int mvldm_mse_loss_amp(const float* pred, const float* noise, const int32_t* tgt
 /* torch.nn.utils.clip_grad_norm_ over a flat fp32 gradient buffer (Lightning gradient_clip_val, src/main.py:131):
  * norm_out[0] = total norm, norm_out[1] = min(1, max_norm / (total + 1e-6)) (max_norm <= 0: 1), norm_out[2] = this
  * buffer's sum of squares.  sumsq_in (optional, device): use this total sum of squares instead (a sharded optimizer
- * all-reduces the per-rank norm_out[2] first).  workspace: 1024 doubles. */
+ * all-reduces the per-rank norm_out[2] first).  workspace: 1024 doubles.  g: 16-byte aligned when n >= 4 (it is read in
+ * 16-byte vectors), else MVLDM_ERR_ARG and nothing is launched. */
 int mvldm_grad_norm(const float* g, size_t n, const float* sumsq_in, float max_norm, float* norm_out, double* workspace,
                     mvldm_stream_t stream);
 /* torch.optim.AdamW step (decoupled weight decay, no amsgrad) on flat fp32 master parameters:
@@ -452,7 +453,8 @@ int mvldm_adamw_step_amp(float* p, const float* g, float* m, float* v, size_t n,
                          float weight_decay, float grad_scale, const float* clip, const mvldm_amp_state* amp, mvldm_stream_t stream);
 /* torch._amp_update_scale_ on the record, one thread: found_inf -> S *= backoff_factor, growth_tracker = 0, skipped += 1;
  * else growth_tracker += 1, adam_step += 1 and, when growth_tracker reaches growth_interval, S *= growth_factor (if that is
- * finite) and growth_tracker = 0.  found_inf is cleared. */
+ * finite) and growth_tracker = 0.  found_inf is cleared.  "Reaches" is >=: a tracker already above the interval (a record
+ * resumed under a shorter one) grows at its next taken step, where torch's == would never grow again. */
 int mvldm_amp_update(mvldm_amp_state* amp, float growth_factor, float backoff_factor, int growth_interval, mvldm_stream_t stream);
 
 /* DiffusionWrapper.on_before_zero_grad -> self.ema.update_parameters(self.denoiser) (diffusion_wrapper.py:138-142,152-154):

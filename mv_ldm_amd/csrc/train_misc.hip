@@ -202,7 +202,14 @@ __global__ __launch_bounds__(256) void mse_kernel(const float* __restrict__ pred
         const int img = tgt_img[t];
         const float d = pred[((size_t)img * hw + pix) * c + ch] - noise[((size_t)t * c + ch) * hw + pix];
         acc += (double)d * (double)d;
-        if (dpred) dpred[((size_t)img * hw + pix) * dc + ch] = from_f32<T>(gscale * d);
+        if (dpred) {
+            // the fp32 product, rounded AGAIN to T (what the header states and the trainer's f32 / 16-bit twins rely on).  Left to itself the
+            // compiler folds multiply + conversion to f16 into v_fma_mixlo_f16, which rounds the EXACT product once: another f16 number in
+            // one element of 16 000 (where the fp32 product lands on an f16 tie).  The empty asm pins the product to an fp32 register.
+            float gd = gscale * d;
+            asm volatile("" : "+v"(gd));
+            dpred[((size_t)img * hw + pix) * dc + ch] = from_f32<T>(gd);
+        }
     }
     const double sum = block_sum(acc);
     if (threadIdx.x == 0) partial[blockIdx.x] = sum;
@@ -337,7 +344,9 @@ __global__ __launch_bounds__(256) void ema_kernel(float* __restrict__ avg, const
     }
 }
 
-// torch._amp_update_scale_ (one thread)
+// torch._amp_update_scale_ (one thread).  One deliberate difference: torch grows only when the incremented tracker EQUALS the interval, so
+// a tracker already at or above it (a record resumed under a shorter interval) would never grow again; here >= grows at that step.
+// tests/torch_optimizer_ops.py clamps the tracker to interval - 1 before the torch call, so that the two agree.
 __global__ void amp_update_kernel(mvldm_amp_state* __restrict__ amp, float growth, float backoff, int interval) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     mvldm_amp_state a = *amp;
@@ -490,6 +499,7 @@ constexpr int kNormBlocks = 1024;
 // amp: the loss scaler's device record, or null (gradients that carry no scale)
 int grad_norm_run(const float* g, size_t n, const float* sumsq_in, float max_norm, float* norm_out, mvldm_amp_state* amp, double* ws, hipStream_t s) {
     MVLDM_REQUIRE(g && norm_out && ws, "grad_norm: null pointer");
+    MVLDM_REQUIRE(n < 4 || ((uintptr_t)g & 15) == 0, "grad_norm: g must be 16-byte aligned (sumsq_kernel reads it in 16-byte vectors)");
     hipLaunchKernelGGL(sumsq_kernel, dim3(kNormBlocks), dim3(256), 0, s, g, n, ws);
     int rc = check_launch();
     if (rc) return rc;

@@ -38,7 +38,12 @@ class TorchOptimizerOps:
 
     @staticmethod
     def update_scale(state, growth_factor, backoff_factor, growth_interval):
+        """torch._amp_update_scale_ on the record, with the growth tracker first clamped to growth_interval - 1.  torch grows only when
+        the incremented tracker EQUALS the interval, so a tracker already at or above it (a record resumed under a shorter interval)
+        would never grow again; amp_update_kernel tests >= and grows at that step.  The clamp makes the two agree
+        (tests/test_hip_glue_edges.py steps both from the same records)."""
         found = int(state[3])
+        state[1] = min(int(state[1]), growth_interval - 1)
         scale = state[0:1].view(torch.float32)
         torch._amp_update_scale_(scale, state[1:2], torch.tensor([float(found)]), growth_factor, backoff_factor, growth_interval)
         state[4 if found else 2] += 1
