@@ -52,7 +52,9 @@ extern "C" {
  *    + mvldm_png_unfilter / _unfilter_host and the MVLDM_PNG_* enums (PNG frames: inflate on the host, row unfiltering and colour expansion
  *    on the device): new symbols and enums only, the number stays 7.
  *    + mvldm_png_inflate / _inflate_host / _inflate_room (PNG frames: IDAT inflated on the device, opt-in): new symbols only, the number
- *    stays 7. */
+ *    stays 7.
+ *    + mvldm_jpeg_rst_room / _rst_need / _rst_prepare / _rst_entropy_device / _rst_entropy_emul_host (the Huffman scan of frames with
+ *    restart intervals decoded on the device, opt-in): new symbols only, the number stays 7. */
 #define MVLDM_ABI_VERSION 7
 
 typedef void* mvldm_stream_t; /* hipStream_t */
@@ -890,6 +892,56 @@ int mvldm_jpeg_entropy_device(const uint8_t* scan, size_t scan_bytes, const int3
 int mvldm_jpeg_entropy_emul_host(const uint8_t* scan /* host */, size_t scan_bytes, const int32_t* desc /* host */, const uint8_t* tables /* host */,
                                  int n_img, int h, int w, int sampling, int16_t* coef /* host */, uint16_t* qt /* host */, int32_t* status /* host */,
                                  int subseq_bits, int chunk_subseqs);
+
+/* ------------------------------------------------------------------------------------------------
+ * JPEG frames: restart intervals on the device.  An opt-in THIRD way to the coefficients: the device entropy decoder above for frames
+ * with and without restart intervals (DRI / RSTn).  mvldm_jpeg_scan_prepare and mvldm_jpeg_entropy_device keep their behaviour (a frame
+ * with DRI is still MVLDM_JPEG_RESTART there).  The result is mvldm_jpeg_entropy's, value for value: coefficients, tables, reason, S.
+ *   streams   those of mvldm_jpeg_entropy.  A frame with DRI = Ri has ceil(MCUs / Ri) intervals; one without DRI, or with Ri at or above
+ *             its MCUs, is ONE interval of all its MCUs.  Between two intervals stands RSTn (after optional 0xFF fill bytes), n counting
+ *             0 .. 7 in order; behind the last, EOI as above.  A stream whose markers are not exactly these -- one missing, one too
+ *             many, one out of order, the data ending first -- is refused by prepare with the reason mvldm_jpeg_entropy gives it.
+ *   region    a frame's part of the packed buffer, at a 16-byte aligned offset: the interval table -- int32 pairs (byte offset of the
+ *             interval inside the region, its exact bit length), rounded up to 16 bytes -- then every interval destuffed (FF 00 -> FF;
+ *             fill bytes and markers dropped) at a 4-byte aligned offset, then zeros up to round_up(bytes behind the table, 16) + 16.
+ *             The device reads aligned dwords relative to an interval's first byte; a bit position is relative to its interval.
+ *   desc      int32 [4] per frame: byte offset of the region (a multiple of 16), intervals, bytes occupied, Ri (MCUs of the frame when
+ *             it is one interval).  The device refuses (MVLDM_JPEG_CORRUPT) a descriptor that does not fit scan_bytes or whose interval
+ *             count is not ceil(MCUs / Ri), and a table with any pair that is misaligned, empty, inside the table or whose widest read
+ *             (12 bytes past its last) leaves the bytes occupied -- before it reads a bit of the frame's scan.
+ *   room      mvldm_jpeg_rst_need(data, len): what this frame can occupy (from its header: table of its intervals, scan bytes, one byte
+ *             of alignment per interval, padding; 0 for a frame the parser refuses).  mvldm_jpeg_rst_room(len) bounds it for any frame of
+ *             len encoded bytes (an interval every two bytes): a multiple of 16, about 5.5 len.
+ *   decoder   one workgroup per frame.  Subsequences of subseq_bits never cross an interval: interval g has ceil(bits_g / subseq_bits),
+ *             each decoded against the interval's end, so DEAD stays inside it.  The first subsequence of an interval has the true
+ *             entry (its first bit, 0, 0) and never takes a predecessor's exit; every other one takes the exit of the one before it,
+ *             so the induction above holds per interval and a chunk needs at most as many rounds as it has subsequences.  The
+ *             workgroup walks the intervals in batches: the longest run of whole intervals whose subsequence counts sum to at most
+ *             1024 is one chunk; an interval of more than 1024 is walked alone in chunks of 1024 with the carry.  Write pass: a thread's
+ *             first block is g Ri (blocks of an MCU) plus the blocks completed by earlier subsequences of the same interval; every store
+ *             is guarded by block < min(end of interval g, blocks of the frame).  The second kernel's DC sums restart at every
+ *             interval (a segmented 64-bit scan); the int16 test applies to every prefix.
+ *   accepted  when no fault stands in front of any interval's last block, every interval's last block completes with fewer than 8 bits
+ *             of that interval left, every DC prefix fits int16 -- else MVLDM_JPEG_CORRUPT -- and no S exceeds the guard (_RANGE).
+ *   status    int32 [4] per frame: reason, largest S, the largest number of rounds a chunk took, intervals (0: descriptor refused).
+ * mvldm_jpeg_rst_prepare (host; no state, any number of threads) reads data[0 .. len) and writes scan[scan_off .. scan_off + desc[2]),
+ * desc and tables (the blob above); info (may be NULL) is mvldm_jpeg_probe's.  Returns the reason: what mvldm_jpeg_probe returns, or
+ * mvldm_jpeg_entropy's for a broken marker structure; MVLDM_ERR_ARG for a null pointer, an offset that is no multiple of 16 or beyond
+ * scan_room, a scan_room above 2^31 - 1, or fewer than mvldm_jpeg_rst_need bytes behind the offset.  After a refusal nothing outside
+ * scan[scan_off .. scan_off + mvldm_jpeg_rst_need), desc and tables was written.
+ * mvldm_jpeg_rst_entropy_device (device): mvldm_jpeg_entropy_device's arguments and rules; a memset and two launches
+ * (jpeg_rst_scan_kernel, jpeg_rst_dc_kernel), no allocation, nothing read back; may be captured.
+ * mvldm_jpeg_rst_entropy_emul_host (host): the same algorithm with loops for threads and the same inline functions
+ * (csrc/jpeg_huff_common.h); the same coef, qt and status, rounds included when the chunk sizes agree. */
+size_t mvldm_jpeg_rst_room(size_t len);
+size_t mvldm_jpeg_rst_need(const uint8_t* data /* host */, size_t len);
+int mvldm_jpeg_rst_prepare(const uint8_t* data /* host */, size_t len, uint8_t* scan /* host */, size_t scan_off, size_t scan_room,
+                           int32_t* desc /* host [4] */, uint8_t* tables /* host [MVLDM_JPEG_TABLE_BYTES] */, int32_t* info /* host [8], may be NULL */);
+int mvldm_jpeg_rst_entropy_device(const uint8_t* scan, size_t scan_bytes, const int32_t* desc, const uint8_t* tables, int n_img, int h, int w,
+                                  int sampling, int16_t* coef, uint16_t* qt, int32_t* status, int subseq_bits, mvldm_stream_t stream);
+int mvldm_jpeg_rst_entropy_emul_host(const uint8_t* scan /* host */, size_t scan_bytes, const int32_t* desc /* host */, const uint8_t* tables /* host */,
+                                     int n_img, int h, int w, int sampling, int16_t* coef /* host */, uint16_t* qt /* host */, int32_t* status /* host */,
+                                     int subseq_bits, int chunk_subseqs);
 
 /* ------------------------------------------------------------------------------------------------
  * PNG frames: row unfiltering and colour expansion on the device.  What `Image.open(BytesIO(frame)).convert("RGB")` gives for a PNG

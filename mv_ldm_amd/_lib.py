@@ -286,6 +286,11 @@ SIGNATURES = {
     "mvldm_jpeg_entropy_chunk_subseqs": (C.c_int, []),
     "mvldm_jpeg_entropy_device": (C.c_int, [vp, sz, vp, vp] + [C.c_int] * 4 + [vp, vp, vp, C.c_int, vp]),
     "mvldm_jpeg_entropy_emul_host": (C.c_int, [vp, sz, vp, vp] + [C.c_int] * 4 + [vp, vp, vp, C.c_int, C.c_int]),
+    "mvldm_jpeg_rst_room": (sz, [sz]),
+    "mvldm_jpeg_rst_need": (sz, [vp, sz]),
+    "mvldm_jpeg_rst_prepare": (C.c_int, [vp, sz, vp, sz, sz, vp, vp, vp]),
+    "mvldm_jpeg_rst_entropy_device": (C.c_int, [vp, sz, vp, vp] + [C.c_int] * 4 + [vp, vp, vp, C.c_int, vp]),
+    "mvldm_jpeg_rst_entropy_emul_host": (C.c_int, [vp, sz, vp, vp] + [C.c_int] * 4 + [vp, vp, vp, C.c_int, C.c_int]),
     "mvldm_png_unfilter": (C.c_int, [vp, sz, vp, vp, sz, vp] + [C.c_int] * 4 + [vp, vp]),
     "mvldm_png_unfilter_host": (C.c_int, [vp, sz, vp, vp, sz, vp] + [C.c_int] * 4 + [vp]),
     "mvldm_png_inflate_room": (sz, [sz]),

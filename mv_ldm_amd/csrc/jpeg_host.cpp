@@ -263,14 +263,16 @@ void quant_rows(const Header& hd, const JpegLayout& L, uint16_t* qt) {
         for (int k = 0; k < 64; ++k) qt[c * 64 + k] = c < L.ncomp ? hd.qt[hd.comp[c].tq][k] : 0;
 }
 
-// The scan.  coef: room for L.blocks * 64 values (checked by the caller).  Returns a reason.
+// The scan.  coef: room for L.blocks * 64 values (checked by the caller).  Returns a reason.  kStore false: the reason alone, coef is
+// not touched (mvldm_jpeg_rst_prepare names a broken marker structure with this decoder's own code).
+template <bool kStore>
 int decode_scan(const uint8_t* d, size_t len, const Header& hd, const JpegLayout& L, int16_t* coef, int32_t* max_s) {
     Bits b{d, hd.scan, len};
     int pred[3] = {0, 0, 0};
     int32_t worst = 0;
     const int mcus = L.mcux * L.mcuy;
     int next_rst = 0, until_rst = hd.restart;
-    memset(coef, 0, (size_t)L.blocks * 64 * sizeof(int16_t));
+    if (kStore) memset(coef, 0, (size_t)L.blocks * 64 * sizeof(int16_t));
     for (int m = 0; m < mcus; ++m) {
         if (hd.restart && until_rst == 0) {     // byte-align, RSTn, predictors back to 0
             b.fill();
@@ -297,7 +299,7 @@ int decode_scan(const uint8_t* d, size_t len, const Header& hd, const JpegLayout
             const uint16_t* q = hd.qt[hd.comp[c].tq];
             for (int by = 0; by < vs; ++by)
                 for (int bx = 0; bx < hs; ++bx) {
-                    int16_t* blk = coef + ((size_t)L.off[c] + (size_t)(my * vs + by) * L.bw[c] + (mx * hs + bx)) * 64;
+                    int16_t* blk = kStore ? coef + ((size_t)L.off[c] + (size_t)(my * vs + by) * L.bw[c] + (mx * hs + bx)) * 64 : nullptr;
                     int s = huff_decode(&b, dc);
                     if (s < 0) return b.stop && b.pos >= len ? MVLDM_JPEG_TRUNCATED : MVLDM_JPEG_CORRUPT;
                     if (s > 15) return MVLDM_JPEG_CORRUPT;
@@ -305,7 +307,7 @@ int decode_scan(const uint8_t* d, size_t len, const Header& hd, const JpegLayout
                     if (s && !receive_extend(&b, s, &diff)) return b.pos >= len ? MVLDM_JPEG_TRUNCATED : MVLDM_JPEG_CORRUPT;
                     pred[c] += diff;
                     if (pred[c] < -32768 || pred[c] > 32767) return MVLDM_JPEG_CORRUPT;
-                    blk[0] = (int16_t)pred[c];
+                    if (kStore) blk[0] = (int16_t)pred[c];
                     int32_t sum = (pred[c] < 0 ? -pred[c] : pred[c]) * (int32_t)q[0];
                     for (int k = 1; k < 64; ++k) {
                         const int rs = huff_decode(&b, ac);
@@ -322,7 +324,7 @@ int decode_scan(const uint8_t* d, size_t len, const Header& hd, const JpegLayout
                         int v = 0;
                         if (!receive_extend(&b, s, &v)) return b.pos >= len ? MVLDM_JPEG_TRUNCATED : MVLDM_JPEG_CORRUPT;
                         const int nat = kZigzag[k];
-                        blk[nat] = (int16_t)v;              // |v| < 2^15
+                        if (kStore) blk[nat] = (int16_t)v;  // |v| < 2^15
                         sum += (v < 0 ? -v : v) * (int32_t)q[nat];     // <= 64 * 32767 * 255 < 2^31
                     }
                     if (sum > worst) worst = sum;
@@ -368,6 +370,18 @@ void huff_blob(const Huff& t, uint8_t* out) {
 }
 static_assert(sizeof(Huff::look) == 1024 && sizeof(Huff::vals) == 256, "table blob layout");
 
+// the frame's MVLDM_JPEG_TABLE_BYTES: the six tables as the scan header selects them, then the quantisation rows
+void tables_blob(const Header& hd, const JpegLayout& L, uint8_t* tables) {
+    memset(tables, 0, (size_t)kHuffBlobBytes);
+    for (int c = 0; c < L.ncomp; ++c) {
+        huff_blob(hd.dc[hd.comp[c].td], tables + (size_t)(2 * c) * kHuffTabBytes);
+        huff_blob(hd.ac[hd.comp[c].ta], tables + (size_t)(2 * c + 1) * kHuffTabBytes);
+    }
+    uint16_t qt[192];
+    quant_rows(hd, L, qt);
+    memcpy(tables + kHuffTabsBytes, qt, sizeof(qt));
+}
+
 }  // namespace
 
 size_t jpeg_coef_count(int h, int w, int sampling) {
@@ -400,7 +414,7 @@ extern "C" int mvldm_jpeg_entropy(const uint8_t* data, size_t len, int16_t* coef
     if (coef_len < (size_t)L.blocks * 64)
         return set_error(MVLDM_ERR_ARG, "jpeg_entropy: room for %zu coefficients, the %d x %d frame has %zu", coef_len, hd.h, hd.w, (size_t)L.blocks * 64);
     quant_rows(hd, L, qt);
-    return decode_scan(data, len, hd, L, coef, max_s);
+    return decode_scan<true>(data, len, hd, L, coef, max_s);
 }
 
 extern "C" int mvldm_jpeg_idct_host(const int16_t* coef, const uint16_t* qt, uint8_t* dst, int h, int w, int sampling) {
@@ -477,14 +491,7 @@ extern "C" int mvldm_jpeg_scan_prepare(const uint8_t* data, size_t len, uint8_t*
     memset(out + n, 0, room - n);
     desc[1] = (int32_t)(n * 8);
     desc[2] = (int32_t)room;
-    memset(tables, 0, (size_t)kHuffBlobBytes);
-    for (int c = 0; c < L.ncomp; ++c) {
-        huff_blob(hd.dc[hd.comp[c].td], tables + (size_t)(2 * c) * kHuffTabBytes);
-        huff_blob(hd.ac[hd.comp[c].ta], tables + (size_t)(2 * c + 1) * kHuffTabBytes);
-    }
-    uint16_t qt[192];
-    quant_rows(hd, L, qt);
-    memcpy(tables + kHuffTabsBytes, qt, sizeof(qt));
+    tables_blob(hd, L, tables);
     return MVLDM_JPEG_OK;
 }
 
@@ -597,5 +604,280 @@ extern "C" int mvldm_jpeg_entropy_emul_host(const uint8_t* scan, size_t scan_byt
     delete[] buf[1];
     delete[] entry;
     delete[] done;
+    return MVLDM_OK;
+}
+
+// ---- restart intervals on the device: prepare and the emulation of jpeg_rst.hip -----------------------------------------------------
+namespace mvldm {
+namespace {
+
+// intervals of the frame, MCUs to an interval (a frame without DRI, or with one at or above its MCUs, is one interval), and the bytes
+// its region can occupy: at most huff_rst_room(len)
+size_t rst_plan(const Header& hd, const JpegLayout& L, size_t len, uint32_t* n_int, uint32_t* ri, size_t* table_bytes) {
+    const uint32_t mcus = (uint32_t)(L.mcux * L.mcuy);
+    *ri = hd.restart != 0 && (uint32_t)hd.restart < mcus ? (uint32_t)hd.restart : mcus;
+    *n_int = (mcus + *ri - 1) / *ri;
+    const size_t scan_len = len - hd.scan, most = huff_rst_max_intervals(scan_len), cap = *n_int < most ? (size_t)*n_int : most;
+    *table_bytes = huff_rst_table_bytes(cap);           // a stream too short for its markers is refused before entry `cap` is written
+    return huff_rst_need(scan_len, cap);
+}
+
+// a marker structure prepare cannot lay down: decode_scan's own reason for the stream
+int rst_refusal(const uint8_t* data, size_t len, const Header& hd, const JpegLayout& L) {
+    const int reason = decode_scan<false>(data, len, hd, L, nullptr, nullptr);
+    return reason == MVLDM_JPEG_OK || reason == MVLDM_JPEG_RANGE ? MVLDM_JPEG_CORRUPT : reason;
+}
+
+struct RstEmul {                // what the kernel keeps in LDS and in its threads' registers, one entry per thread of a chunk
+    HuffState* buf[2];
+    HuffState* entry;
+    uint32_t *done, *ex, *pre;
+    HuffRstLane* lane;
+};
+
+// One chunk of n_act subsequences described by E.lane: cold pass, rounds, segmented scan of the completed blocks, write pass.
+// Returns the blocks the chunk completed; *carry is the last thread's exit.
+uint32_t rst_chunk(const RstEmul& E, uint32_t n_act, uint32_t sb, const uint8_t* tab, const HuffGeom& G, int16_t* cf, const uint8_t* zigzag, uint32_t* bad,
+                   uint32_t* ended, HuffState* carry, uint32_t* rounds_max) {
+    HuffNoSink none;
+    for (uint32_t i = 0; i < n_act; ++i) {              // cold pass
+        const HuffRstLane& ln = E.lane[i];
+        HuffState st = E.entry[i] = huff_rst_cold(ln, sb);
+        huff_run(ln.sc, ln.bits, tab, G.nl, G.nb, huff_rst_end(ln, sb), sb, &st, &E.done[i], &none);
+        E.buf[0][i] = st;
+    }
+    int cur = 0;
+    uint32_t rounds = 0;
+    for (uint32_t r = 0; r < n_act; ++r) {
+        bool any = false;
+        for (uint32_t i = 0; i < n_act; ++i) {
+            const HuffRstLane& ln = E.lane[i];
+            HuffState st = E.buf[cur][i];
+            if (!ln.first && !huff_same(E.buf[cur][i - 1], E.entry[i])) {
+                E.entry[i] = st = E.buf[cur][i - 1];
+                huff_run(ln.sc, ln.bits, tab, G.nl, G.nb, huff_rst_end(ln, sb), sb, &st, &E.done[i], &none);
+                any = true;
+            }
+            E.buf[cur ^ 1][i] = st;
+        }
+        cur ^= 1;
+        ++rounds;
+        if (!any) break;
+    }
+    if (rounds > *rounds_max) *rounds_max = rounds;
+    uint32_t blocks = 0;
+    for (uint32_t i = 0; i < n_act; ++i) {
+        E.ex[i] = blocks;
+        blocks += E.done[i];
+    }
+    for (uint32_t i = 0; i < n_act; ++i) {              // write pass
+        const HuffRstLane& ln = E.lane[i];
+        HuffRstSink sink{cf, zigzag, G, ln.base + E.ex[i] - E.ex[ln.start], ln.limit, ln.bits, 0u, bad, nullptr};
+        sink.open();
+        HuffState st = E.entry[i];
+        uint32_t again = 0;
+        huff_run(ln.sc, ln.bits, tab, G.nl, G.nb, huff_rst_end(ln, sb), sb, &st, &again, &sink);
+        *ended += sink.ended;
+    }
+    *carry = E.buf[cur][n_act - 1];
+    return blocks;
+}
+
+inline int32_t rst_word(const uint8_t* region, size_t i) {          // the host's packed buffer need not be aligned
+    int32_t v;
+    memcpy(&v, region + 4 * i, 4);
+    return v;
+}
+
+}  // namespace
+}  // namespace mvldm
+
+extern "C" size_t mvldm_jpeg_rst_room(size_t len) { return huff_rst_room(len); }
+
+extern "C" size_t mvldm_jpeg_rst_need(const uint8_t* data, size_t len) {
+    if (data == nullptr) return 0;
+    Header hd;
+    JpegLayout L;
+    if (parse_header(data, len, &hd) != MVLDM_JPEG_OK || !jpeg_layout(hd.h, hd.w, hd.sampling, &L)) return 0;
+    uint32_t n_int, ri;
+    size_t table_bytes;
+    return rst_plan(hd, L, len, &n_int, &ri, &table_bytes);
+}
+
+extern "C" int mvldm_jpeg_rst_prepare(const uint8_t* data, size_t len, uint8_t* scan, size_t scan_off, size_t scan_room, int32_t* desc, uint8_t* tables,
+                                      int32_t* info) {
+    if (data == nullptr || scan == nullptr || desc == nullptr || tables == nullptr) return set_error(MVLDM_ERR_ARG, "jpeg_rst_prepare: null pointer");
+    if ((scan_off & 15) || len >= ((size_t)1 << 28) || scan_room > 0x7FFFFFFFu || scan_room < scan_off)
+        return set_error(MVLDM_ERR_ARG, "jpeg_rst_prepare: offset %zu of %zu bytes for a frame of %zu (a multiple of 16, inside the buffer, below 2^31)", scan_off,
+                         scan_room, len);
+    Header hd;
+    const int reason = parse_header(data, len, &hd);
+    if (info) fill_info(hd, reason, info);
+    desc[0] = (int32_t)scan_off;
+    desc[1] = desc[2] = desc[3] = 0;
+    if (reason != MVLDM_JPEG_OK) return reason;
+    JpegLayout L;
+    if (!jpeg_layout(hd.h, hd.w, hd.sampling, &L)) return MVLDM_JPEG_SIZE;
+    uint32_t n_int, ri;
+    size_t T;
+    const size_t need = rst_plan(hd, L, len, &n_int, &ri, &T);
+    if (scan_room - scan_off < need)
+        return set_error(MVLDM_ERR_ARG, "jpeg_rst_prepare: %zu bytes behind offset %zu, the frame can need %zu (mvldm_jpeg_rst_need; at most mvldm_jpeg_rst_room)",
+                         scan_room - scan_off, scan_off, need);
+    // one walk of the scan: FF 00 -> FF, fill bytes and RSTn dropped, every interval at a 4-byte aligned offset, its pair into the table
+    uint8_t* out = scan + scan_off;
+    memset(out, 0, T);
+    size_t w = T, first = T, i = hd.scan;
+    uint32_t g = 0;
+    int next_rst = 0;
+    auto close = [&]() {
+        const int32_t pair[2] = {(int32_t)first, (int32_t)((w - first) * 8)};
+        memcpy(out + 8 * (size_t)g, pair, 8);           // g < cap: every interval in front of this one ended at a marker of two bytes
+        ++g;
+    };
+    while (true) {
+        if (i >= len) return rst_refusal(data, len, hd, L);
+        const uint8_t b = data[i];
+        if (b != 0xFF) {
+            out[w++] = b;                               // w - T <= bytes read - 2 markers' + 3 of padding an interval: below need - 16
+            ++i;
+            continue;
+        }
+        if (i + 1 >= len) return rst_refusal(data, len, hd, L);
+        if (data[i + 1] == 0x00) {
+            out[w++] = 0xFF;
+            i += 2;
+            continue;
+        }
+        if (g + 1 < n_int) {                            // RSTn, counted 0 .. 7, after any number of fill bytes
+            size_t p = i;
+            while (p < len && data[p] == 0xFF) ++p;
+            if (p >= len || data[p] != 0xD0 + next_rst) return rst_refusal(data, len, hd, L);
+            close();
+            next_rst = (next_rst + 1) & 7;
+            while (w & 3) out[w++] = 0;
+            first = w;
+            i = p + 1;
+        } else {                                        // behind the last interval: EOI
+            if (expect_eoi(data, len, i) != MVLDM_JPEG_OK) return rst_refusal(data, len, hd, L);
+            close();
+            break;
+        }
+    }
+    const size_t total = T + huff_scan_room(w - T);     // <= need
+    memset(out + w, 0, total - w);
+    desc[1] = (int32_t)n_int;
+    desc[2] = (int32_t)total;
+    desc[3] = (int32_t)ri;
+    tables_blob(hd, L, tables);
+    return MVLDM_JPEG_OK;
+}
+
+extern "C" int mvldm_jpeg_rst_entropy_emul_host(const uint8_t* scan, size_t scan_bytes, const int32_t* desc, const uint8_t* tables, int n_img, int h, int w,
+                                                int sampling, int16_t* coef, uint16_t* qt, int32_t* status, int subseq_bits, int chunk_subseqs) {
+    if (scan == nullptr || desc == nullptr || tables == nullptr || coef == nullptr || qt == nullptr || status == nullptr)
+        return set_error(MVLDM_ERR_ARG, "jpeg_rst_entropy_emul_host: null pointer");
+    JpegLayout L;
+    if (n_img < 0 || !jpeg_layout(h, w, sampling, &L)) return set_error(MVLDM_ERR_ARG, "jpeg_rst_entropy_emul_host: %d frames of %d x %d, sampling %d", n_img, h, w, sampling);
+    if (!huff_bits_ok(subseq_bits) || chunk_subseqs < 0 || chunk_subseqs > (1 << 20))
+        return set_error(MVLDM_ERR_ARG, "jpeg_rst_entropy_emul_host: subseq_bits %d (0, or a multiple of 32 in 32 .. %d), chunk of %d", subseq_bits, kHuffMaxBits, chunk_subseqs);
+    const uint32_t sb = subseq_bits ? (uint32_t)subseq_bits : (uint32_t)kHuffDefaultBits;
+    const uint32_t T = chunk_subseqs ? (uint32_t)chunk_subseqs : (uint32_t)kHuffChunk;
+    const HuffGeom G = huff_geom(L);
+    const size_t count = (size_t)L.blocks * 64;
+    RstEmul E{{new HuffState[T], new HuffState[T]}, new HuffState[T], new uint32_t[T], new uint32_t[T], new uint32_t[T], new HuffRstLane[T]};
+    uint8_t zigzag[64];
+    for (uint32_t i = 0; i < 64; ++i) zigzag[i] = huff_zigzag(i);
+    for (int img = 0; img < n_img; ++img) {
+        int16_t* cf = coef + (size_t)img * count;
+        uint16_t* q = qt + (size_t)img * 192;
+        const int32_t* d = desc + (size_t)img * 4;
+        const uint8_t* tab = tables + (size_t)img * kHuffBlobBytes;
+        memset(cf, 0, count * sizeof(int16_t));
+        memcpy(q, tab + kHuffTabsBytes, 192 * sizeof(uint16_t));
+        int reason = MVLDM_JPEG_CORRUPT;
+        uint32_t rounds_max = 0, n_int = 0, ri = 1;
+        const bool ok = huff_rst_desc_ok(d, scan_bytes, G.mcus);
+        const uint8_t* region = scan + (ok ? (size_t)d[0] : 0);
+        if (ok) {
+            n_int = (uint32_t)d[1];
+            ri = (uint32_t)d[3];
+            bool wrong = false;                         // the whole table against the descriptor before any scan bit is read
+            for (uint32_t g = 0; g < n_int; ++g) wrong = wrong || !huff_rst_entry_ok(rst_word(region, 2 * (size_t)g), rst_word(region, 2 * (size_t)g + 1), d);
+            uint32_t bad = 0, ended = 0;
+            for (uint32_t g0 = 0; g0 < n_int && !wrong;) {
+                // the batch: the longest run of whole intervals from g0 whose subsequences fit a chunk
+                uint32_t nbi = 0, sum = 0;
+                for (uint32_t j = 0; j < T && g0 + j < n_int; ++j) {
+                    sum += huff_rst_count_capped((uint32_t)rst_word(region, 2 * (size_t)(g0 + j) + 1), sb, T);
+                    E.pre[j] = sum;
+                    if (sum > T) break;                 // the sums only grow: the batch ends here
+                    nbi = j + 1;
+                }
+                HuffState carry = {0u, 0u};
+                if (nbi == 0) {                         // an interval of more than a chunk: its chunks in order, with the carry
+                    const uint8_t* sc = region + rst_word(region, 2 * (size_t)g0);
+                    const uint32_t bits = (uint32_t)rst_word(region, 2 * (size_t)g0 + 1), cnt = huff_rst_count(bits, sb);
+                    uint32_t base, limit;
+                    huff_rst_blocks(G, g0, ri, &base, &limit);
+                    for (uint32_t ch0 = 0; ch0 < cnt; ch0 += T) {
+                        const uint32_t n_act = cnt - ch0 < T ? cnt - ch0 : T;
+                        for (uint32_t i = 0; i < n_act; ++i) E.lane[i] = HuffRstLane{sc, bits, ch0 + i, 0u, base, limit, carry, i == 0};
+                        base += rst_chunk(E, n_act, sb, tab, G, cf, zigzag, &bad, &ended, &carry, &rounds_max);
+                    }
+                    g0 += 1;
+                } else {
+                    const uint32_t n_act = E.pre[nbi - 1];
+                    for (uint32_t i = 0; i < n_act; ++i) {
+                        const uint32_t j = huff_rst_find(E.pre, nbi, i), start = j ? E.pre[j - 1] : 0u;
+                        uint32_t base, limit;
+                        huff_rst_blocks(G, g0 + j, ri, &base, &limit);
+                        E.lane[i] = HuffRstLane{region + rst_word(region, 2 * (size_t)(g0 + j)), (uint32_t)rst_word(region, 2 * (size_t)(g0 + j) + 1), i - start, start, base,
+                                                limit, HuffState{0u, 0u}, i == start};
+                    }
+                    rst_chunk(E, n_act, sb, tab, G, cf, zigzag, &bad, &ended, &carry, &rounds_max);
+                    g0 += nbi;
+                }
+            }
+            if (!wrong && !bad && ended == n_int) reason = MVLDM_JPEG_OK;
+        }
+        int32_t worst = 0;
+        if (reason == MVLDM_JPEG_OK) {          // the second launch: DC prefixes per interval in scan order, S of every block
+            bool bad = false;
+            for (uint32_t c = 0; c < G.ncomp; ++c) {
+                const uint32_t per = c == 0 ? G.nl : 1u, nc = G.mcus * per, period = ri * per;
+                long long pred = 0;
+                for (uint32_t j = 0; j < nc; ++j) {
+                    const uint32_t m = c == 0 ? j / G.nl : j, b = c == 0 ? j - m * G.nl : G.nl + c - 1;
+                    int16_t* blk = cf + (size_t)huff_block_index(G, m, b) * 64;
+                    bool f = j % period == 0;
+                    long long v = blk[0];
+                    huff_rst_join(false, pred, &f, &v);
+                    pred = v;
+                    if (pred < -32768 || pred > 32767) {
+                        bad = true;
+                        continue;
+                    }
+                    blk[0] = (int16_t)pred;
+                    int32_t sum = 0;
+                    for (int k = 0; k < 64; ++k) sum += (blk[k] < 0 ? -(int32_t)blk[k] : (int32_t)blk[k]) * (int32_t)q[c * 64 + k];
+                    if (sum > worst) worst = sum;
+                }
+            }
+            reason = bad ? MVLDM_JPEG_CORRUPT : worst > kJpegGuard ? MVLDM_JPEG_RANGE : MVLDM_JPEG_OK;
+            if (bad) worst = 0;
+        }
+        status[img * 4 + 0] = reason;
+        status[img * 4 + 1] = worst;
+        status[img * 4 + 2] = (int32_t)rounds_max;
+        status[img * 4 + 3] = (int32_t)n_int;
+    }
+    delete[] E.buf[0];
+    delete[] E.buf[1];
+    delete[] E.entry;
+    delete[] E.done;
+    delete[] E.ex;
+    delete[] E.pre;
+    delete[] E.lane;
     return MVLDM_OK;
 }

@@ -252,4 +252,110 @@ MVLDM_HD void huff_run(const uint8_t* scan, uint32_t bit_len, const uint8_t* tab
     *blocks = nblk;
 }
 
+// ---- restart intervals (jpeg_rst.hip, mvldm_jpeg_rst_entropy_emul_host) ---------------------------------------------------------------
+// A frame's region of the packed buffer: the interval table -- int32 pairs (byte offset inside the region, exact bit length), n of them,
+// rounded up to 16 bytes -- then the destuffed intervals, each at a 4-byte aligned offset (huff_word reads aligned dwords relative to the
+// interval's first byte), and zeros up to huff_scan_room behind the last.  A bit position is relative to its interval, bit_len is the
+// interval's: DEAD stays inside it.  desc[0..3] = offset of the region (a multiple of 16), intervals, bytes occupied, MCUs per interval.
+MVLDM_HD size_t huff_rst_table_bytes(size_t n) { return (n * 8 + 15) & ~(size_t)15; }
+// what a frame with `scan_len` bytes behind its scan header and at most n intervals can occupy: a marker takes two bytes away and the
+// alignment in front of the next interval gives at most three back
+MVLDM_HD size_t huff_rst_need(size_t scan_len, size_t n) { return huff_rst_table_bytes(n) + huff_scan_room(scan_len + n); }
+MVLDM_HD size_t huff_rst_max_intervals(size_t scan_len) { return scan_len / 2 + 1; }
+MVLDM_HD size_t huff_rst_room(size_t len) { return huff_rst_need(len, huff_rst_max_intervals(len)); }
+
+// false: nothing of the frame is read
+MVLDM_HD bool huff_rst_desc_ok(const int32_t* d, size_t scan_bytes, uint32_t mcus) {
+    if (d[0] < 0 || d[1] < 1 || d[2] < 0 || d[3] < 1 || (d[0] & 15) || (uint32_t)d[3] > mcus) return false;
+    if ((mcus + (uint32_t)d[3] - 1) / (uint32_t)d[3] != (uint32_t)d[1]) return false;
+    if ((size_t)d[2] < huff_rst_table_bytes((size_t)d[1]) + 16) return false;
+    return (size_t)d[0] <= scan_bytes && scan_bytes - (size_t)d[0] >= (size_t)d[2];
+}
+// one pair of the table against the region's descriptor: behind the table, aligned, not empty, and the widest read of a symbol that
+// starts at its last bit (12 bytes past its bytes) inside the bytes occupied.  false: no scan bit of the frame is read
+MVLDM_HD bool huff_rst_entry_ok(int32_t off, int32_t bits, const int32_t* d) {
+    if (off < 0 || bits < 1 || (off & 3) || (size_t)off < huff_rst_table_bytes((size_t)d[1])) return false;
+    return (size_t)off + (((size_t)bits + 7) >> 3) + 12 <= (size_t)d[2];
+}
+// subsequences of an interval; `cap` + 1 stands for anything above cap, so that the sum over a chunk's worth of intervals fits 32 bits
+MVLDM_HD uint32_t huff_rst_count(uint32_t bits, uint32_t sb) { return (uint32_t)(((uint64_t)bits + sb - 1) / sb); }
+MVLDM_HD uint32_t huff_rst_count_capped(uint32_t bits, uint32_t sb, uint32_t cap) {
+    const uint32_t c = huff_rst_count(bits, sb);
+    return c > cap ? cap + 1 : c;
+}
+// pre[0 .. n): inclusive sums of the counts of a batch's intervals (every count >= 1).  The interval of the batch's subsequence t <
+// pre[n - 1]: the first j with pre[j] > t
+MVLDM_HD uint32_t huff_rst_find(const uint32_t* pre, uint32_t n, uint32_t t) {
+    uint32_t lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (pre[mid] > t) hi = mid;
+        else lo = mid + 1;
+    }
+    return lo;
+}
+
+// What one thread of a chunk knows about its subsequence: subsequence s of the interval at sc (bits long), whose first subsequence of
+// this chunk is thread `start`.  first: the thread does not take its neighbour's exit -- its entry entry0 is true (the interval's
+// start, or the carry of the chunk before when an interval is longer than a chunk).  base: the block at which thread `start` begins,
+// limit: the end of the interval's blocks, at most the frame's.
+struct HuffRstLane {
+    const uint8_t* sc;
+    uint32_t bits, s, start, base, limit;
+    HuffState entry0;
+    bool first;
+};
+MVLDM_HD uint32_t huff_rst_end(const HuffRstLane& ln, uint32_t sb) {
+    const uint64_t e = ((uint64_t)ln.s + 1) * sb;
+    return e < ln.bits ? (uint32_t)e : ln.bits;
+}
+MVLDM_HD HuffState huff_rst_cold(const HuffRstLane& ln, uint32_t sb) { return ln.first ? ln.entry0 : HuffState{ln.s * sb, 0u}; }
+// interval g of a frame whose intervals hold ri MCUs: its first block and the end of its blocks
+MVLDM_HD void huff_rst_blocks(const HuffGeom& G, uint32_t g, uint32_t ri, uint32_t* base, uint32_t* limit) {
+    const uint64_t b = (uint64_t)g * ri * G.nb, e = b + (uint64_t)ri * G.nb;
+    *base = b < G.total ? (uint32_t)b : G.total;
+    *limit = e < G.total ? (uint32_t)e : G.total;
+}
+
+// The write pass's sink of the restart form: HuffCoefSink with the interval's end for the frame's.  Every store is guarded by n < limit
+// <= blocks of the frame, so the padding bits of one interval never write into the next.  `ended`: the interval's last block completed
+// in this subsequence; it has to leave fewer than 8 bits of the interval (decode_scan's test in front of a marker and at the end).
+struct HuffRstSink {
+    int16_t* coef;
+    const uint8_t* zigzag;
+    HuffGeom G;
+    uint32_t n, limit, bits, ended;
+    uint32_t* bad;
+    int16_t* blk;
+    MVLDM_HD void fault() {
+        if (blk != nullptr) *bad = 1u;
+    }
+    MVLDM_HD void open() {
+        if (n < limit) {
+            const uint32_t m = n / G.nb;
+            blk = coef + (size_t)huff_block_index(G, m, n - m * G.nb) * 64;
+        } else {
+            blk = nullptr;
+        }
+    }
+    MVLDM_HD void put(uint32_t k, int v) {
+        if (blk != nullptr) blk[zigzag[k & 63]] = (int16_t)v;
+    }
+    MVLDM_HD void done(uint32_t p) {
+        ++n;
+        if (n == limit) {
+            ended = 1u;
+            if (bits - p >= 8u) *bad = 1u;
+        }
+        open();
+    }
+};
+
+// The DC differences of a component in scan order become predictions by a SEGMENTED sum: a block that opens a restart interval (head)
+// starts from 0.  (f, v) is the pair of the scan: f says a head lies in the range summed so far.  later after earlier:
+MVLDM_HD void huff_rst_join(bool ef, long long ev, bool* f, long long* v) {
+    if (!*f) *v += ev;
+    *f = *f || ef;
+}
+
 }  // namespace mvldm

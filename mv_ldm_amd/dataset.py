@@ -139,15 +139,17 @@ class _RE10KReader:
     """what `RE10KScenes` and `RE10KTrainLoader` share: which chunks are read (`root/*.torch` sorted, or those `root/index.json` names
     for `scenes`), how their frames are decoded, and the per-scene steps of `DatasetRE10k.__iter__`.  Nothing here draws a random number."""
 
-    def __init__(self, root, scenes, image_shape, make_baseline_1, baseline_epsilon, max_fov, crop, device_decode, device_entropy):
+    def __init__(self, root, scenes, image_shape, make_baseline_1, baseline_epsilon, max_fov, crop, device_decode, device_entropy, device_restarts=False):
         self.root = Path(root)
         self.scenes = None if scenes is None else list(scenes)
         self.image_shape = (int(image_shape[0]), int(image_shape[1]))
         self.make_baseline_1, self.baseline_epsilon, self.max_fov = bool(make_baseline_1), float(baseline_epsilon), float(max_fov)
         self.crop = bool(crop)
-        self.device_entropy = bool(device_entropy) and self.crop           # implies device_decode: the Huffman scan is decoded on the device too
+        self.device_restarts = bool(device_restarts) and self.crop         # implies device_entropy: frames with restart intervals too
+        self.device_entropy = (bool(device_entropy) or self.device_restarts) and self.crop     # implies device_decode: the Huffman scan is decoded on the device too
         self.device_decode = (bool(device_decode) or self.device_entropy) and self.crop
-        self.entropy = "device" if self.device_entropy else "host"         # `ops.jpeg_decode`'s mode
+        self.entropy = "device" if self.device_entropy else "host"         # `ops.jpeg_decode`'s modes
+        self.restarts = "device" if self.device_restarts else "host"
         if self.scenes is None:
             self.chunks = sorted(p for p in self.root.iterdir() if p.suffix == ".torch")
         else:
@@ -207,15 +209,17 @@ class RE10KScenes(_RE10KReader):
     on the device, PNG frames and frames the library refuses through `decode_image` into their slots -- and its device tensor feeds
     the crop shim: the same bytes.  `device_entropy` (implies `device_decode`): the host only removes the scan's byte stuffing and the
     Huffman decoding runs on the device as well (`ops.jpeg_decode(entropy="device")`): a twelfth of the upload, the same bytes.
+    `device_restarts` (implies `device_entropy`): frames with restart intervals are decoded on the device too, interval by interval
+    (`ops.jpeg_decode(entropy="device", restarts="device")`), instead of by the host's Huffman pass: the same bytes.
     `crop=False` leaves out the device: the groups then carry the decoded uint8 frames `[1, v, h, w, 3]` and the unscaled intrinsics
     (inspection, CPU tests)."""
 
     def __init__(self, root, stage: str = "test", index=None, image_shape: Tuple[int, int] = (256, 256), make_baseline_1: bool = True,
                  baseline_epsilon: float = 1e-3, max_fov: float = 100.0, scenes: Optional[Sequence[str]] = None, crop: bool = True,
-                 device_decode: bool = False, device_entropy: bool = False):
+                 device_decode: bool = False, device_entropy: bool = False, device_restarts: bool = False):
         if index is None:
             raise ValueError("RE10KScenes needs an evaluation index (load_index(path), or the path)")
-        super().__init__(Path(root) / stage, scenes, image_shape, make_baseline_1, baseline_epsilon, max_fov, crop, device_decode, device_entropy)
+        super().__init__(Path(root) / stage, scenes, image_shape, make_baseline_1, baseline_epsilon, max_fov, crop, device_decode, device_entropy, device_restarts)
         self.index = load_index(index) if isinstance(index, (str, Path)) else {k: v for k, v in index.items() if v}
 
     def _views(self, example: dict, indices: Sequence[int], extrinsics, intrinsics, scale) -> Optional[dict]:
@@ -226,7 +230,7 @@ class RE10KScenes(_RE10KReader):
             return None
         if frames is None:
             from . import ops
-            images = ops.jpeg_decode(data, entropy=self.entropy)
+            images = ops.jpeg_decode(data, entropy=self.entropy, restarts=self.restarts)
         else:
             images = torch.from_numpy(np.stack(frames))
         idx = torch.tensor(list(indices), dtype=torch.int64)
@@ -496,6 +500,8 @@ class RE10KTrainLoader(_RE10KReader):
     library refuses are decoded as before and uploaded into their slots, so a batch may mix them.  The bytes, and the draws, are the same.
     `device_entropy` (implies `device_decode`): the workers only parse the markers and remove the byte stuffing; the Huffman scans are
     decoded on the device too (`ops.jpeg_decode(entropy="device")`), at the price of one small status read-back per frame size.
+    `device_restarts` (implies `device_entropy`): so are the scans of frames with restart intervals (`restarts="device"`), which
+    `device_entropy` alone leaves to the host's Huffman pass.
 
     No rank sharding: like the reference's iterable dataset, every rank walks all chunks, under its own torch seed."""
 
@@ -504,7 +510,7 @@ class RE10KTrainLoader(_RE10KReader):
     def __init__(self, root, stage: str = "train", view_sampler: Optional[ViewSampler] = None, image_shape: Tuple[int, int] = (256, 256),
                  batch_size: int = 6, drop_last: bool = True, augment: bool = False, make_baseline_1: bool = True, baseline_epsilon: float = 1e-3,
                  max_fov: float = 100.0, scenes: Optional[Sequence[str]] = None, decode_workers: int = 0, crop: bool = True,
-                 random_transform_extrinsics: bool = False, device_decode: bool = False, device_entropy: bool = False):
+                 random_transform_extrinsics: bool = False, device_decode: bool = False, device_entropy: bool = False, device_restarts: bool = False):
         if stage not in ("train", "val"):
             raise ValueError(f"RE10KTrainLoader reads stage train or val, got {stage!r} (RE10KScenes reads test)")
         if random_transform_extrinsics:
@@ -513,7 +519,7 @@ class RE10KTrainLoader(_RE10KReader):
             view_sampler = ViewSamplerBounded(num_context_views=2, num_target_views=3, min_distance_between_context_views=50,
                                               max_distance_between_context_views=180, stage=stage)
         super().__init__(Path(root) / ("test" if stage == "val" or scenes is not None else stage),     # `data_stage`
-                         scenes, image_shape, make_baseline_1, baseline_epsilon, max_fov, crop, device_decode, device_entropy)
+                         scenes, image_shape, make_baseline_1, baseline_epsilon, max_fov, crop, device_decode, device_entropy, device_restarts)
         self.stage, self.view_sampler = stage, view_sampler
         self.batch_size, self.drop_last, self.augment = int(batch_size), bool(drop_last), bool(augment)
         self.decode_workers = max(0, min(int(decode_workers), self.MAX_DECODE_WORKERS))
@@ -596,7 +602,7 @@ class RE10KTrainLoader(_RE10KReader):
             dev = torch.device("cuda", torch.cuda.current_device())
             for (h, w), members in by_size.items():
                 if self.device_decode:      # coefficients up, frames decoded on the device
-                    source = ops.jpeg_decode([blobs[i * v + t] for i in members for t in range(v)], pool=self._workers(), entropy=self.entropy)
+                    source = ops.jpeg_decode([blobs[i * v + t] for i in members for t in range(v)], pool=self._workers(), entropy=self.entropy, restarts=self.restarts)
                 else:
                     staged = torch.empty(len(members) * v, h, w, 3, dtype=torch.uint8, pin_memory=True)      # one upload per frame size
                     host = staged.numpy()

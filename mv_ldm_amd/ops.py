@@ -1239,6 +1239,77 @@ def jpeg_status_download(status: torch.Tensor) -> np.ndarray:
     return status.cpu().numpy()
 
 
+def jpeg_rst_room(n: int) -> int:
+    """bytes of the packed buffer ANY frame of n encoded bytes can take on the restart path (`mvldm_jpeg_rst_room`): a multiple of 16"""
+    return int(L.load().mvldm_jpeg_rst_room(n))
+
+
+def jpeg_rst_need(blob: bytes) -> int:
+    """bytes of the packed buffer THIS frame can take (`mvldm_jpeg_rst_need`, from its header: interval table, scan, alignment, padding);
+    0 for a frame the parser refuses.  At most `jpeg_rst_room(len(blob))`; what `jpeg_rst_prepare` asks for behind its offset."""
+    return int(L.load().mvldm_jpeg_rst_need(blob, len(blob)))
+
+
+def jpeg_rst_prepare(blob: bytes, scan: Optional[np.ndarray] = None, scan_off: int = 0, desc: Optional[np.ndarray] = None,
+                     tables: Optional[np.ndarray] = None) -> JpegScan:
+    """`jpeg_scan_prepare` for frames with and without restart intervals (`mvldm_jpeg_rst_prepare`): the frame's region -- interval table
+    and destuffed intervals -- into `scan[scan_off:]` (room for `jpeg_rst_need(blob)` bytes behind the offset, a multiple of 16), the
+    descriptor (offset, intervals, bytes, MCUs per interval) into `desc` and the tables into `tables`: what `jpeg_rst_entropy_device`
+    takes.  Never answers `_lib.JPEG_RESTART`.  Buffers left out are made.  Releases the GIL; keeps no state."""
+    if scan is None:
+        scan = np.zeros(scan_off + jpeg_rst_need(blob), dtype=np.uint8)
+    if desc is None:
+        desc = np.zeros(4, dtype=np.int32)
+    if tables is None:
+        tables = np.zeros(L.JPEG_TABLE_BYTES, dtype=np.uint8)
+    assert scan.dtype == np.uint8 and scan.flags.c_contiguous and scan.ndim == 1
+    assert desc.dtype == np.int32 and desc.flags.c_contiguous and desc.size == 4
+    assert tables.dtype == np.uint8 and tables.flags.c_contiguous and tables.size == L.JPEG_TABLE_BYTES
+    info = (C.c_int32 * 8)()
+    rc = L.load().mvldm_jpeg_rst_prepare(blob, len(blob), scan.ctypes.data, scan_off, scan.size, desc.ctypes.data, tables.ctypes.data, info)
+    if rc < 0:
+        L.check(rc)
+    return JpegScan(rc, JpegInfo(*info), scan, desc, tables)
+
+
+def jpeg_rst_entropy_emul(scan: np.ndarray, desc: np.ndarray, tables: np.ndarray, h: int, w: int, sampling: int, coef: Optional[np.ndarray] = None,
+                          qt: Optional[np.ndarray] = None, status: Optional[np.ndarray] = None, subseq_bits: int = 0, chunk_subseqs: int = 0):
+    """`jpeg_entropy_emul` of the restart path (`mvldm_jpeg_rst_entropy_emul_host`) over the frames `jpeg_rst_prepare` laid down ->
+    (coef, qt, status int32 `[n, 4]` = reason, largest S, rounds, intervals): tests and tools"""
+    desc, tables = desc.reshape(-1, 4), tables.reshape(-1, L.JPEG_TABLE_BYTES)
+    n, count = desc.shape[0], jpeg_coef_count(h, w, sampling)
+    assert scan.dtype == np.uint8 and scan.flags.c_contiguous and desc.dtype == np.int32 and desc.flags.c_contiguous
+    assert tables.dtype == np.uint8 and tables.flags.c_contiguous and tables.shape[0] == n and count > 0
+    coef = np.empty((n, count), dtype=np.int16) if coef is None else coef
+    qt = np.empty((n, 192), dtype=np.uint16) if qt is None else qt
+    status = np.empty((n, 4), dtype=np.int32) if status is None else status
+    assert coef.dtype == np.int16 and coef.flags.c_contiguous and coef.size == n * count and qt.dtype.itemsize == 2 and qt.flags.c_contiguous and qt.size == n * 192
+    assert status.dtype == np.int32 and status.flags.c_contiguous and status.size == n * 4
+    L.check(L.load().mvldm_jpeg_rst_entropy_emul_host(scan.ctypes.data, scan.size, desc.ctypes.data, tables.ctypes.data, n, h, w, sampling, coef.ctypes.data,
+                                                      qt.ctypes.data, status.ctypes.data, subseq_bits, chunk_subseqs))
+    return coef, qt, status
+
+
+def jpeg_rst_entropy_device(scan: torch.Tensor, desc: torch.Tensor, tables: torch.Tensor, h: int, w: int, sampling: int, coef: Optional[torch.Tensor] = None,
+                            qt: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None, subseq_bits: int = 0):
+    """`mvldm_jpeg_rst_entropy_device`: `jpeg_entropy_device` for the frames `jpeg_rst_prepare` laid down, with and without restart
+    intervals -> (coef, qt, status int32 `[n, 4]` = reason, largest S, rounds, intervals).  A memset and two launches; nothing is
+    allocated when the three outputs are given, and nothing is read back, so the call can be captured."""
+    n, count = desc.shape[0], jpeg_coef_count(h, w, sampling)
+    assert scan.is_cuda and scan.is_contiguous() and scan.dtype == torch.uint8 and scan.dim() == 1
+    assert desc.is_cuda and desc.is_contiguous() and desc.dtype == torch.int32 and tuple(desc.shape) == (n, 4)
+    assert tables.is_cuda and tables.is_contiguous() and tables.dtype == torch.uint8 and tuple(tables.shape) == (n, L.JPEG_TABLE_BYTES) and count > 0
+    coef = torch.empty(n, count, dtype=torch.int16, device=scan.device) if coef is None else coef
+    qt = torch.empty(n, 192, dtype=torch.int16, device=scan.device) if qt is None else qt
+    status = torch.empty(n, 4, dtype=torch.int32, device=scan.device) if status is None else status
+    assert coef.is_cuda and coef.is_contiguous() and coef.dtype == torch.int16 and tuple(coef.shape) == (n, count)
+    assert qt.is_cuda and qt.is_contiguous() and qt.dtype == torch.int16 and tuple(qt.shape) == (n, 192)
+    assert status.is_cuda and status.is_contiguous() and status.dtype == torch.int32 and tuple(status.shape) == (n, 4)
+    L.check(L.load().mvldm_jpeg_rst_entropy_device(scan.data_ptr(), scan.numel(), desc.data_ptr(), tables.data_ptr(), n, h, w, sampling, coef.data_ptr(),
+                                                   qt.data_ptr(), status.data_ptr(), subseq_bits, stream()))
+    return coef, qt, status
+
+
 def _map(pool, f, xs) -> list:
     """`[f(x) for x in xs]`, on `pool` when one is given and there is more than one job (results in the order of `xs`)"""
     return list(pool.map(f, xs)) if pool is not None and len(xs) > 1 else [f(x) for x in xs]
@@ -1271,7 +1342,22 @@ def _jpeg_stage_device(blobs, members, info):
                                                          on_dev[end:end + m * tb].view(m, tb), info.h, info.w, info.sampling)
 
 
-def jpeg_decode(blobs: Sequence[bytes], pool=None, device=None, entropy: str = "host") -> torch.Tensor:
+def _jpeg_stage_restart(blobs, members, info):
+    """[regions | tables | descriptors], filled by `jpeg_rst_prepare`; the coefficients are `jpeg_rst_entropy_device`'s"""
+    m, tb = len(members), L.JPEG_TABLE_BYTES
+    offs = [0]
+    for i in members:
+        offs.append(offs[-1] + jpeg_rst_need(blobs[i]))         # a multiple of 16: from the frame's header, not the bound for any frame
+    end = offs[-1]
+    buf = torch.empty(end + m * (tb + 16), dtype=torch.uint8, pin_memory=True)
+    host = buf.numpy()
+    tables, desc = host[end:end + m * tb].reshape(m, tb), host[end + m * tb:].view(np.int32).reshape(m, 4)
+    jobs = [(jpeg_rst_prepare, blobs[i], host[:offs[j + 1]], offs[j], desc[j], tables[j]) for j, i in enumerate(members)]
+    return buf, jobs, lambda on_dev: jpeg_rst_entropy_device(on_dev[:end], on_dev[end + m * tb:].view(torch.int32).view(m, 4),
+                                                             on_dev[end:end + m * tb].view(m, tb), info.h, info.w, info.sampling)
+
+
+def jpeg_decode(blobs: Sequence[bytes], pool=None, device=None, entropy: str = "host", restarts: str = "host") -> torch.Tensor:
     """encoded frames of ONE size -> uint8 `[n, h, w, 3]` on the current device, the bytes `Image.open(...).convert("RGB")` gives.
 
     Per frame the host parses the markers and decodes the Huffman scan (`mvldm_jpeg_entropy`: no Pillow, no GIL; on `pool`, a
@@ -1283,14 +1369,20 @@ def jpeg_decode(blobs: Sequence[bytes], pool=None, device=None, entropy: str = "
     pinned tensor per layout -- scans, tables, descriptors: about a twelfth of the coefficients -- and each layout is one upload, one
     `mvldm_jpeg_entropy_device`, one `mvldm_jpeg_decode` and then ONE small download of the frames' status words: a synchronisation
     with the device that the host path does not have.  A frame with restart intervals takes the host's entropy pass into the same device
-    call; a frame whose status is not 0, or that prepare refused, goes through `decode_image` as above.  The same bytes either way."""
+    call; a frame whose status is not 0, or that prepare refused, goes through `decode_image` as above.  The same bytes either way.
+
+    `restarts="device"` (needs `entropy="device"`): every frame of a layout, with or without restart intervals, goes through
+    `mvldm_jpeg_rst_prepare` and ONE `mvldm_jpeg_rst_entropy_device` per layout -- the intervals are independent streams with known start
+    states -- and `mvldm_jpeg_entropy` is never called.  The same bytes again."""
     from .dataset import decode_image
     n = len(blobs)
     if n == 0:
         raise ValueError("jpeg_decode: no frames")
     if entropy not in ("host", "device"):
         raise ValueError(f"jpeg_decode: entropy {entropy!r} (host or device)")
-    stage = _jpeg_stage_device if entropy == "device" else _jpeg_stage_host
+    if restarts not in ("host", "device") or (restarts == "device" and entropy != "device"):
+        raise ValueError(f"jpeg_decode: restarts {restarts!r} with entropy {entropy!r} (host or device; device needs entropy=\"device\")")
+    stage = _jpeg_stage_host if entropy == "host" else _jpeg_stage_restart if restarts == "device" else _jpeg_stage_device
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     infos = [jpeg_probe(b) for b in blobs]
     groups: dict = {}

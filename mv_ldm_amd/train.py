@@ -2221,7 +2221,7 @@ TRAIN_CONFIG = {
 
 def main(argv=None, overrides=None):
     """`python -m mv_ldm_amd.train --dataset ROOT [--stage train] --steps N [--batch 6] [--res 256] [--seed S] [--resume CKPT] [--save CKPT]
-    [--log-every K] [--decode-workers W] [--device-decode] [--device-entropy] [--allow-random-init] [key.sub=value ...]`: N optimizer steps on the RE10K root's chunks
+    [--log-every K] [--decode-workers W] [--device-decode] [--device-entropy] [--device-restarts] [--allow-random-init] [key.sub=value ...]`: N optimizer steps on the RE10K root's chunks
     (`dataset.RE10KTrainLoader`: the reference's shuffles, view sampler, augmentation coin; images through the crop shim on the device).
     Overrides as in `generate`: `dataset.view_sampler.*`, `dataset.augment`, `trainer.precision`, `optimizer.lr`,
     `trainer.accumulate_grad_batches`, and the `model.*` / `checkpointing.load` keys `generate.build_pipeline` reads.  Every optimizer step
@@ -2253,6 +2253,8 @@ def main(argv=None, overrides=None):
                                                                   "upsampling and colour on the device; the same bytes")
     ap.add_argument("--device-entropy", action="store_true", help="JPEG frames: the Huffman scan on the device as well (implies --device-decode): the host "
                                                                    "only removes the byte stuffing; the same bytes")
+    ap.add_argument("--device-restarts", action="store_true", help="JPEG frames with restart intervals: their Huffman scan on the device too, interval by "
+                                                                    "interval (implies --device-entropy); the same bytes")
     ap.add_argument("--allow-random-init", action="store_true", help="no pretrained weights: random ones of the right shape")
     args = ap.parse_args(argv)
     cfg = merge_config(DEFAULT_CONFIG, TRAIN_CONFIG)
@@ -2302,7 +2304,8 @@ def main(argv=None, overrides=None):
     loader = RE10KTrainLoader(args.dataset, args.stage, view_sampler=sampler, image_shape=(args.res, args.res), batch_size=args.batch, augment=bool(d["augment"]),
                               make_baseline_1=bool(d["make_baseline_1"]), baseline_epsilon=float(d["baseline_epsilon"]), max_fov=float(d["max_fov"]),
                               scenes=[scenes] if isinstance(scenes, str) else scenes, decode_workers=args.decode_workers,
-                              random_transform_extrinsics=bool(d["random_transform_extrinsics"]), device_decode=args.device_decode, device_entropy=args.device_entropy)
+                              random_transform_extrinsics=bool(d["random_transform_extrinsics"]), device_decode=args.device_decode, device_entropy=args.device_entropy,
+                              device_restarts=args.device_restarts)
 
     def windows():
         """`acc` batches at a time, epoch after epoch"""

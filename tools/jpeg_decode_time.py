@@ -1,5 +1,5 @@
 """time the JPEG decoder (mv_ldm_amd/ops.py jpeg_decode: csrc/jpeg_host.cpp on the host, csrc/jpeg.hip on the device) next to Pillow:
-    python tools/jpeg_decode_time.py [--entropy] [--json OUT]
+    python tools/jpeg_decode_time.py [--entropy] [--restarts] [--json OUT]
 Two 360 x 640 4:2:0 quality-90 frames built here: "fixture" (tests/train_fixture.py's kind: 45 x 80 noise repeated 8 x each way, so every
 luma block is flat) and "photo" (smooth ramps plus +-12 of noise: every block has AC coefficients).  Per frame:
   * host: `mvldm_jpeg_entropy` (markers + Huffman scan into a reused buffer) on ONE thread, best of 5 passes of 20 calls, ms a frame; and
@@ -12,6 +12,13 @@ luma block is flat) and "photo" (smooth ramps plus +-12 of noise: every block ha
     bytes uploaded per frame (scan with padding + tables + descriptor); next to it, IN THE SAME RUN, the host's entropy pass spread over a
     pool of 16 threads (wall time of 30 frames / 30) and `mvldm_jpeg_scan_prepare` on one thread.  Coefficients are checked against the
     host's before anything is timed.
+  * `--restarts`: the same pixels re-encoded with `restart_marker_rows=1` (one restart interval per MCU row: 23 of 40 MCUs) through
+    `mvldm_jpeg_rst_entropy_device` (csrc/jpeg_rst.hip): per subseq_bits in 128, 256, 512, 1024 and n = 5, 30 the hot / cold microseconds
+    per frame and the rounds of the worst chunk; next to it, IN THE SAME RUN, `mvldm_jpeg_entropy_device` on the stream without markers,
+    the host's entropy pass of the restart stream on one thread and over 16 workers, `mvldm_jpeg_rst_prepare` on one thread and the bytes
+    uploaded per frame.  Coefficients are checked against the host's before anything is timed.  The same again under
+    "device_restarts_8_mcus" for `restart_marker_blocks=8` (an interval of 8 MCUs, about 3,000 bits: shorter than the ~9,000 bits a cold
+    decoder needs to synchronise, which an MCU row of 40 is not).
 The device result is checked against Pillow's before anything is timed.  No threshold: the figures go to DESIGN.md and profiles/."""
 import json, os, sys, time
 from io import BytesIO
@@ -123,6 +130,53 @@ for name, pixels in FRAMES.items():
                 cold = sorted(cold)[3]
                 e[f"n{n}_bits{sb}"] = {"hot_us_per_frame": round(hot / n, 3), "cold_us_per_frame": round(cold / n, 3), "hot_us_per_call": round(hot, 2),
                                        "cold_us_per_call": round(cold, 2), "rounds": int(status[:, 2].max())}
+    if "--restarts" in sys.argv:
+        from concurrent.futures import ThreadPoolExecutor
+        from mv_ldm_amd import _lib
+        for tag, markers in (("device_restarts", dict(restart_marker_rows=1)), ("device_restarts_8_mcus", dict(restart_marker_blocks=8))):
+            e = r[tag] = {}
+            buf = BytesIO()
+            Image.fromarray(pixels).save(buf, format="JPEG", quality=90, subsampling=2, **markers)
+            rblob = buf.getvalue()
+            rcoef, rqt = np.zeros(count, dtype=np.int16), np.zeros(192, dtype=np.int16)
+            reason, rmax_s = ops.jpeg_entropy(rblob, rcoef, rqt)
+            assert reason == 0 and np.array_equal(np.asarray(Image.open(BytesIO(rblob)).convert("RGB")), want), "markers change no pixel"
+            plain, marked = ops.jpeg_scan_prepare(blob), ops.jpeg_rst_prepare(rblob)
+            assert plain.reason == 0 and marked.reason == 0
+            e["stream_bytes"], e["stream_bytes_without_markers"], e["intervals"], e["mcus_per_interval"] = len(rblob), len(blob), int(marked.desc[1]), int(marked.desc[3])
+            e["upload_bytes_per_frame"] = int(marked.desc[2]) + _lib.JPEG_TABLE_BYTES + 16
+            e["upload_bytes_per_frame_without_markers"] = int(plain.desc[2]) + _lib.JPEG_TABLE_BYTES + 16
+            e["coefficient_bytes_per_frame"] = count * 2
+            e["prepare_ms_per_frame"] = round(best_ms(lambda: ops.jpeg_rst_prepare(rblob, marked.scan, 0, marked.desc, marked.tables)), 4)
+            e["host_entropy_ms_per_frame"] = round(best_ms(lambda: ops.jpeg_entropy(rblob, rcoef, rqt)), 4)
+            with ThreadPoolExecutor(16) as pool:
+                bufs = [(np.zeros(count, dtype=np.int16), np.zeros(192, dtype=np.int16)) for _ in range(30)]
+                spread = lambda: list(pool.map(lambda b: ops.jpeg_entropy(rblob, b[0], b[1]), bufs))
+                e["host_entropy_16_workers_ms_per_frame"] = round(best_ms(spread) / 30, 4)
+            for n in (5, 30):
+                dc, dq = torch.empty(n, count, dtype=torch.int16, device="cuda"), torch.empty(n, 192, dtype=torch.int16, device="cuda")
+                st = torch.empty(n, 4, dtype=torch.int32, device="cuda")
+                for key, p, fn, hcoef, hmax in (("restarts", marked, ops.jpeg_rst_entropy_device, rcoef, rmax_s), ("no_markers", plain, ops.jpeg_entropy_device, coef, max_s)):
+                    room = int(p.desc[2])
+                    scan = torch.from_numpy(p.scan[:room]).cuda().repeat(n)
+                    desc = torch.from_numpy(p.desc).cuda().repeat(n, 1)
+                    desc[:, 0] = torch.arange(n, device="cuda", dtype=torch.int32) * room
+                    tables = torch.from_numpy(p.tables).cuda().repeat(n, 1)
+                    for sb in (128, 256, 512, 1024):
+                        call = lambda: fn(scan, desc, tables, H, W, 3, dc, dq, st, subseq_bits=sb)
+                        call()
+                        torch.cuda.synchronize()
+                        status = st.cpu().numpy()
+                        assert (status[:, 0] == 0).all() and (status[:, 1] == hmax).all(), status
+                        assert all(np.array_equal(dc[i].cpu().numpy(), hcoef) and np.array_equal(dq[i].cpu().numpy(), rqt) for i in (0, n - 1)), "not the host's coefficients"
+                        hot = sorted(event_us(call, 20) for _ in range(5))[2]
+                        cold = []
+                        for _ in range(7):
+                            flush.fill_(1)
+                            cold.append(event_us(call, 1))
+                        cold = sorted(cold)[3]
+                        e[f"{key}_n{n}_bits{sb}"] = {"hot_us_per_frame": round(hot / n, 3), "cold_us_per_frame": round(cold / n, 3), "hot_us_per_call": round(hot, 2),
+                                                     "cold_us_per_call": round(cold, 2), "rounds": int(status[:, 2].max())}
     print(name, json.dumps(r), flush=True)
 if "--json" in sys.argv:
     with open(sys.argv[sys.argv.index("--json") + 1], "w") as f:
