@@ -12,7 +12,7 @@ from pathlib import Path
 CSRC = Path(__file__).resolve().parent / "csrc"
 LIB = CSRC / "libmvldm_hip.so"
 SOURCES = ["api.cpp", "plan.cpp", "igemm.hip", "igemm_small.hip", "igemm_large.hip", "igemm_xl.hip", "igemm_halo.hip", "pack.hip", "attention.hip", "norm.hip", "misc.hip",
-           "wgrad.hip", "attention_bwd.hip", "norm_bwd.hip", "train_misc.hip", "linear_pp.hip", "linear_pw.hip", "linear_ws.hip", "linear_rs.hip", "skinny.hip", "metrics.hip", "lpips.hip", "dists.hip", "fid.hip", "inception.hip", "kid.hip", "cropshim.hip", "jpeg.hip", "jpeg_huff.hip", "jpeg_rst.hip", "jpeg_host.cpp", "png.hip", "png_host.cpp", "inflate.hip", "inflate_host.cpp"]
+           "wgrad.hip", "attention_bwd.hip", "norm_bwd.hip", "train_misc.hip", "linear_pp.hip", "linear_pw.hip", "linear_ws.hip", "linear_rs.hip", "skinny.hip", "metrics.hip", "lpips.hip", "dists.hip", "fid.hip", "inception.hip", "kid.hip", "cropshim.hip", "jpeg.hip", "jpeg_huff.hip", "jpeg_host.cpp", "png.hip", "png_host.cpp", "inflate.hip", "inflate_host.cpp"]
 HEADERS = [*sorted(CSRC.glob("*.h")), CSRC.parent.parent / "include" / "mvldm.h"]   # every object depends on every header
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wno-unused-result",
          "-Rpass-analysis=kernel-resource-usage"]          # per-kernel registers / scratch -> csrc/kernel_resources.json

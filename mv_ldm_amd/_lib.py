@@ -198,6 +198,10 @@ class Op(C.Structure):
     _fields_ = [("kind", i32), ("tag", i32), ("u", _OpUnion)]
 
 
+# the plain and the restart form of the JPEG device entropy path take the same arguments
+_JPEG_PREPARE = (C.c_int, [vp, sz, vp, sz, sz, vp, vp, vp])
+_JPEG_ENTROPY = [vp, sz, vp, vp] + [C.c_int] * 4 + [vp, vp, vp, C.c_int]      # then the stream (device) or the chunk's subsequences (emulation)
+
 # name -> (restype, argtypes); mirrors include/mvldm.h one to one (checked by tests/test_abi.py)
 SIGNATURES = {
     "mvldm_abi_version": (C.c_int, []),
@@ -282,15 +286,15 @@ SIGNATURES = {
     "mvldm_jpeg_decode": (C.c_int, [vp, vp, vp] + [C.c_int] * 4 + [vp, sz, vp]),
     "mvldm_jpeg_idct_host": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int]),
     "mvldm_jpeg_scan_room": (sz, [sz]),
-    "mvldm_jpeg_scan_prepare": (C.c_int, [vp, sz, vp, sz, sz, vp, vp, vp]),
+    "mvldm_jpeg_scan_prepare": _JPEG_PREPARE,
     "mvldm_jpeg_entropy_chunk_subseqs": (C.c_int, []),
-    "mvldm_jpeg_entropy_device": (C.c_int, [vp, sz, vp, vp] + [C.c_int] * 4 + [vp, vp, vp, C.c_int, vp]),
-    "mvldm_jpeg_entropy_emul_host": (C.c_int, [vp, sz, vp, vp] + [C.c_int] * 4 + [vp, vp, vp, C.c_int, C.c_int]),
+    "mvldm_jpeg_entropy_device": (C.c_int, _JPEG_ENTROPY + [vp]),
+    "mvldm_jpeg_entropy_emul_host": (C.c_int, _JPEG_ENTROPY + [C.c_int]),
     "mvldm_jpeg_rst_room": (sz, [sz]),
     "mvldm_jpeg_rst_need": (sz, [vp, sz]),
-    "mvldm_jpeg_rst_prepare": (C.c_int, [vp, sz, vp, sz, sz, vp, vp, vp]),
-    "mvldm_jpeg_rst_entropy_device": (C.c_int, [vp, sz, vp, vp] + [C.c_int] * 4 + [vp, vp, vp, C.c_int, vp]),
-    "mvldm_jpeg_rst_entropy_emul_host": (C.c_int, [vp, sz, vp, vp] + [C.c_int] * 4 + [vp, vp, vp, C.c_int, C.c_int]),
+    "mvldm_jpeg_rst_prepare": _JPEG_PREPARE,
+    "mvldm_jpeg_rst_entropy_device": (C.c_int, _JPEG_ENTROPY + [vp]),
+    "mvldm_jpeg_rst_entropy_emul_host": (C.c_int, _JPEG_ENTROPY + [C.c_int]),
     "mvldm_png_unfilter": (C.c_int, [vp, sz, vp, vp, sz, vp] + [C.c_int] * 4 + [vp, vp]),
     "mvldm_png_unfilter_host": (C.c_int, [vp, sz, vp, vp, sz, vp] + [C.c_int] * 4 + [vp]),
     "mvldm_png_inflate_room": (sz, [sz]),

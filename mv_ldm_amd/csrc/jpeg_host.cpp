@@ -3,6 +3,8 @@
 // number of threads may decode at once.  Every read of the stream goes through an index checked against `len`.
 #include <string.h>
 
+#include <vector>
+
 #include "jpeg_common.h"
 #include "jpeg_huff_common.h"
 
@@ -452,164 +454,29 @@ extern "C" int mvldm_jpeg_idct_host(const int16_t* coef, const uint16_t* qt, uin
     return MVLDM_OK;
 }
 
-// ---- the scan on the device: what the host still does, and the decoder's emulation ---------------------------------------------------
-extern "C" size_t mvldm_jpeg_scan_room(size_t len) { return huff_scan_room(len); }
-
-extern "C" int mvldm_jpeg_scan_prepare(const uint8_t* data, size_t len, uint8_t* scan, size_t scan_off, size_t scan_room, int32_t* desc, uint8_t* tables,
-                                       int32_t* info) {
-    if (data == nullptr || scan == nullptr || desc == nullptr || tables == nullptr) return set_error(MVLDM_ERR_ARG, "jpeg_scan_prepare: null pointer");
-    if ((scan_off & 15) || len >= ((size_t)1 << 28) || scan_room > 0x7FFFFFFFu || scan_room < scan_off || scan_room - scan_off < huff_scan_room(len))
-        return set_error(MVLDM_ERR_ARG, "jpeg_scan_prepare: offset %zu of %zu bytes for a frame of %zu (a multiple of 16, room for %zu, below 2^31)", scan_off,
-                         scan_room, len, huff_scan_room(len));
-    Header hd;
-    const int reason = parse_header(data, len, &hd);
-    if (info) fill_info(hd, reason, info);
-    desc[0] = (int32_t)scan_off;
-    desc[1] = desc[2] = desc[3] = 0;
-    if (reason != MVLDM_JPEG_OK) return reason;
-    JpegLayout L;
-    if (!jpeg_layout(hd.h, hd.w, hd.sampling, &L)) return MVLDM_JPEG_SIZE;
-    if (hd.restart != 0) return MVLDM_JPEG_RESTART;
-    // the entropy-coded bytes up to the first marker, FF 00 -> FF
-    uint8_t* out = scan + scan_off;
-    size_t n = 0, i = hd.scan;
-    while (true) {
-        if (i >= len) return MVLDM_JPEG_TRUNCATED;
-        const uint8_t b = data[i];
-        if (b == 0xFF) {
-            if (i + 1 >= len) return MVLDM_JPEG_TRUNCATED;
-            if (data[i + 1] != 0x00) break;
-            i += 2;
-        } else {
-            ++i;
-        }
-        out[n++] = b;                           // n <= i - hd.scan < len
-    }
-    const int tail = expect_eoi(data, len, i);  // i sits on the marker's FF
-    if (tail != MVLDM_JPEG_OK) return tail;
-    const size_t room = huff_scan_room(n);      // <= huff_scan_room(len)
-    memset(out + n, 0, room - n);
-    desc[1] = (int32_t)(n * 8);
-    desc[2] = (int32_t)room;
-    tables_blob(hd, L, tables);
-    return MVLDM_JPEG_OK;
-}
-
-extern "C" int mvldm_jpeg_entropy_chunk_subseqs(void) { return kHuffChunk; }
-
-extern "C" int mvldm_jpeg_entropy_emul_host(const uint8_t* scan, size_t scan_bytes, const int32_t* desc, const uint8_t* tables, int n_img, int h, int w,
-                                            int sampling, int16_t* coef, uint16_t* qt, int32_t* status, int subseq_bits, int chunk_subseqs) {
-    if (scan == nullptr || desc == nullptr || tables == nullptr || coef == nullptr || qt == nullptr || status == nullptr)
-        return set_error(MVLDM_ERR_ARG, "jpeg_entropy_emul_host: null pointer");
-    JpegLayout L;
-    if (n_img < 0 || !jpeg_layout(h, w, sampling, &L)) return set_error(MVLDM_ERR_ARG, "jpeg_entropy_emul_host: %d frames of %d x %d, sampling %d", n_img, h, w, sampling);
-    if (!huff_bits_ok(subseq_bits) || chunk_subseqs < 0 || chunk_subseqs > (1 << 20))
-        return set_error(MVLDM_ERR_ARG, "jpeg_entropy_emul_host: subseq_bits %d (0, or a multiple of 32 in 32 .. %d), chunk of %d", subseq_bits, kHuffMaxBits, chunk_subseqs);
-    const uint32_t sb = subseq_bits ? (uint32_t)subseq_bits : (uint32_t)kHuffDefaultBits;
-    const uint32_t T = chunk_subseqs ? (uint32_t)chunk_subseqs : (uint32_t)kHuffChunk;
-    const HuffGeom G = huff_geom(L);
-    const size_t count = (size_t)L.blocks * 64;
-    HuffState* buf[2] = {new HuffState[T], new HuffState[T]};      // the exit states: the barrier of a round is the swap of the two
-    HuffState* entry = new HuffState[T];
-    uint32_t* done = new uint32_t[T];
-    uint8_t zigzag[64];
-    for (uint32_t i = 0; i < 64; ++i) zigzag[i] = huff_zigzag(i);
-    for (int img = 0; img < n_img; ++img) {
-        int16_t* cf = coef + (size_t)img * count;
-        uint16_t* q = qt + (size_t)img * 192;
-        const int32_t* d = desc + (size_t)img * 4;
-        const uint8_t* tab = tables + (size_t)img * kHuffBlobBytes;
-        memset(cf, 0, count * sizeof(int16_t));
-        memcpy(q, tab + kHuffTabsBytes, 192 * sizeof(uint16_t));
-        int reason = MVLDM_JPEG_CORRUPT;
-        uint32_t rounds_max = 0;
-        if (huff_desc_ok(d, scan_bytes)) {
-            const uint8_t* sc = scan + d[0];
-            const uint32_t bit_len = (uint32_t)d[1];
-            const uint32_t nsub = (uint32_t)(((uint64_t)bit_len + sb - 1) / sb);
-            HuffState carry = {0u, 0u};
-            uint32_t base = 0, end_p = 0xFFFFFFFFu, bad = 0;
-            for (uint32_t ch0 = 0; ch0 < nsub; ch0 += T) {
-                const uint32_t n_act = nsub - ch0 < T ? nsub - ch0 : T;
-                auto end_of = [&](uint32_t i) {
-                    const uint64_t e = ((uint64_t)(ch0 + i) + 1) * sb;
-                    return e < bit_len ? (uint32_t)e : bit_len;
-                };
-                HuffNoSink none;
-                for (uint32_t i = 0; i < n_act; ++i) {          // cold pass
-                    entry[i] = i == 0 ? carry : HuffState{(ch0 + i) * sb, 0u};
-                    HuffState st = entry[i];
-                    huff_run(sc, bit_len, tab, G.nl, G.nb, end_of(i), sb, &st, &done[i], &none);
-                    buf[0][i] = st;
-                }
-                int cur = 0;
-                uint32_t rounds = 0;
-                for (uint32_t r = 0; r < n_act; ++r) {
-                    bool any = false;
-                    for (uint32_t i = 0; i < n_act; ++i) {
-                        HuffState st = buf[cur][i];
-                        if (i >= 1 && !huff_same(buf[cur][i - 1], entry[i])) {
-                            entry[i] = st = buf[cur][i - 1];
-                            huff_run(sc, bit_len, tab, G.nl, G.nb, end_of(i), sb, &st, &done[i], &none);
-                            any = true;
-                        }
-                        buf[cur ^ 1][i] = st;
-                    }
-                    cur ^= 1;
-                    ++rounds;
-                    if (!any) break;
-                }
-                if (rounds > rounds_max) rounds_max = rounds;
-                for (uint32_t i = 0; i < n_act; ++i) {          // write pass
-                    HuffCoefSink sink{cf, zigzag, G, base, &end_p, &bad, nullptr};
-                    sink.open();
-                    HuffState st = entry[i];
-                    uint32_t nb = 0;
-                    huff_run(sc, bit_len, tab, G.nl, G.nb, end_of(i), sb, &st, &nb, &sink);
-                    base += nb;
-                }
-                carry = buf[cur][n_act - 1];
-            }
-            if (!bad && end_p != 0xFFFFFFFFu && bit_len - end_p < 8u) reason = MVLDM_JPEG_OK;
-        }
-        int32_t worst = 0;
-        if (reason == MVLDM_JPEG_OK) {          // the second launch: DC prefixes in scan order, S of every block
-            bool bad = false;
-            for (uint32_t c = 0; c < G.ncomp; ++c) {
-                const uint32_t nc = c == 0 ? G.mcus * G.nl : G.mcus;
-                int64_t pred = 0;
-                for (uint32_t j = 0; j < nc; ++j) {
-                    const uint32_t m = c == 0 ? j / G.nl : j, b = c == 0 ? j - m * G.nl : G.nl + c - 1;
-                    int16_t* blk = cf + (size_t)huff_block_index(G, m, b) * 64;
-                    pred += blk[0];
-                    if (pred < -32768 || pred > 32767) {
-                        bad = true;
-                        continue;
-                    }
-                    blk[0] = (int16_t)pred;
-                    int32_t sum = 0;
-                    for (int k = 0; k < 64; ++k) sum += (blk[k] < 0 ? -(int32_t)blk[k] : (int32_t)blk[k]) * (int32_t)q[c * 64 + k];
-                    if (sum > worst) worst = sum;
-                }
-            }
-            reason = bad ? MVLDM_JPEG_CORRUPT : worst > kJpegGuard ? MVLDM_JPEG_RANGE : MVLDM_JPEG_OK;
-            if (bad) worst = 0;
-        }
-        status[img * 4 + 0] = reason;
-        status[img * 4 + 1] = worst;
-        status[img * 4 + 2] = (int32_t)rounds_max;
-        status[img * 4 + 3] = 0;
-    }
-    delete[] buf[0];
-    delete[] buf[1];
-    delete[] entry;
-    delete[] done;
-    return MVLDM_OK;
-}
-
-// ---- restart intervals on the device: prepare and the emulation of jpeg_rst.hip -----------------------------------------------------
+// ---- the scan on the device: what the host still does, and the emulations of jpeg_huff.hip's two forms ----------------------------------
 namespace mvldm {
 namespace {
+
+// The front of the two prepares: the argument checks (at least min_room bytes behind the offset), the header into *hd and `info`, the
+// descriptor reset and the layout.  false: *rc is the prepare's answer.
+bool prepare_front(const char* name, const uint8_t* data, size_t len, uint8_t* scan, size_t scan_off, size_t scan_room, size_t min_room, int32_t* desc,
+                   uint8_t* tables, int32_t* info, Header* hd, JpegLayout* L, int* rc) {
+    *rc = MVLDM_JPEG_OK;
+    if (data == nullptr || scan == nullptr || desc == nullptr || tables == nullptr) {
+        *rc = set_error(MVLDM_ERR_ARG, "%s: null pointer", name);
+    } else if ((scan_off & 15) || len >= ((size_t)1 << 28) || scan_room > 0x7FFFFFFFu || scan_room < scan_off || scan_room - scan_off < min_room) {
+        *rc = set_error(MVLDM_ERR_ARG, "%s: offset %zu of %zu bytes for a frame of %zu (a multiple of 16, %zu bytes or more behind it, below 2^31)", name, scan_off,
+                        scan_room, len, min_room);
+    } else {
+        *rc = parse_header(data, len, hd);
+        if (info) fill_info(*hd, *rc, info);
+        desc[0] = (int32_t)scan_off;
+        desc[1] = desc[2] = desc[3] = 0;
+        if (*rc == MVLDM_JPEG_OK && !jpeg_layout(hd->h, hd->w, hd->sampling, L)) *rc = MVLDM_JPEG_SIZE;
+    }
+    return *rc == MVLDM_JPEG_OK;
+}
 
 // intervals of the frame, MCUs to an interval (a frame without DRI, or with one at or above its MCUs, is one interval), and the bytes
 // its region can occupy: at most huff_rst_room(len)
@@ -628,17 +495,41 @@ int rst_refusal(const uint8_t* data, size_t len, const Header& hd, const JpegLay
     return reason == MVLDM_JPEG_OK || reason == MVLDM_JPEG_RANGE ? MVLDM_JPEG_CORRUPT : reason;
 }
 
-struct RstEmul {                // what the kernel keeps in LDS and in its threads' registers, one entry per thread of a chunk
-    HuffState* buf[2];
-    HuffState* entry;
-    uint32_t *done, *ex, *pre;
-    HuffRstLane* lane;
+struct HuffEmul {               // what a kernel keeps in LDS and in its threads' registers, one entry per thread of a chunk
+    std::vector<HuffState> buf[2], entry;       // the exit states twice: the barrier of a round is the swap of the two
+    std::vector<uint32_t> done, ex, pre;
+    std::vector<HuffRstLane> lane;
+    uint32_t sb, T;             // bits of a subsequence, subsequences of a chunk
+    HuffGeom G;
+    size_t count;               // coefficients of a frame
+    uint8_t zigzag[64];
 };
+
+// The emulations' argument checks and buffers.
+int emul_open(const char* name, const void* scan, const void* desc, const void* tables, int n_img, int h, int w, int sampling, const void* coef, const void* qt,
+              const void* status, int subseq_bits, int chunk_subseqs, HuffEmul* E) {
+    if (scan == nullptr || desc == nullptr || tables == nullptr || coef == nullptr || qt == nullptr || status == nullptr)
+        return set_error(MVLDM_ERR_ARG, "%s: null pointer", name);
+    JpegLayout L;
+    if (n_img < 0 || !jpeg_layout(h, w, sampling, &L)) return set_error(MVLDM_ERR_ARG, "%s: %d frames of %d x %d, sampling %d", name, n_img, h, w, sampling);
+    if (!huff_bits_ok(subseq_bits) || chunk_subseqs < 0 || chunk_subseqs > (1 << 20))
+        return set_error(MVLDM_ERR_ARG, "%s: subseq_bits %d (0, or a multiple of 32 in 32 .. %d), chunk of %d", name, subseq_bits, kHuffMaxBits, chunk_subseqs);
+    E->sb = subseq_bits ? (uint32_t)subseq_bits : (uint32_t)kHuffDefaultBits;
+    E->T = chunk_subseqs ? (uint32_t)chunk_subseqs : (uint32_t)kHuffChunk;
+    E->G = huff_geom(L);
+    E->count = (size_t)L.blocks * 64;
+    for (auto* v : {&E->buf[0], &E->buf[1], &E->entry}) v->resize(E->T);
+    for (auto* v : {&E->done, &E->ex, &E->pre}) v->resize(E->T);
+    E->lane.resize(E->T);
+    for (uint32_t i = 0; i < 64; ++i) E->zigzag[i] = huff_zigzag(i);
+    return MVLDM_OK;
+}
 
 // One chunk of n_act subsequences described by E.lane: cold pass, rounds, segmented scan of the completed blocks, write pass.
 // Returns the blocks the chunk completed; *carry is the last thread's exit.
-uint32_t rst_chunk(const RstEmul& E, uint32_t n_act, uint32_t sb, const uint8_t* tab, const HuffGeom& G, int16_t* cf, const uint8_t* zigzag, uint32_t* bad,
-                   uint32_t* ended, HuffState* carry, uint32_t* rounds_max) {
+uint32_t huff_chunk(HuffEmul& E, uint32_t n_act, const uint8_t* tab, int16_t* cf, uint32_t* bad, uint32_t* ended, HuffState* carry, uint32_t* rounds_max) {
+    const HuffGeom& G = E.G;
+    const uint32_t sb = E.sb;
     HuffNoSink none;
     for (uint32_t i = 0; i < n_act; ++i) {              // cold pass
         const HuffRstLane& ln = E.lane[i];
@@ -672,7 +563,7 @@ uint32_t rst_chunk(const RstEmul& E, uint32_t n_act, uint32_t sb, const uint8_t*
     }
     for (uint32_t i = 0; i < n_act; ++i) {              // write pass
         const HuffRstLane& ln = E.lane[i];
-        HuffRstSink sink{cf, zigzag, G, ln.base + E.ex[i] - E.ex[ln.start], ln.limit, ln.bits, 0u, bad, nullptr};
+        HuffCoefSink sink{cf, E.zigzag, G, ln.base + E.ex[i] - E.ex[ln.start], ln.limit, ln.bits, 0u, bad, nullptr};
         sink.open();
         HuffState st = E.entry[i];
         uint32_t again = 0;
@@ -683,6 +574,63 @@ uint32_t rst_chunk(const RstEmul& E, uint32_t n_act, uint32_t sb, const uint8_t*
     return blocks;
 }
 
+// One stream (a frame without intervals, or an interval of more than a chunk) of `bits` bits whose blocks are base .. limit: its
+// chunks in order, the first lane of each entering with the carry of the chunk before.
+void huff_stream(HuffEmul& E, const uint8_t* sc, uint32_t bits, uint32_t base, uint32_t limit, const uint8_t* tab, int16_t* cf, uint32_t* bad, uint32_t* ended,
+                 uint32_t* rounds_max) {
+    const uint32_t cnt = huff_rst_count(bits, E.sb);
+    HuffState carry = {0u, 0u};
+    for (uint32_t ch0 = 0; ch0 < cnt; ch0 += E.T) {
+        const uint32_t n_act = cnt - ch0 < E.T ? cnt - ch0 : E.T;
+        for (uint32_t i = 0; i < n_act; ++i) E.lane[i] = HuffRstLane{sc, bits, ch0 + i, 0u, base, limit, carry, i == 0};
+        base += huff_chunk(E, n_act, tab, cf, bad, ended, &carry, rounds_max);
+    }
+}
+
+// A frame's slot and tables before its scan is decoded.
+const uint8_t* emul_frame(const HuffEmul& E, int img, const uint8_t* tables, int16_t* coef, uint16_t* qt, int16_t** cf) {
+    const uint8_t* tab = tables + (size_t)img * kHuffBlobBytes;
+    *cf = coef + (size_t)img * E.count;
+    memset(*cf, 0, E.count * sizeof(int16_t));
+    memcpy(qt + (size_t)img * 192, tab + kHuffTabsBytes, 192 * sizeof(uint16_t));
+    return tab;
+}
+
+// The second launch and the status words of a frame whose scan gave `reason`: DC prefixes per interval of ri MCUs in scan order (a
+// frame without intervals: ri = its MCUs), S of every block.
+void emul_finish(const HuffGeom& G, uint32_t ri, int16_t* cf, const uint16_t* q, int reason, uint32_t rounds_max, uint32_t n_int, int32_t* status) {
+    int32_t worst = 0;
+    if (reason == MVLDM_JPEG_OK) {
+        bool bad = false;
+        for (uint32_t c = 0; c < G.ncomp; ++c) {
+            const uint32_t per = c == 0 ? G.nl : 1u, nc = G.mcus * per, period = ri * per;
+            long long pred = 0;
+            for (uint32_t j = 0; j < nc; ++j) {
+                const uint32_t m = c == 0 ? j / G.nl : j, b = c == 0 ? j - m * G.nl : G.nl + c - 1;
+                int16_t* blk = cf + (size_t)huff_block_index(G, m, b) * 64;
+                bool f = j % period == 0;
+                long long v = blk[0];
+                huff_rst_join(false, pred, &f, &v);
+                pred = v;
+                if (pred < -32768 || pred > 32767) {
+                    bad = true;
+                    continue;
+                }
+                blk[0] = (int16_t)pred;
+                int32_t sum = 0;
+                for (int k = 0; k < 64; ++k) sum += (blk[k] < 0 ? -(int32_t)blk[k] : (int32_t)blk[k]) * (int32_t)q[c * 64 + k];
+                if (sum > worst) worst = sum;
+            }
+        }
+        reason = bad ? MVLDM_JPEG_CORRUPT : worst > kJpegGuard ? MVLDM_JPEG_RANGE : MVLDM_JPEG_OK;
+        if (bad) worst = 0;
+    }
+    status[0] = reason;
+    status[1] = worst;
+    status[2] = (int32_t)rounds_max;
+    status[3] = (int32_t)n_int;
+}
+
 inline int32_t rst_word(const uint8_t* region, size_t i) {          // the host's packed buffer need not be aligned
     int32_t v;
     memcpy(&v, region + 4 * i, 4);
@@ -691,6 +639,58 @@ inline int32_t rst_word(const uint8_t* region, size_t i) {          // the host'
 
 }  // namespace
 }  // namespace mvldm
+
+extern "C" size_t mvldm_jpeg_scan_room(size_t len) { return huff_scan_room(len); }
+
+extern "C" int mvldm_jpeg_scan_prepare(const uint8_t* data, size_t len, uint8_t* scan, size_t scan_off, size_t scan_room, int32_t* desc, uint8_t* tables,
+                                       int32_t* info) {
+    Header hd;
+    JpegLayout L;
+    int rc;
+    if (!prepare_front("jpeg_scan_prepare", data, len, scan, scan_off, scan_room, huff_scan_room(len), desc, tables, info, &hd, &L, &rc)) return rc;
+    if (hd.restart != 0) return MVLDM_JPEG_RESTART;
+    // the entropy-coded bytes up to the first marker, FF 00 -> FF
+    uint8_t* out = scan + scan_off;
+    size_t n = 0, i = hd.scan;
+    while (true) {
+        if (i >= len) return MVLDM_JPEG_TRUNCATED;
+        const uint8_t b = data[i];
+        if (b == 0xFF) {
+            if (i + 1 >= len) return MVLDM_JPEG_TRUNCATED;
+            if (data[i + 1] != 0x00) break;
+            i += 2;
+        } else {
+            ++i;
+        }
+        out[n++] = b;                           // n <= i - hd.scan < len
+    }
+    const int tail = expect_eoi(data, len, i);  // i sits on the marker's FF
+    if (tail != MVLDM_JPEG_OK) return tail;
+    const size_t room = huff_scan_room(n);      // <= huff_scan_room(len)
+    memset(out + n, 0, room - n);
+    desc[1] = (int32_t)(n * 8);
+    desc[2] = (int32_t)room;
+    tables_blob(hd, L, tables);
+    return MVLDM_JPEG_OK;
+}
+
+extern "C" int mvldm_jpeg_entropy_chunk_subseqs(void) { return kHuffChunk; }
+
+extern "C" int mvldm_jpeg_entropy_emul_host(const uint8_t* scan, size_t scan_bytes, const int32_t* desc, const uint8_t* tables, int n_img, int h, int w,
+                                            int sampling, int16_t* coef, uint16_t* qt, int32_t* status, int subseq_bits, int chunk_subseqs) {
+    HuffEmul E;
+    const int rc = emul_open("jpeg_entropy_emul_host", scan, desc, tables, n_img, h, w, sampling, coef, qt, status, subseq_bits, chunk_subseqs, &E);
+    if (rc != MVLDM_OK) return rc;
+    for (int img = 0; img < n_img; ++img) {
+        int16_t* cf;
+        const uint8_t* tab = emul_frame(E, img, tables, coef, qt, &cf);
+        const int32_t* d = desc + (size_t)img * 4;
+        uint32_t rounds_max = 0, bad = 0, ended = 0;
+        if (huff_desc_ok(d, scan_bytes)) huff_stream(E, scan + d[0], (uint32_t)d[1], 0u, E.G.total, tab, cf, &bad, &ended, &rounds_max);      // the frame: one interval
+        emul_finish(E.G, E.G.mcus, cf, qt + (size_t)img * 192, !bad && ended == 1u ? MVLDM_JPEG_OK : MVLDM_JPEG_CORRUPT, rounds_max, 0u, status + (size_t)img * 4);
+    }
+    return MVLDM_OK;
+}
 
 extern "C" size_t mvldm_jpeg_rst_room(size_t len) { return huff_rst_room(len); }
 
@@ -706,18 +706,10 @@ extern "C" size_t mvldm_jpeg_rst_need(const uint8_t* data, size_t len) {
 
 extern "C" int mvldm_jpeg_rst_prepare(const uint8_t* data, size_t len, uint8_t* scan, size_t scan_off, size_t scan_room, int32_t* desc, uint8_t* tables,
                                       int32_t* info) {
-    if (data == nullptr || scan == nullptr || desc == nullptr || tables == nullptr) return set_error(MVLDM_ERR_ARG, "jpeg_rst_prepare: null pointer");
-    if ((scan_off & 15) || len >= ((size_t)1 << 28) || scan_room > 0x7FFFFFFFu || scan_room < scan_off)
-        return set_error(MVLDM_ERR_ARG, "jpeg_rst_prepare: offset %zu of %zu bytes for a frame of %zu (a multiple of 16, inside the buffer, below 2^31)", scan_off,
-                         scan_room, len);
     Header hd;
-    const int reason = parse_header(data, len, &hd);
-    if (info) fill_info(hd, reason, info);
-    desc[0] = (int32_t)scan_off;
-    desc[1] = desc[2] = desc[3] = 0;
-    if (reason != MVLDM_JPEG_OK) return reason;
     JpegLayout L;
-    if (!jpeg_layout(hd.h, hd.w, hd.sampling, &L)) return MVLDM_JPEG_SIZE;
+    int rc;
+    if (!prepare_front("jpeg_rst_prepare", data, len, scan, scan_off, scan_room, 0, desc, tables, info, &hd, &L, &rc)) return rc;
     uint32_t n_int, ri;
     size_t T;
     const size_t need = rst_plan(hd, L, len, &n_int, &ri, &T);
@@ -775,31 +767,19 @@ extern "C" int mvldm_jpeg_rst_prepare(const uint8_t* data, size_t len, uint8_t* 
 
 extern "C" int mvldm_jpeg_rst_entropy_emul_host(const uint8_t* scan, size_t scan_bytes, const int32_t* desc, const uint8_t* tables, int n_img, int h, int w,
                                                 int sampling, int16_t* coef, uint16_t* qt, int32_t* status, int subseq_bits, int chunk_subseqs) {
-    if (scan == nullptr || desc == nullptr || tables == nullptr || coef == nullptr || qt == nullptr || status == nullptr)
-        return set_error(MVLDM_ERR_ARG, "jpeg_rst_entropy_emul_host: null pointer");
-    JpegLayout L;
-    if (n_img < 0 || !jpeg_layout(h, w, sampling, &L)) return set_error(MVLDM_ERR_ARG, "jpeg_rst_entropy_emul_host: %d frames of %d x %d, sampling %d", n_img, h, w, sampling);
-    if (!huff_bits_ok(subseq_bits) || chunk_subseqs < 0 || chunk_subseqs > (1 << 20))
-        return set_error(MVLDM_ERR_ARG, "jpeg_rst_entropy_emul_host: subseq_bits %d (0, or a multiple of 32 in 32 .. %d), chunk of %d", subseq_bits, kHuffMaxBits, chunk_subseqs);
-    const uint32_t sb = subseq_bits ? (uint32_t)subseq_bits : (uint32_t)kHuffDefaultBits;
-    const uint32_t T = chunk_subseqs ? (uint32_t)chunk_subseqs : (uint32_t)kHuffChunk;
-    const HuffGeom G = huff_geom(L);
-    const size_t count = (size_t)L.blocks * 64;
-    RstEmul E{{new HuffState[T], new HuffState[T]}, new HuffState[T], new uint32_t[T], new uint32_t[T], new uint32_t[T], new HuffRstLane[T]};
-    uint8_t zigzag[64];
-    for (uint32_t i = 0; i < 64; ++i) zigzag[i] = huff_zigzag(i);
+    HuffEmul E;
+    const int rc = emul_open("jpeg_rst_entropy_emul_host", scan, desc, tables, n_img, h, w, sampling, coef, qt, status, subseq_bits, chunk_subseqs, &E);
+    if (rc != MVLDM_OK) return rc;
+    const HuffGeom& G = E.G;
+    const uint32_t sb = E.sb, T = E.T;
     for (int img = 0; img < n_img; ++img) {
-        int16_t* cf = coef + (size_t)img * count;
-        uint16_t* q = qt + (size_t)img * 192;
+        int16_t* cf;
+        const uint8_t* tab = emul_frame(E, img, tables, coef, qt, &cf);
         const int32_t* d = desc + (size_t)img * 4;
-        const uint8_t* tab = tables + (size_t)img * kHuffBlobBytes;
-        memset(cf, 0, count * sizeof(int16_t));
-        memcpy(q, tab + kHuffTabsBytes, 192 * sizeof(uint16_t));
         int reason = MVLDM_JPEG_CORRUPT;
         uint32_t rounds_max = 0, n_int = 0, ri = 1;
-        const bool ok = huff_rst_desc_ok(d, scan_bytes, G.mcus);
-        const uint8_t* region = scan + (ok ? (size_t)d[0] : 0);
-        if (ok) {
+        if (huff_rst_desc_ok(d, scan_bytes, G.mcus)) {
+            const uint8_t* region = scan + d[0];
             n_int = (uint32_t)d[1];
             ri = (uint32_t)d[3];
             bool wrong = false;                         // the whole table against the descriptor before any scan bit is read
@@ -814,70 +794,29 @@ extern "C" int mvldm_jpeg_rst_entropy_emul_host(const uint8_t* scan, size_t scan
                     if (sum > T) break;                 // the sums only grow: the batch ends here
                     nbi = j + 1;
                 }
-                HuffState carry = {0u, 0u};
-                if (nbi == 0) {                         // an interval of more than a chunk: its chunks in order, with the carry
-                    const uint8_t* sc = region + rst_word(region, 2 * (size_t)g0);
-                    const uint32_t bits = (uint32_t)rst_word(region, 2 * (size_t)g0 + 1), cnt = huff_rst_count(bits, sb);
+                if (nbi == 0) {                         // an interval of more than a chunk: walked alone
                     uint32_t base, limit;
                     huff_rst_blocks(G, g0, ri, &base, &limit);
-                    for (uint32_t ch0 = 0; ch0 < cnt; ch0 += T) {
-                        const uint32_t n_act = cnt - ch0 < T ? cnt - ch0 : T;
-                        for (uint32_t i = 0; i < n_act; ++i) E.lane[i] = HuffRstLane{sc, bits, ch0 + i, 0u, base, limit, carry, i == 0};
-                        base += rst_chunk(E, n_act, sb, tab, G, cf, zigzag, &bad, &ended, &carry, &rounds_max);
-                    }
+                    huff_stream(E, region + rst_word(region, 2 * (size_t)g0), (uint32_t)rst_word(region, 2 * (size_t)g0 + 1), base, limit, tab, cf, &bad, &ended,
+                                &rounds_max);
                     g0 += 1;
                 } else {
                     const uint32_t n_act = E.pre[nbi - 1];
                     for (uint32_t i = 0; i < n_act; ++i) {
-                        const uint32_t j = huff_rst_find(E.pre, nbi, i), start = j ? E.pre[j - 1] : 0u;
+                        const uint32_t j = huff_rst_find(E.pre.data(), nbi, i), start = j ? E.pre[j - 1] : 0u;
                         uint32_t base, limit;
                         huff_rst_blocks(G, g0 + j, ri, &base, &limit);
                         E.lane[i] = HuffRstLane{region + rst_word(region, 2 * (size_t)(g0 + j)), (uint32_t)rst_word(region, 2 * (size_t)(g0 + j) + 1), i - start, start, base,
                                                 limit, HuffState{0u, 0u}, i == start};
                     }
-                    rst_chunk(E, n_act, sb, tab, G, cf, zigzag, &bad, &ended, &carry, &rounds_max);
+                    HuffState carry;
+                    huff_chunk(E, n_act, tab, cf, &bad, &ended, &carry, &rounds_max);
                     g0 += nbi;
                 }
             }
             if (!wrong && !bad && ended == n_int) reason = MVLDM_JPEG_OK;
         }
-        int32_t worst = 0;
-        if (reason == MVLDM_JPEG_OK) {          // the second launch: DC prefixes per interval in scan order, S of every block
-            bool bad = false;
-            for (uint32_t c = 0; c < G.ncomp; ++c) {
-                const uint32_t per = c == 0 ? G.nl : 1u, nc = G.mcus * per, period = ri * per;
-                long long pred = 0;
-                for (uint32_t j = 0; j < nc; ++j) {
-                    const uint32_t m = c == 0 ? j / G.nl : j, b = c == 0 ? j - m * G.nl : G.nl + c - 1;
-                    int16_t* blk = cf + (size_t)huff_block_index(G, m, b) * 64;
-                    bool f = j % period == 0;
-                    long long v = blk[0];
-                    huff_rst_join(false, pred, &f, &v);
-                    pred = v;
-                    if (pred < -32768 || pred > 32767) {
-                        bad = true;
-                        continue;
-                    }
-                    blk[0] = (int16_t)pred;
-                    int32_t sum = 0;
-                    for (int k = 0; k < 64; ++k) sum += (blk[k] < 0 ? -(int32_t)blk[k] : (int32_t)blk[k]) * (int32_t)q[c * 64 + k];
-                    if (sum > worst) worst = sum;
-                }
-            }
-            reason = bad ? MVLDM_JPEG_CORRUPT : worst > kJpegGuard ? MVLDM_JPEG_RANGE : MVLDM_JPEG_OK;
-            if (bad) worst = 0;
-        }
-        status[img * 4 + 0] = reason;
-        status[img * 4 + 1] = worst;
-        status[img * 4 + 2] = (int32_t)rounds_max;
-        status[img * 4 + 3] = (int32_t)n_int;
+        emul_finish(G, ri, cf, qt + (size_t)img * 192, reason, rounds_max, n_int, status + (size_t)img * 4);
     }
-    delete[] E.buf[0];
-    delete[] E.buf[1];
-    delete[] E.entry;
-    delete[] E.done;
-    delete[] E.ex;
-    delete[] E.pre;
-    delete[] E.lane;
     return MVLDM_OK;
 }

@@ -1,6 +1,7 @@
-// What the device entropy decoder (jpeg_huff.hip) and its host emulation (jpeg_host.cpp, mvldm_jpeg_entropy_emul_host) share: the bit
-// window, the one-symbol step of the decoder state (p, b, k), the address of a block and the store of a coefficient -- written once, so
-// that the kernels and the emulation run the same statements (include/mvldm.h, "JPEG frames: the scan on the device").
+// What the device entropy decoders (jpeg_huff.hip: the plain and the restart form) and their host emulations (jpeg_host.cpp,
+// mvldm_jpeg_entropy_emul_host and mvldm_jpeg_rst_entropy_emul_host) share: the bit window, the one-symbol step of the decoder state
+// (p, b, k), the address of a block, the store of a coefficient and a lane's description of its subsequence -- written once, so that the
+// kernels and the emulations run the same statements (include/mvldm.h, "JPEG frames: the scan on the device").
 // No HIP call and no other header of the library.
 #pragma once
 #include "jpeg_common.h"
@@ -131,22 +132,27 @@ struct HuffNoSink {
     MVLDM_HD void done(uint32_t) {}
     MVLDM_HD void fault() {}
 };
-// The write pass's sink: n is the absolute index (scan order) of the block being decoded.  Every store is guarded by n < total; the bit
-// position at which block total - 1 completes goes to *end_p (decode_scan stops there and wants fewer than 8 bits to remain), and a
-// fault in front of that point sets *bad: the write pass decodes from true entries, so its first fault is the stream's.
+// The write pass's sink, of the plain and of the restart form: n is the absolute index (scan order) of the block being decoded, limit the
+// end of the blocks this lane's stream may fill -- the frame's (G.total) on the plain path, the interval's on the restart path -- and bits
+// the length of that stream.  Every store is guarded by n < limit <= blocks of the frame, so the padding bits of one interval never write
+// into the next.  `ended`: block limit - 1 completed in this subsequence; decode_scan stops there and wants fewer than 8 bits of the
+// stream to remain (in front of a marker and at the end), so 8 or more set *bad.  A fault in front of that point sets *bad too: the write
+// pass decodes from true entries, so its first fault is the stream's.  A stream is accepted when *bad == 0 and exactly one of its lanes
+// reports `ended`.  For the plain path this is the test it had with a shared end position end_p (written where n reached G.total):
+// end_p != sentinel && bit_len - end_p < 8 && !bad.  n reaches limit in at most one lane, because the lanes' n continue each other, so
+// "one lane ended" is "end_p was written", and bit_len - end_p >= 8 is the case that now sets *bad.
 struct HuffCoefSink {
     int16_t* coef;              // the frame's slot
     const uint8_t* zigzag;
     HuffGeom G;
-    uint32_t n;
-    uint32_t* end_p;
+    uint32_t n, limit, bits, ended;
     uint32_t* bad;
     int16_t* blk;
     MVLDM_HD void fault() {
         if (blk != nullptr) *bad = 1u;
     }
     MVLDM_HD void open() {
-        if (n < G.total) {
+        if (n < limit) {
             const uint32_t m = n / G.nb;
             blk = coef + (size_t)huff_block_index(G, m, n - m * G.nb) * 64;
         } else {
@@ -158,7 +164,10 @@ struct HuffCoefSink {
     }
     MVLDM_HD void done(uint32_t p) {
         ++n;
-        if (n == G.total) *end_p = p;
+        if (n == limit) {
+            ended = 1u;
+            if (bits - p >= 8u) *bad = 1u;
+        }
         open();
     }
 };
@@ -252,7 +261,7 @@ MVLDM_HD void huff_run(const uint8_t* scan, uint32_t bit_len, const uint8_t* tab
     *blocks = nblk;
 }
 
-// ---- restart intervals (jpeg_rst.hip, mvldm_jpeg_rst_entropy_emul_host) ---------------------------------------------------------------
+// ---- restart intervals (jpeg_huff.hip jpeg_rst_*_kernel, mvldm_jpeg_rst_entropy_emul_host) -------------------------------------------
 // A frame's region of the packed buffer: the interval table -- int32 pairs (byte offset inside the region, exact bit length), n of them,
 // rounded up to 16 bytes -- then the destuffed intervals, each at a 4-byte aligned offset (huff_word reads aligned dwords relative to the
 // interval's first byte), and zeros up to huff_scan_room behind the last.  A bit position is relative to its interval, bit_len is the
@@ -316,40 +325,6 @@ MVLDM_HD void huff_rst_blocks(const HuffGeom& G, uint32_t g, uint32_t ri, uint32
     *base = b < G.total ? (uint32_t)b : G.total;
     *limit = e < G.total ? (uint32_t)e : G.total;
 }
-
-// The write pass's sink of the restart form: HuffCoefSink with the interval's end for the frame's.  Every store is guarded by n < limit
-// <= blocks of the frame, so the padding bits of one interval never write into the next.  `ended`: the interval's last block completed
-// in this subsequence; it has to leave fewer than 8 bits of the interval (decode_scan's test in front of a marker and at the end).
-struct HuffRstSink {
-    int16_t* coef;
-    const uint8_t* zigzag;
-    HuffGeom G;
-    uint32_t n, limit, bits, ended;
-    uint32_t* bad;
-    int16_t* blk;
-    MVLDM_HD void fault() {
-        if (blk != nullptr) *bad = 1u;
-    }
-    MVLDM_HD void open() {
-        if (n < limit) {
-            const uint32_t m = n / G.nb;
-            blk = coef + (size_t)huff_block_index(G, m, n - m * G.nb) * 64;
-        } else {
-            blk = nullptr;
-        }
-    }
-    MVLDM_HD void put(uint32_t k, int v) {
-        if (blk != nullptr) blk[zigzag[k & 63]] = (int16_t)v;
-    }
-    MVLDM_HD void done(uint32_t p) {
-        ++n;
-        if (n == limit) {
-            ended = 1u;
-            if (bits - p >= 8u) *bad = 1u;
-        }
-        open();
-    }
-};
 
 // The DC differences of a component in scan order become predictions by a SEGMENTED sum: a block that opens a restart interval (head)
 // starts from 0.  (f, v) is the pair of the scan: f says a head lies in the range summed so far.  later after earlier:

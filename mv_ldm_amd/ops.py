@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
+import functools
 import os
 import struct
 import zlib
@@ -1173,14 +1174,10 @@ def jpeg_entropy_chunk_subseqs() -> int:
     return int(L.load().mvldm_jpeg_entropy_chunk_subseqs())
 
 
-def jpeg_scan_prepare(blob: bytes, scan: Optional[np.ndarray] = None, scan_off: int = 0, desc: Optional[np.ndarray] = None,
-                      tables: Optional[np.ndarray] = None) -> JpegScan:
-    """what the host still does for the device entropy decoder (`mvldm_jpeg_scan_prepare`): the markers, the destuffed scan into
-    `scan[scan_off:]` (uint8, room for `jpeg_scan_room(len(blob))` bytes behind the offset, a multiple of 16), the descriptor into `desc`
-    (int32 `[4]`) and the Huffman and quantisation tables into `tables` (uint8 `[_lib.JPEG_TABLE_BYTES]`).  Buffers left out are made.
-    Releases the GIL; keeps no state."""
+def _jpeg_prepare(c_name, room, blob, scan, scan_off, desc, tables) -> JpegScan:
+    """the two prepares: `room()` bytes behind the offset when `scan` is left out, then the C function `c_name`"""
     if scan is None:
-        scan = np.zeros(scan_off + jpeg_scan_room(len(blob)), dtype=np.uint8)
+        scan = np.zeros(scan_off + room(), dtype=np.uint8)
     if desc is None:
         desc = np.zeros(4, dtype=np.int32)
     if tables is None:
@@ -1189,16 +1186,23 @@ def jpeg_scan_prepare(blob: bytes, scan: Optional[np.ndarray] = None, scan_off: 
     assert desc.dtype == np.int32 and desc.flags.c_contiguous and desc.size == 4
     assert tables.dtype == np.uint8 and tables.flags.c_contiguous and tables.size == L.JPEG_TABLE_BYTES
     info = (C.c_int32 * 8)()
-    rc = L.load().mvldm_jpeg_scan_prepare(blob, len(blob), scan.ctypes.data, scan_off, scan.size, desc.ctypes.data, tables.ctypes.data, info)
+    rc = getattr(L.load(), c_name)(blob, len(blob), scan.ctypes.data, scan_off, scan.size, desc.ctypes.data, tables.ctypes.data, info)
     if rc < 0:
         L.check(rc)
     return JpegScan(rc, JpegInfo(*info), scan, desc, tables)
 
 
-def jpeg_entropy_emul(scan: np.ndarray, desc: np.ndarray, tables: np.ndarray, h: int, w: int, sampling: int, coef: Optional[np.ndarray] = None,
-                      qt: Optional[np.ndarray] = None, status: Optional[np.ndarray] = None, subseq_bits: int = 0, chunk_subseqs: int = 0):
-    """the device entropy decoder on the host (`mvldm_jpeg_entropy_emul_host`: the same step function, loops for threads) over the
-    frames of `desc` int32 `[n, 4]` -> (coef int16 `[n, jpeg_coef_count]`, qt uint16 `[n, 192]`, status int32 `[n, 4]`): tests and tools"""
+def jpeg_scan_prepare(blob: bytes, scan: Optional[np.ndarray] = None, scan_off: int = 0, desc: Optional[np.ndarray] = None,
+                      tables: Optional[np.ndarray] = None) -> JpegScan:
+    """what the host still does for the device entropy decoder (`mvldm_jpeg_scan_prepare`): the markers, the destuffed scan into
+    `scan[scan_off:]` (uint8, room for `jpeg_scan_room(len(blob))` bytes behind the offset, a multiple of 16), the descriptor into `desc`
+    (int32 `[4]`) and the Huffman and quantisation tables into `tables` (uint8 `[_lib.JPEG_TABLE_BYTES]`).  Buffers left out are made.
+    Releases the GIL; keeps no state."""
+    return _jpeg_prepare("mvldm_jpeg_scan_prepare", lambda: jpeg_scan_room(len(blob)), blob, scan, scan_off, desc, tables)
+
+
+def _jpeg_entropy_emul(c_name, scan, desc, tables, h, w, sampling, coef, qt, status, subseq_bits, chunk_subseqs):
+    """the two emulations: the C function `c_name` over the frames of `desc`; outputs left out are made"""
     desc, tables = desc.reshape(-1, 4), tables.reshape(-1, L.JPEG_TABLE_BYTES)
     n, count = desc.shape[0], jpeg_coef_count(h, w, sampling)
     assert scan.dtype == np.uint8 and scan.flags.c_contiguous and desc.dtype == np.int32 and desc.flags.c_contiguous
@@ -1208,17 +1212,20 @@ def jpeg_entropy_emul(scan: np.ndarray, desc: np.ndarray, tables: np.ndarray, h:
     status = np.empty((n, 4), dtype=np.int32) if status is None else status
     assert coef.dtype == np.int16 and coef.flags.c_contiguous and coef.size == n * count and qt.dtype.itemsize == 2 and qt.flags.c_contiguous and qt.size == n * 192
     assert status.dtype == np.int32 and status.flags.c_contiguous and status.size == n * 4
-    L.check(L.load().mvldm_jpeg_entropy_emul_host(scan.ctypes.data, scan.size, desc.ctypes.data, tables.ctypes.data, n, h, w, sampling, coef.ctypes.data,
-                                                  qt.ctypes.data, status.ctypes.data, subseq_bits, chunk_subseqs))
+    L.check(getattr(L.load(), c_name)(scan.ctypes.data, scan.size, desc.ctypes.data, tables.ctypes.data, n, h, w, sampling, coef.ctypes.data, qt.ctypes.data,
+                                      status.ctypes.data, subseq_bits, chunk_subseqs))
     return coef, qt, status
 
 
-def jpeg_entropy_device(scan: torch.Tensor, desc: torch.Tensor, tables: torch.Tensor, h: int, w: int, sampling: int, coef: Optional[torch.Tensor] = None,
-                        qt: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None, subseq_bits: int = 0):
-    """`mvldm_jpeg_entropy_device`: the prepared frames of `desc` int32 `[n, 4]` (packed scans uint8, tables uint8 `[n, JPEG_TABLE_BYTES]`, all
-    on the device) -> (coef int16 `[n, jpeg_coef_count]`, qt int16 `[n, 192]`, status int32 `[n, 4]` = reason, largest S, rounds, 0): what
-    `jpeg_decode_coefs` takes.  A memset and two launches; nothing is allocated when the three outputs are given, and nothing is read
-    back, so the call can be captured."""
+def jpeg_entropy_emul(scan: np.ndarray, desc: np.ndarray, tables: np.ndarray, h: int, w: int, sampling: int, coef: Optional[np.ndarray] = None,
+                      qt: Optional[np.ndarray] = None, status: Optional[np.ndarray] = None, subseq_bits: int = 0, chunk_subseqs: int = 0):
+    """the device entropy decoder on the host (`mvldm_jpeg_entropy_emul_host`: the same step function, loops for threads) over the
+    frames of `desc` int32 `[n, 4]` -> (coef int16 `[n, jpeg_coef_count]`, qt uint16 `[n, 192]`, status int32 `[n, 4]`): tests and tools"""
+    return _jpeg_entropy_emul("mvldm_jpeg_entropy_emul_host", scan, desc, tables, h, w, sampling, coef, qt, status, subseq_bits, chunk_subseqs)
+
+
+def _jpeg_entropy_device(c_name, scan, desc, tables, h, w, sampling, coef, qt, status, subseq_bits):
+    """the two device entropy calls: the C function `c_name` over the frames of `desc`; outputs left out are made"""
     n, count = desc.shape[0], jpeg_coef_count(h, w, sampling)
     assert scan.is_cuda and scan.is_contiguous() and scan.dtype == torch.uint8 and scan.dim() == 1
     assert desc.is_cuda and desc.is_contiguous() and desc.dtype == torch.int32 and tuple(desc.shape) == (n, 4)
@@ -1229,9 +1236,18 @@ def jpeg_entropy_device(scan: torch.Tensor, desc: torch.Tensor, tables: torch.Te
     assert coef.is_cuda and coef.is_contiguous() and coef.dtype == torch.int16 and tuple(coef.shape) == (n, count)
     assert qt.is_cuda and qt.is_contiguous() and qt.dtype == torch.int16 and tuple(qt.shape) == (n, 192)
     assert status.is_cuda and status.is_contiguous() and status.dtype == torch.int32 and tuple(status.shape) == (n, 4)
-    L.check(L.load().mvldm_jpeg_entropy_device(scan.data_ptr(), scan.numel(), desc.data_ptr(), tables.data_ptr(), n, h, w, sampling, coef.data_ptr(),
-                                               qt.data_ptr(), status.data_ptr(), subseq_bits, stream()))
+    L.check(getattr(L.load(), c_name)(scan.data_ptr(), scan.numel(), desc.data_ptr(), tables.data_ptr(), n, h, w, sampling, coef.data_ptr(), qt.data_ptr(),
+                                      status.data_ptr(), subseq_bits, stream()))
     return coef, qt, status
+
+
+def jpeg_entropy_device(scan: torch.Tensor, desc: torch.Tensor, tables: torch.Tensor, h: int, w: int, sampling: int, coef: Optional[torch.Tensor] = None,
+                        qt: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None, subseq_bits: int = 0):
+    """`mvldm_jpeg_entropy_device`: the prepared frames of `desc` int32 `[n, 4]` (packed scans uint8, tables uint8 `[n, JPEG_TABLE_BYTES]`, all
+    on the device) -> (coef int16 `[n, jpeg_coef_count]`, qt int16 `[n, 192]`, status int32 `[n, 4]` = reason, largest S, rounds, 0): what
+    `jpeg_decode_coefs` takes.  A memset and two launches; nothing is allocated when the three outputs are given, and nothing is read
+    back, so the call can be captured."""
+    return _jpeg_entropy_device("mvldm_jpeg_entropy_device", scan, desc, tables, h, w, sampling, coef, qt, status, subseq_bits)
 
 
 def jpeg_status_download(status: torch.Tensor) -> np.ndarray:
@@ -1256,38 +1272,14 @@ def jpeg_rst_prepare(blob: bytes, scan: Optional[np.ndarray] = None, scan_off: i
     and destuffed intervals -- into `scan[scan_off:]` (room for `jpeg_rst_need(blob)` bytes behind the offset, a multiple of 16), the
     descriptor (offset, intervals, bytes, MCUs per interval) into `desc` and the tables into `tables`: what `jpeg_rst_entropy_device`
     takes.  Never answers `_lib.JPEG_RESTART`.  Buffers left out are made.  Releases the GIL; keeps no state."""
-    if scan is None:
-        scan = np.zeros(scan_off + jpeg_rst_need(blob), dtype=np.uint8)
-    if desc is None:
-        desc = np.zeros(4, dtype=np.int32)
-    if tables is None:
-        tables = np.zeros(L.JPEG_TABLE_BYTES, dtype=np.uint8)
-    assert scan.dtype == np.uint8 and scan.flags.c_contiguous and scan.ndim == 1
-    assert desc.dtype == np.int32 and desc.flags.c_contiguous and desc.size == 4
-    assert tables.dtype == np.uint8 and tables.flags.c_contiguous and tables.size == L.JPEG_TABLE_BYTES
-    info = (C.c_int32 * 8)()
-    rc = L.load().mvldm_jpeg_rst_prepare(blob, len(blob), scan.ctypes.data, scan_off, scan.size, desc.ctypes.data, tables.ctypes.data, info)
-    if rc < 0:
-        L.check(rc)
-    return JpegScan(rc, JpegInfo(*info), scan, desc, tables)
+    return _jpeg_prepare("mvldm_jpeg_rst_prepare", lambda: jpeg_rst_need(blob), blob, scan, scan_off, desc, tables)
 
 
 def jpeg_rst_entropy_emul(scan: np.ndarray, desc: np.ndarray, tables: np.ndarray, h: int, w: int, sampling: int, coef: Optional[np.ndarray] = None,
                           qt: Optional[np.ndarray] = None, status: Optional[np.ndarray] = None, subseq_bits: int = 0, chunk_subseqs: int = 0):
     """`jpeg_entropy_emul` of the restart path (`mvldm_jpeg_rst_entropy_emul_host`) over the frames `jpeg_rst_prepare` laid down ->
     (coef, qt, status int32 `[n, 4]` = reason, largest S, rounds, intervals): tests and tools"""
-    desc, tables = desc.reshape(-1, 4), tables.reshape(-1, L.JPEG_TABLE_BYTES)
-    n, count = desc.shape[0], jpeg_coef_count(h, w, sampling)
-    assert scan.dtype == np.uint8 and scan.flags.c_contiguous and desc.dtype == np.int32 and desc.flags.c_contiguous
-    assert tables.dtype == np.uint8 and tables.flags.c_contiguous and tables.shape[0] == n and count > 0
-    coef = np.empty((n, count), dtype=np.int16) if coef is None else coef
-    qt = np.empty((n, 192), dtype=np.uint16) if qt is None else qt
-    status = np.empty((n, 4), dtype=np.int32) if status is None else status
-    assert coef.dtype == np.int16 and coef.flags.c_contiguous and coef.size == n * count and qt.dtype.itemsize == 2 and qt.flags.c_contiguous and qt.size == n * 192
-    assert status.dtype == np.int32 and status.flags.c_contiguous and status.size == n * 4
-    L.check(L.load().mvldm_jpeg_rst_entropy_emul_host(scan.ctypes.data, scan.size, desc.ctypes.data, tables.ctypes.data, n, h, w, sampling, coef.ctypes.data,
-                                                      qt.ctypes.data, status.ctypes.data, subseq_bits, chunk_subseqs))
-    return coef, qt, status
+    return _jpeg_entropy_emul("mvldm_jpeg_rst_entropy_emul_host", scan, desc, tables, h, w, sampling, coef, qt, status, subseq_bits, chunk_subseqs)
 
 
 def jpeg_rst_entropy_device(scan: torch.Tensor, desc: torch.Tensor, tables: torch.Tensor, h: int, w: int, sampling: int, coef: Optional[torch.Tensor] = None,
@@ -1295,19 +1287,7 @@ def jpeg_rst_entropy_device(scan: torch.Tensor, desc: torch.Tensor, tables: torc
     """`mvldm_jpeg_rst_entropy_device`: `jpeg_entropy_device` for the frames `jpeg_rst_prepare` laid down, with and without restart
     intervals -> (coef, qt, status int32 `[n, 4]` = reason, largest S, rounds, intervals).  A memset and two launches; nothing is
     allocated when the three outputs are given, and nothing is read back, so the call can be captured."""
-    n, count = desc.shape[0], jpeg_coef_count(h, w, sampling)
-    assert scan.is_cuda and scan.is_contiguous() and scan.dtype == torch.uint8 and scan.dim() == 1
-    assert desc.is_cuda and desc.is_contiguous() and desc.dtype == torch.int32 and tuple(desc.shape) == (n, 4)
-    assert tables.is_cuda and tables.is_contiguous() and tables.dtype == torch.uint8 and tuple(tables.shape) == (n, L.JPEG_TABLE_BYTES) and count > 0
-    coef = torch.empty(n, count, dtype=torch.int16, device=scan.device) if coef is None else coef
-    qt = torch.empty(n, 192, dtype=torch.int16, device=scan.device) if qt is None else qt
-    status = torch.empty(n, 4, dtype=torch.int32, device=scan.device) if status is None else status
-    assert coef.is_cuda and coef.is_contiguous() and coef.dtype == torch.int16 and tuple(coef.shape) == (n, count)
-    assert qt.is_cuda and qt.is_contiguous() and qt.dtype == torch.int16 and tuple(qt.shape) == (n, 192)
-    assert status.is_cuda and status.is_contiguous() and status.dtype == torch.int32 and tuple(status.shape) == (n, 4)
-    L.check(L.load().mvldm_jpeg_rst_entropy_device(scan.data_ptr(), scan.numel(), desc.data_ptr(), tables.data_ptr(), n, h, w, sampling, coef.data_ptr(),
-                                                   qt.data_ptr(), status.data_ptr(), subseq_bits, stream()))
-    return coef, qt, status
+    return _jpeg_entropy_device("mvldm_jpeg_rst_entropy_device", scan, desc, tables, h, w, sampling, coef, qt, status, subseq_bits)
 
 
 def _map(pool, f, xs) -> list:
@@ -1327,34 +1307,20 @@ def _jpeg_stage_host(blobs, members, info):
     return buf, jobs, lambda on_dev: (on_dev[:m * count].view(m, count), on_dev[m * count:].view(m, 192), None)
 
 
-def _jpeg_stage_device(blobs, members, info):
-    """[scans | tables | descriptors], filled by `jpeg_scan_prepare`; the coefficients are `jpeg_entropy_device`'s"""
+def _jpeg_stage_scans(room, prepare, entropy, blobs, members, info):
+    """[scans or regions | tables | descriptors]: `room(blob)` bytes a frame (a multiple of 16), filled by `prepare`; the coefficients are
+    `entropy`'s"""
     m, tb = len(members), L.JPEG_TABLE_BYTES
     offs = [0]
     for i in members:
-        offs.append(offs[-1] + jpeg_scan_room(len(blobs[i])))
+        offs.append(offs[-1] + room(blobs[i]))
     end = offs[-1]
     buf = torch.empty(end + m * (tb + 16), dtype=torch.uint8, pin_memory=True)
     host = buf.numpy()
     tables, desc = host[end:end + m * tb].reshape(m, tb), host[end + m * tb:].view(np.int32).reshape(m, 4)
-    jobs = [(jpeg_scan_prepare, blobs[i], host[:end], offs[j], desc[j], tables[j]) for j, i in enumerate(members)]
-    return buf, jobs, lambda on_dev: jpeg_entropy_device(on_dev[:end], on_dev[end + m * tb:].view(torch.int32).view(m, 4),
-                                                         on_dev[end:end + m * tb].view(m, tb), info.h, info.w, info.sampling)
-
-
-def _jpeg_stage_restart(blobs, members, info):
-    """[regions | tables | descriptors], filled by `jpeg_rst_prepare`; the coefficients are `jpeg_rst_entropy_device`'s"""
-    m, tb = len(members), L.JPEG_TABLE_BYTES
-    offs = [0]
-    for i in members:
-        offs.append(offs[-1] + jpeg_rst_need(blobs[i]))         # a multiple of 16: from the frame's header, not the bound for any frame
-    end = offs[-1]
-    buf = torch.empty(end + m * (tb + 16), dtype=torch.uint8, pin_memory=True)
-    host = buf.numpy()
-    tables, desc = host[end:end + m * tb].reshape(m, tb), host[end + m * tb:].view(np.int32).reshape(m, 4)
-    jobs = [(jpeg_rst_prepare, blobs[i], host[:offs[j + 1]], offs[j], desc[j], tables[j]) for j, i in enumerate(members)]
-    return buf, jobs, lambda on_dev: jpeg_rst_entropy_device(on_dev[:end], on_dev[end + m * tb:].view(torch.int32).view(m, 4),
-                                                             on_dev[end:end + m * tb].view(m, tb), info.h, info.w, info.sampling)
+    jobs = [(prepare, blobs[i], host[:offs[j + 1]], offs[j], desc[j], tables[j]) for j, i in enumerate(members)]
+    return buf, jobs, lambda on_dev: entropy(on_dev[:end], on_dev[end + m * tb:].view(torch.int32).view(m, 4), on_dev[end:end + m * tb].view(m, tb),
+                                             info.h, info.w, info.sampling)
 
 
 def jpeg_decode(blobs: Sequence[bytes], pool=None, device=None, entropy: str = "host", restarts: str = "host") -> torch.Tensor:
@@ -1382,7 +1348,12 @@ def jpeg_decode(blobs: Sequence[bytes], pool=None, device=None, entropy: str = "
         raise ValueError(f"jpeg_decode: entropy {entropy!r} (host or device)")
     if restarts not in ("host", "device") or (restarts == "device" and entropy != "device"):
         raise ValueError(f"jpeg_decode: restarts {restarts!r} with entropy {entropy!r} (host or device; device needs entropy=\"device\")")
-    stage = _jpeg_stage_host if entropy == "host" else _jpeg_stage_restart if restarts == "device" else _jpeg_stage_device
+    if entropy == "host":
+        stage = _jpeg_stage_host
+    elif restarts == "device":      # the room from the frame's header, not the bound for any frame
+        stage = functools.partial(_jpeg_stage_scans, jpeg_rst_need, jpeg_rst_prepare, jpeg_rst_entropy_device)
+    else:
+        stage = functools.partial(_jpeg_stage_scans, lambda blob: jpeg_scan_room(len(blob)), jpeg_scan_prepare, jpeg_entropy_device)
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     infos = [jpeg_probe(b) for b in blobs]
     groups: dict = {}

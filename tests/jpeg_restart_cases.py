@@ -22,6 +22,12 @@ def frames():
     ]
 
 
+def seam_case() -> bytes:
+    """264 x 264 noise, quality 50, 4:4:4, no DRI: the frame both device entropy paths take.  33 x 33 = 1089 blocks a component, so the
+    DC pass of either form runs a second pass of 1024 with a carry; about 4,700 subsequences of 32 bits, so the scan takes several chunks"""
+    return J.encode(J.pixels(264, 264, "noise"), quality=50, subsampling=0)
+
+
 def dri(blob: bytes) -> int:
     """the restart interval of the stream's DRI segment, 0 without one"""
     pos = 2

@@ -1,4 +1,4 @@
-"""CPU: the restart-interval kernels (csrc/jpeg_rst.hip) in the build's resource report.  A workgroup of 1024 leaves a lane 128 registers;
+"""CPU: the restart-interval kernels (csrc/jpeg_huff.hip) in the build's resource report.  A workgroup of 1024 leaves a lane 128 registers;
 the lane's description of its subsequence (pointer, bits, index, first lane, blocks) is scalars, and anything hipcc demotes to scratch
 would sit behind every symbol of a serial chain: each kernel once, zero scratch, zero spills."""
 import json

@@ -1,4 +1,4 @@
-"""GPU: the Huffman scan of frames with restart intervals decoded on the device (csrc/jpeg_rst.hip through `ops.jpeg_rst_entropy_device`)
+"""GPU: the Huffman scan of frames with restart intervals decoded on the device (csrc/jpeg_huff.hip through `ops.jpeg_rst_entropy_device`)
 against its host emulation and the host's Huffman decoder, `torch.equal` everywhere, then `ops.jpeg_decode(entropy="device",
 restarts="device")` and a reader end to end against Pillow.  The frames are those of tests/test_jpeg_restart_cpu.py, which pins the
 emulation (the kernels' own inline functions) to the host decoder without a device: run this file after that one passes."""
@@ -49,13 +49,13 @@ def _pack(ops, blobs, room=None):
     return scan, desc, tables, infos[0]
 
 
-def _device(ops, scan, desc, tables, info, subseq_bits=0):
-    """`jpeg_rst_entropy_device` with canaries around coef, qt and status -> host tensors"""
+def _device(ops, scan, desc, tables, info, subseq_bits=0, entry=None):
+    """`jpeg_rst_entropy_device` (or `entry`) with canaries around coef, qt and status -> host tensors"""
     n, count, pad = desc.shape[0], ops.jpeg_coef_count(info.h, info.w, info.sampling), 64
     bufs = [torch.full((n * k * size + 2 * pad,), CANARY, dtype=torch.uint8, device="cuda") for k, size in ((count, 2), (192, 2), (4, 4))]
     views = [b[pad:b.numel() - pad].view(dt).view(n, k) for b, dt, k in zip(bufs, (torch.int16, torch.int16, torch.int32), (count, 192, 4))]
-    ops.jpeg_rst_entropy_device(torch.from_numpy(scan).cuda(), torch.from_numpy(desc).cuda(), torch.from_numpy(tables).cuda(), info.h, info.w, info.sampling,
-                                *views, subseq_bits=subseq_bits)
+    (entry or ops.jpeg_rst_entropy_device)(torch.from_numpy(scan).cuda(), torch.from_numpy(desc).cuda(), torch.from_numpy(tables).cuda(), info.h, info.w,
+                                           info.sampling, *views, subseq_bits=subseq_bits)
     torch.cuda.synchronize()
     for b in bufs:
         assert (b[:pad] == CANARY).all() and (b[-pad:] == CANARY).all(), "a write outside coef, qt or status"
@@ -96,6 +96,31 @@ def test_three_frames_three_intervals(ops):
              J.encode(noise, quality=50, subsampling=2, optimize=True)]
     assert [R.dri(b) for b in blobs] == [1, 7, 0]
     _check(ops, blobs, "three")
+
+
+def test_both_paths_on_a_frame_without_dri(ops):
+    """`R.seam_case()` through `jpeg_entropy_device` and `jpeg_rst_entropy_device`, which share their passes: the same coefficients,
+    tables, reason, S and rounds, the host decoder's values, and each path's emulation on all four status words.  1089 blocks a
+    component: both DC passes carry into a second pass of 1024; at 32 bits the scan takes several chunks"""
+    blob = R.seam_case()
+    reason, max_s, hcoef, hqt = _host(ops, blob)
+    assert R.dri(blob) == 0 and reason == 0
+    scan, desc, tables, info = _pack(ops, [blob])
+    plain = ops.jpeg_scan_prepare(blob)
+    assert plain.reason == 0 and info.mcu_cols * info.mcu_rows == 1089
+    pscan, pdesc, ptables = plain.scan, plain.desc.reshape(1, 4), plain.tables.reshape(1, -1)
+    for sb in (32, 0):
+        got = {"restart": _device(ops, scan, desc, tables, info, sb), "plain": _device(ops, pscan, pdesc, ptables, info, sb, entry=ops.jpeg_entropy_device)}
+        emul = {"restart": ops.jpeg_rst_entropy_emul(scan, desc, tables, info.h, info.w, info.sampling, subseq_bits=sb),
+                "plain": ops.jpeg_entropy_emul(pscan, pdesc, ptables, info.h, info.w, info.sampling, subseq_bits=sb)}
+        (pc, pq, ps), (rc, rq, rs) = got["plain"], got["restart"]
+        assert torch.equal(pc, rc) and torch.equal(pq, rq) and torch.equal(ps[:, :3], rs[:, :3]), (sb, ps, rs)
+        for path, (coef, qt, status) in got.items():
+            assert (int(status[0, 0]), int(status[0, 1])) == (reason, max_s), (path, sb, status)
+            assert torch.equal(coef[0], torch.from_numpy(hcoef)) and torch.equal(qt[0], torch.from_numpy(hqt.view(np.int16))), (path, sb)
+            assert torch.equal(status, torch.from_numpy(emul[path][2])), (path, sb, status, emul[path][2])
+            assert torch.equal(coef, torch.from_numpy(emul[path][0])) and torch.equal(qt, torch.from_numpy(emul[path][1].view(np.int16))), (path, sb)
+        assert got["plain"][2][0, 3] == 0 and got["restart"][2][0, 3] == 1
 
 
 def test_range_guard(ops):

@@ -1,5 +1,5 @@
 """CPU: the restart-interval path of the device entropy decoder on the host -- `ops.jpeg_rst_prepare` (csrc/jpeg_host.cpp) and
-`ops.jpeg_rst_entropy_emul`, the emulation that runs jpeg_rst.hip's own inline functions (csrc/jpeg_huff_common.h) with loops for
+`ops.jpeg_rst_entropy_emul`, the emulation that runs jpeg_huff.hip's own inline functions (csrc/jpeg_huff_common.h) with loops for
 threads -- against the host's Huffman decoder `ops.jpeg_entropy`, `np.array_equal` everywhere, canaries around every buffer.
 Frames: tests/jpeg_restart_cases.py."""
 import numpy as np
@@ -146,6 +146,24 @@ def test_a_frame_without_dri_equals_the_existing_emulation(ops):
         got = emulate(ops, p, info, sb, chunk)
         assert got[:3] == tuple(int(v) for v in want[2][0, :3])              # reason, S and rounds: one interval is the frame's walk
         assert np.array_equal(got[4], want[0][0]) and np.array_equal(got[5], want[1][0])
+
+
+def test_the_two_emulations_agree_on_a_frame_of_several_chunks(ops):
+    """`R.seam_case()`: the host decoder accepts it under the guard, and both emulations give its values at chunks of 4 and of 1024 --
+    more than one chunk of the scan and a carry in the DC pass"""
+    blob = R.seam_case()
+    reason, max_s, coef, qt, info = host(ops, blob)
+    assert R.dri(blob) == 0 and reason == 0 and 0 < max_s <= 5905 and (info.h, info.w, info.sampling) == (264, 264, 1)
+    assert info.mcu_cols * info.mcu_rows == 1089 > 1024
+    old, p = ops.jpeg_scan_prepare(blob), prepare(ops, blob)
+    assert old.reason == p.reason == 0 and p.desc[1] == 1 and p.desc[3] == 1089
+    assert old.desc[1] > 4 * 1024 * 32                                          # bits: more than four chunks of 1024 at 32 bits
+    for sb, chunk in [(32, 4), (32, 1024), (0, 4), (0, 1024)]:
+        want = ops.jpeg_entropy_emul(old.scan, old.desc, old.tables, info.h, info.w, info.sampling, subseq_bits=sb, chunk_subseqs=chunk)
+        got = emulate(ops, p, info, sb, chunk)
+        assert tuple(int(v) for v in want[2][0]) == (0, max_s, got[2], 0) and got[:2] == (0, max_s) and got[3] == 1, (sb, chunk, want[2], got[:4])
+        for c, q in ((want[0][0], want[1][0]), (got[4], got[5])):
+            assert np.array_equal(c, coef) and np.array_equal(q, qt), (sb, chunk)
 
 
 def test_fill_byte_in_front_of_a_marker(ops):

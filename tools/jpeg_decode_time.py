@@ -13,7 +13,7 @@ luma block is flat) and "photo" (smooth ramps plus +-12 of noise: every block ha
     pool of 16 threads (wall time of 30 frames / 30) and `mvldm_jpeg_scan_prepare` on one thread.  Coefficients are checked against the
     host's before anything is timed.
   * `--restarts`: the same pixels re-encoded with `restart_marker_rows=1` (one restart interval per MCU row: 23 of 40 MCUs) through
-    `mvldm_jpeg_rst_entropy_device` (csrc/jpeg_rst.hip): per subseq_bits in 128, 256, 512, 1024 and n = 5, 30 the hot / cold microseconds
+    `mvldm_jpeg_rst_entropy_device` (csrc/jpeg_huff.hip): per subseq_bits in 128, 256, 512, 1024 and n = 5, 30 the hot / cold microseconds
     per frame and the rounds of the worst chunk; next to it, IN THE SAME RUN, `mvldm_jpeg_entropy_device` on the stream without markers,
     the host's entropy pass of the restart stream on one thread and over 16 workers, `mvldm_jpeg_rst_prepare` on one thread and the bytes
     uploaded per frame.  Coefficients are checked against the host's before anything is timed.  The same again under
