@@ -8,7 +8,8 @@
 // (coalesced 16-byte global loads, zeros for padding taps / rows past M / columns past n_out) and consumed through the
 // LDS transpose read ds_read_b64_tr_b16, which hands a lane 4 consecutive PIXELS of its own column -- exactly the
 // K-major fragment of v_mfma_f32_32x32x16_{bf16,f16} (both operands see the same pixel permutation, so the
-// contraction is exact).  fp32: v_mfma_f32_32x32x2_f32 reads its scalars straight from the row-major tiles.
+// contraction is exact).  fp32: v_mfma_f32_32x32x2_f32 reads its scalars straight from the row-major tiles and sums 16 pixels
+// into a partial before adding it, so that every dtype accumulates in fp32 in steps of 16 pixels.
 // Register prefetch of the next pixel block overlaps the MFMAs of the current one.
 //
 // The pixel range is split over gridDim.z (split-K) so that small layers still fill 256 CUs; every split writes its
@@ -90,7 +91,8 @@ constexpr int wg_tr_pitch(int cols) {        // elements (16-bit)
 }
 
 template <typename T>
-__global__ __launch_bounds__(256) void wgrad_kernel(const WgradParams p) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(std::is_same<T, float>::value ? 3 : 1)))
+void wgrad_kernel(const WgradParams p) {
     constexpr bool F32 = std::is_same<T, float>::value;
     constexpr int EPC = Elt<T>::EPC;
     // row pitches (elements): a transpose-read half-wave touches 4 pixel rows x two 32-byte column pieces, conflict-free when the
@@ -178,12 +180,24 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const WgradParams p) {
         __syncthreads();
         if (m0 + WG_BP < m_end) load(m0 + WG_BP);
         if constexpr (F32) {
-#pragma unroll 8
-            for (int kk = 0; kk < WG_BP / 2; ++kk) {
-                const int px = 2 * kk + hi;
-                const float a = s_d[px * PD + wave * 32 + l31];
+            // 16 pixels (8 MFMAs of K = 2) go into a fresh partial that is then added once: the same "fp32 accumulation in steps of 16
+            // pixels" as the 16-bit MFMAs below.  One chain of K = 2 steps over the whole split made 8 x as many dependent fp32
+            // additions and left the worst element at 1.5 x its bound (tests/test_hip_wgrad_edges.py, "Found by this module").
+#pragma unroll 1
+            for (int g = 0; g < WG_BP / 16; ++g) {
+                float a[8];
 #pragma unroll
-                for (int j = 0; j < 2; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, s_x[px * PX + j * 32 + l31], acc[j], 0, 0, 0);
+                for (int kk = 0; kk < 8; ++kk) a[kk] = s_d[(16 * g + 2 * kk + hi) * PD + wave * 32 + l31];
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {          // one 32-column block after the other: one partial (16 registers) at a time
+                    f32x16 part;
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) part[r] = 0.f;
+#pragma unroll
+                    for (int kk = 0; kk < 8; ++kk)
+                        part = __builtin_amdgcn_mfma_f32_32x32x2f32(a[kk], s_x[(16 * g + 2 * kk + hi) * PX + j * 32 + l31], part, 0, 0, 0);
+                    acc[j] += part;
+                }
             }
         } else {
             // transpose-read source of this lane: pixel row 4*(gi>>1) + (sl>>2) (+8 for the upper half), columns

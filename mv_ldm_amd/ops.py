@@ -501,9 +501,11 @@ def ddpm_cfg_step(eps_c, eps_u, x_t, noise, cfg_scale, coef, clip_range: float =
 
 # ------------------------------------------------------------------------------------------ training kernels
 def wgrad_desc(x, x2, dy, grad, ws, *, h_out, w_out, ksize, stride, pad, upsample, n_out, c_in=None, accumulate=False, form: int = 0,
-               into=None) -> L.WgradDesc:
+               target: int = 0, into=None) -> L.WgradDesc:
     """the one place a weight-gradient descriptor is filled (`into=op.u.wgrad` for a plan).  `ws`: uint8 slab workspace;
-    form: 0 = the library's rule, 1 = register-staged small tile, 2 = wide LDS-DMA tile (bits 8-9 of `accumulate`)"""
+    form: 0 = the library's rule, 1 = register-staged small tile, 2 = wide LDS-DMA tile (bits 8-9 of `accumulate`);
+    target: workgroup target of the pixel split, 0 = the library's, else 64 << target (bits 10-12, as plan.autotune_wgrad writes them)"""
+    assert 0 <= int(form) <= 3 and 0 <= int(target) <= 7, (form, target)
     d = L.WgradDesc() if into is None else into
     n, h, w, c0 = x.shape
     c1 = 0 if x2 is None else x2.shape[-1]
@@ -512,13 +514,15 @@ def wgrad_desc(x, x2, dy, grad, ws, *, h_out, w_out, ksize, stride, pad, upsampl
     d.c0, d.c1, d.c_in = c0, c1, (c0 + c1) if c_in is None else c_in
     d.n_img, d.h_in, d.w_in, d.h_out, d.w_out = n, h, w, h_out, w_out
     d.ksize, d.stride, d.pad, d.upsample = ksize, stride, pad, int(upsample)
-    d.n_out, d.dy_ld, d.act_dtype, d.accumulate = n_out, dy.stride(-2), dt(x), int(accumulate) | (int(form) << 8)
+    d.n_out, d.dy_ld, d.act_dtype, d.accumulate = n_out, dy.stride(-2), dt(x), int(accumulate) | (int(form) << 8) | (int(target) << 10)
     return d
 
 
-def conv_wgrad(x, dy, grad, *, ksize, stride=1, pad=None, upsample=False, x2=None, c_in=None, accumulate=False, n_out=None, form: int = 0) -> torch.Tensor:
+def conv_wgrad(x, dy, grad, *, ksize, stride=1, pad=None, upsample=False, x2=None, c_in=None, accumulate=False, n_out=None, form: int = 0,
+               target: int = 0, ws=None) -> torch.Tensor:
     """x (x2): NHWC forward input(s); dy: NHWC / `[m, ld]` upstream gradient (columns [0, n_out)); grad: fp32 PyTorch-layout
-    weight gradient `[n_out, c_in, k, k]` / `[n_out, c_in]`, written or accumulated in place."""
+    weight gradient `[n_out, c_in, k, k]` / `[n_out, c_in]`, written or accumulated in place.  `ws`: a caller-owned uint8 slab
+    workspace (its size caps the split count); default: the shared one, 8 slabs."""
     n, h, w, c0 = x.shape
     c1 = 0 if x2 is None else x2.shape[-1]
     pad = ksize // 2 if pad is None else pad
@@ -526,9 +530,13 @@ def conv_wgrad(x, dy, grad, *, ksize, stride=1, pad=None, upsample=False, x2=Non
     ho, wo = (hs + 2 * pad - ksize) // stride + 1, (ws_ + 2 * pad - ksize) // stride + 1
     n_out = grad.shape[0] if n_out is None else n_out
     need = n_out * ksize * ksize * (c0 + c1) * 4
-    scratch = workspace(min(max(need * 8, 1 << 20), max(need, 512 << 20)), x.device, "wgrad")
+    if ws is None:
+        scratch = workspace(min(max(need * 8, 1 << 20), max(need, 512 << 20)), x.device, "wgrad")
+    else:
+        assert ws.is_cuda and ws.dtype == torch.uint8 and ws.is_contiguous() and ws.data_ptr() % 16 == 0
+        scratch = ws
     d = wgrad_desc(x, x2, dy, grad, scratch, h_out=ho, w_out=wo, ksize=ksize, stride=stride, pad=pad, upsample=upsample, n_out=n_out,
-                   c_in=c_in, accumulate=accumulate, form=form)
+                   c_in=c_in, accumulate=accumulate, form=form, target=target)
     L.check(L.load().mvldm_igemm_wgrad(C.byref(d), stream()))
     return grad
 

@@ -10,7 +10,13 @@ test_hip_backward.py (small-shape tests) and test_hip_backward_edges.py.
     fp32 statistics          the attention log-sum-exp, `out` in the activation type, (mean, rstd) of the norms
     GELU                     the A-S 7.1.26 erf polynomial of common.h (|error| <= 1.5e-7)
 
-`python tests/grad_emulation.py` prints max|emulation - fp64| / rms(fp64) per (kind, dtype) and 3 x that value, the bound."""
+`python tests/grad_emulation.py` prints max|emulation - fp64| / rms(fp64) per (kind, dtype) and 3 x that value, the bound.
+
+A further kind, `wgrad_long`, does the same for the split weight gradients of test_hip_wgrad_edges.py, whose sums are up to 4096 pixels long:
+products of the dtype-rounded operands, fp32 accumulation over the pixel index in steps of 16, one partial per split of `rows_per_split`
+rows (the launch rule restated in that module), partials added in split order in fp32, the accumulate case added onto the previous
+gradient.  Its rows give the worst element / RMS and the relative L2 per case family and dtype, over every launch of the family."""
+import functools
 import math
 import sys
 from pathlib import Path
@@ -22,6 +28,7 @@ sys.path.insert(0, str(Path(__file__).resolve().parent))
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 import test_hip_backward as B       # noqa: E402
 import test_hip_backward_edges as E  # noqa: E402
+import test_hip_wgrad_edges as W  # noqa: E402
 from test_hip_backward_edges import G, rnd, worst_over_rms  # noqa: E402
 
 DTYPES, IDS = E.DTYPES, E.IDS
@@ -220,6 +227,41 @@ def worst_gemm(dtype):
     return wd, ww
 
 
+# ------------------------------------------------------------------------------------------------ long weight-gradient sums
+@functools.lru_cache(maxsize=None)
+def im2col(name, dtype):
+    """-> (A [M, c * k * k] in PyTorch's (c, ky, kx) column order, dY [M, n_out]) of a case of test_hip_wgrad_edges.py, fp32"""
+    k = W.case(name, dtype)
+    xin = F.interpolate(k["x"], scale_factor=2, mode="nearest") if k["up"] else k["x"]
+    a = F.unfold(xin, k["ks"], padding=k["pad"], stride=k["stride"])              # [n, c * k * k, h_out * w_out]
+    return a.permute(0, 2, 1).reshape(-1, a.shape[1]).contiguous(), k["dy"].permute(0, 2, 3, 1).reshape(-1, k["co"]).contiguous()
+
+
+def emu_wgrad_long(name, dtype, rps, accumulate):
+    """one fp32 partial per split of `rps` pixel rows, each accumulated in steps of 16 pixels; partials added in split order"""
+    k = W.case(name, dtype)
+    a, d = im2col(name, dtype)
+    total = None
+    for m0 in range(0, a.shape[0], rps):
+        part = mm(d[m0:m0 + rps].t(), a[m0:m0 + rps], step=16)
+        total = part if total is None else total + part
+    total = total.view(k["gw"].shape)
+    return k["g0"] + total if accumulate else total
+
+
+def wgrad_long_table():
+    """family -> per dtype (worst element / RMS, relative L2), the maximum over the family's launches"""
+    rows = {}
+    for dtype in DTYPES:
+        for family, name, rps, accumulate in W.emulation_runs(dtype):
+            k = W.case(name, dtype)
+            ref = k["g0"].double() + k["gw"] if accumulate else k["gw"]
+            l2, worst = W.errors(emu_wgrad_long(name, dtype, rps, accumulate), ref)
+            cur = rows.setdefault(family, {}).setdefault(dtype, (0.0, 0.0))
+            rows[family][dtype] = (max(cur[0], worst), max(cur[1], l2))
+    return rows
+
+
 # ------------------------------------------------------------------------------------------------ elementwise
 def erf_as(x):
     """common.h erf_as_f: Abramowitz-Stegun 7.1.26 in fp32"""
@@ -286,3 +328,12 @@ if __name__ == "__main__":
     print(f"{'kind':10s}" + "".join(f"{i:>11s}" for i in IDS) + "   |" + "".join(f"{'3x ' + i:>11s}" for i in IDS))
     for kind, vals in table().items():
         print(f"{kind:10s}" + "".join(f"{v:11.2e}" for v in vals) + "   |" + "".join(f"{3 * v:11.2e}" for v in vals))
+    print()
+    print(f"{'wgrad_long':13s}{'longest sum':16s}{'emulated worst element / RMS':34s}{'emulated relative L2':34s}{'bound: worst (3 x)':34s}bound: rel. L2 (3 x)")
+    print(f"{'family':13s}{'(pixels)':13s}" + "".join("".join(f"{i:>10s}" for i in IDS) + "    " for _ in range(4)).rstrip())
+    long_rows = wgrad_long_table()
+    for family in W.EMU:                # (a family that no test runs in a dtype has no value there)
+        line = f"{family:13s}{W.EMU[family]['longest']:<13d}"
+        for f in (lambda v: v[0], lambda v: v[1], lambda v: 3 * v[0], lambda v: 3 * v[1]):
+            line += "".join(f"{f(long_rows[family][t]):10.2e}" if t in long_rows[family] else f"{'-':>10s}" for t in DTYPES) + "    "
+        print(line.rstrip())
