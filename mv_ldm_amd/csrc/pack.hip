@@ -35,9 +35,9 @@ __device__ __forceinline__ void pack_generic_body(const mvldm_pack_job& j, int b
             // data-gradient weight: row np = input channel c_off + np, K channel `c` = OUTPUT channel, taps flipped
             if (np < j.n_rows && tap < taps && c < j.n_out)
                 v = src[((size_t)c * j.c_in + (j.c_off + np)) * taps + (taps - 1 - tap)];
-        } else {
+        } else if (np < j.n_out) {      // padding rows are zero (the GEGLU interleave would map some of them back into the weight)
             const int n = orig_col(np, j.n_out, j.geglu != 0);
-            if (n < j.n_out && tap < taps && c < j.c_in)
+            if (tap < taps && c < j.c_in)
                 v = src[((size_t)n * j.c_in + c) * taps + tap];
         }
         dst[idx] = from_f32<T>(v);
@@ -59,7 +59,7 @@ __device__ __forceinline__ void pack_fwd_k1_body(const mvldm_pack_job& j, int bx
         const int np = (int)(idx / kq), k = (int)(idx - (size_t)np * kq) * 4;
         const int n = orig_col(np, j.n_out, j.geglu != 0);
         float v[4] = {0.f, 0.f, 0.f, 0.f};
-        if (n < j.n_out) {
+        if (np < j.n_out) {      // padding rows are zero (the GEGLU interleave would map some of them back into the weight)
             const float* sp = src + (size_t)n * j.c_in + k;
             if (k + 3 < j.c_in && (((size_t)n * j.c_in + k) & 3) == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0) {
                 const f32x4 q = *reinterpret_cast<const f32x4*>(sp);
@@ -195,8 +195,9 @@ static int pack_job_prepare(mvldm_pack_job& j, int dst_dtype) {
     j.kind = PACK_GENERIC;
     j.blocks = (int)std::min<size_t>((total + 255) / 256, 65535);
     const int taps = j.ksize * j.ksize;
-    // block-major 16-bit layout: the LDS-tiled packers (same bytes out as the generic body)
-    if (dst_dtype != MVLDM_F32 && j.k_order == 1 && j.c_pad % 64 == 0 && j.k_pad == taps * j.c_pad && (j.ksize == 1 || j.ksize == 3)) {
+    // block-major 16-bit layout: the LDS-tiled packers (same bytes out as the generic body).  Only the 1x1 one interleaves GEGLU rows.
+    if (dst_dtype != MVLDM_F32 && j.k_order == 1 && j.c_pad % 64 == 0 && j.k_pad == taps * j.c_pad && (j.ksize == 1 || j.ksize == 3) &&
+        !(j.geglu && j.ksize != 1)) {
         if (j.transpose) {
             const int rb = j.ksize == 3 ? 8 : 64;
             j.kind = j.ksize == 3 ? PACK_T_K3 : PACK_T_K1;
